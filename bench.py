@@ -18,7 +18,16 @@ checking slice r against its replica (no collective on the data path): the node 
 times every rank on its own 64K requests beside it. Configs 2, 3 run the same way; 5
 (``--config mixed``) checks a device-resident batch per rank and step beside its Watch batch.
 
-Also printed: the roofline of the dominant kernel (SURVEY.md §8d algorithmic bytes of a batch,
+A plain run (``--gpus 1 --steps N --warmup W``) does what `value` needs and no more: it builds the
+graph, warms up, times the N device-resident steps, writes their last results with
+``--dump-outputs DIR`` and prints the line (the timed requests are checked once, untimed, before
+the warm-up, as the host-buffer region has checked them with ``--full``; beyond 4,096 batches such a
+run cycles through 4,096 distinct requests). Everything else described here (the host-buffer phases
+`baseline_pipelined` / `baseline_step` / `host_buffers`, the uniform format, `weak_scaling` and
+`coalesced`, the solo launches and the roofline, the oracle comparison and the CPU baseline) runs
+with ``--full``.
+
+Also printed with ``--full``: the roofline of the dominant kernel (SURVEY.md §8d algorithmic bytes of a batch,
 counted by the oracle's counting mode, / the mean stage-A launch time of device-resident batches
 one at a time after the timed region, from the queue's dispatch timestamps; `traffic` = HBM bytes
 per batch from rocprofv3 PMC), the host link's share (`pcie`), the process's placement on the
@@ -40,6 +49,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X spec (MI355X_MICROARCH.md: 8.0 TB/s)
 BATCH = 65536
+ROT_MAX = 4096  # distinct pre-generated requests of a run without --full (5.4 GB of items at batch 64K)
 
 
 def parse():
@@ -112,7 +122,20 @@ def parse():
                          "on the engine's staging threads beside the apply; a consumer holding that many further "
                          "responses); 0 = gck_apply_updates")
     ap.add_argument("--scale", type=float, default=1.0, help="configs 2 / 3: 1.0 = 10M / 100M tuples")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the host-buffer (PCIe-inclusive) phases, the uniform "
+                         "format, weak scaling / coalescing (N > 1), the solo launches and the roofline, the oracle "
+                         "comparison and the CPU baseline. Without it a run sets up, warms up, times --steps steps of "
+                         "`value`'s path and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what `value`'s path computed in its last step (perm, err: the "
+                         "arrays a caller receives) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if not args.full:
+        if args.trace_loop:
+            ap.error("--trace-loop records the host-buffer loop: it needs --full")
+        args.no_oracle = args.no_cpu = True
+        args.host_steps = 0
     nested = args.config == "nested"
     pipelined = args.config in ("nested", "gdocs", "github")  # batches in flight through the compiled loop
     if args.steps is None:
@@ -389,6 +412,24 @@ def progress(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: `arrays` (name -> device tensor or numpy array) as path/<name>.npy in float32
+    (rank r > 0 of several: <name>.rank<r>.npy). Arrays that together exceed 64 MB are cut to a
+    fixed, seeded sample of their elements (the same indices every run, in ascending order)."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)).reshape(-1)
+            for k, v in arrays.items()}
+    cap = DUMP_MAX_BYTES // 4 // max(1, len(host))  # float32 elements per array
+    for name, a in host.items():
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(20251003).choice(a.size, size=cap, replace=False))]
+        suffix = ".npy" if world == 1 or rank == 0 else f".rank{rank}.npy"
+        np.save(os.path.join(path, name + suffix), a.astype(np.float32))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -453,6 +494,9 @@ def main():
     stream = torch.cuda.current_stream(dev).cuda_stream
     run_steps = None  # the nested workload's compiled submit/wait loop (--driver native)
     loop_s = {"s": None}  # the compiled loop's own wall time of the last phase (first submit to last wait)
+    # without --full the pipelined configs time `value`'s own phase alone (device-resident, below): no
+    # host-buffer copies of the requests and no host-buffer timed region
+    lean_dev = False
     if args.partitioned:
         # one global batch: every rank's 64K checks, the same items on every rank
         from gochugaru_amd.partition import PartitionedChecker, RcclPartitionedChecker
@@ -569,7 +613,12 @@ def main():
         from gochugaru_amd.sharded import slices
         s_lo, s_hi = slices(args.batch, world)[rank]
         n_slice = s_hi - s_lo
+        lean_dev = not args.full and args.driver == "native"
         n_rot = args.warm + args.steps
+        if lean_dev and args.coalesce == 1:
+            # (a run without --full of more batches than ROT_MAX cycles through ROT_MAX distinct
+            # requests, a working set far beyond the caches: its setup time and memory stay bounded)
+            n_rot = min(n_rot, ROT_MAX)
         # (one device array for every rotated slice and one per result plane: a rank's slices of
         # consecutive requests lie back to back, so several can go in one dispatch)
         rot_all = torch.cat([WL.checks(args.batch, 1000 + k)[s_lo:s_hi] for k in range(n_rot)]).contiguous()
@@ -586,15 +635,16 @@ def main():
         coal = max(1, min(args.coalesce, coal_max))
         coal_for = lambda count, cap=None: max(c for c in range(1, (cap or coal) + 1) if count % c == 0)
         streams = [torch.cuda.Stream(dev) for _ in range(depth)]
-        # `value`'s path (BASELINE.md:40-41, SURVEY §8d: items H2D + kernels + results D2H): the
+        # BASELINE's path (BASELINE.md:40-41, SURVEY §8d: items H2D + kernels + results D2H): the
         # same requests in host memory — pinned, from gck_host_alloc, where a cgo caller builds its
         # requests — and the results back into host memory. One allocation per array, every
         # batch its own slice (no step re-reads a batch another step read).
-        h_items = eng.host_array(n_rot * n_slice, ITEM_DTYPE)
-        h_perm = eng.host_array(n_rot * n_slice, np.uint8)
-        h_err = eng.host_array(n_rot * n_slice, np.int32)
-        for k in range(n_rot):
-            h_items[k * n_slice:(k + 1) * n_slice] = rot[k].cpu().numpy().view(ITEM_DTYPE).reshape(-1)
+        if not lean_dev:
+            h_items = eng.host_array(n_rot * n_slice, ITEM_DTYPE)
+            h_perm = eng.host_array(n_rot * n_slice, np.uint8)
+            h_err = eng.host_array(n_rot * n_slice, np.int32)
+            for k in range(n_rot):
+                h_items[k * n_slice:(k + 1) * n_slice] = rot[k].cpu().numpy().view(ITEM_DTYPE).reshape(-1)
         h_ptr = lambda a, k: a.ctypes.data + k * n_slice * a.itemsize
         torch.cuda.synchronize()
         cursor = {"k": 0}
@@ -612,7 +662,7 @@ def main():
             while pending:
                 pending.popleft().wait()
 
-        if args.driver == "native":
+        if args.driver == "native" and not lean_dev:
             # the same submit/wait loop, run by the compiled caller (libgck_driver.so) over the
             # steps of one phase: run_steps(count) checks the next `count` rotated batches; the
             # loop's arguments are marshalled before the phase (prepare), so a timed phase is the C
@@ -637,45 +687,46 @@ def main():
             prepare(args.steps)
 
     native = run_steps is not None
-    if native:
-        run_steps(args.warm)
-    else:
-        for _ in range(args.warm):
-            step()
-    if WL.kind != "quota" and not args.partitioned:
-        drain()
-    torch.cuda.synchronize()
-    eng.reset_stats()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    trace = None
-    if native and args.trace_loop:  # per-batch submit / wait return times of the timed loop
-        from gochugaru_amd.engine import _driver
-        import ctypes
-        trace = np.zeros(2 * args.steps, dtype=np.float64)
-        _driver().gckd_set_trace(trace.ctypes.data_as(ctypes.c_void_p), args.steps)
-    if WL.kind == "mixed":
-        rev["apply_s"] = rev["submit_s"] = rev["wait_s"] = 0.0  # (the Watch share is of the timed steps only)
-    t0 = time.perf_counter()
-    if native:
-        run_steps(args.steps)
-    else:
-        for _ in range(args.steps):
-            step()
-    if WL.kind != "quota" and not args.partitioned:
-        drain()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
-    if WL.kind == "mixed":
-        rev["apply_timed"], rev["submit_timed"], rev["wait_timed"] = rev["apply_s"], rev["submit_s"], rev["wait_s"]
-    if trace is not None:
-        _driver().gckd_set_trace(None, 0)
-    progress(f"timed region: {args.steps} steps in {elapsed * 1e3:.2f} ms"
-             + (f" (compiled loop {loop_s['s'] * 1e3:.3f} ms)" if native else ""))
-    pipelined = native and WL.kind in ("nested", "gdocs", "github") and not args.partitioned
+    elapsed = trace = None
+    if not lean_dev:
+        if native:
+            run_steps(args.warm)
+        else:
+            for _ in range(args.warm):
+                step()
+        if WL.kind != "quota" and not args.partitioned:
+            drain()
+        torch.cuda.synchronize()
+        eng.reset_stats()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        if native and args.trace_loop:  # per-batch submit / wait return times of the timed loop
+            from gochugaru_amd.engine import _driver
+            import ctypes
+            trace = np.zeros(2 * args.steps, dtype=np.float64)
+            _driver().gckd_set_trace(trace.ctypes.data_as(ctypes.c_void_p), args.steps)
+        if WL.kind == "mixed":
+            rev["apply_s"] = rev["submit_s"] = rev["wait_s"] = 0.0  # (the Watch share is of the timed steps only)
+        t0 = time.perf_counter()
+        if native:
+            run_steps(args.steps)
+        else:
+            for _ in range(args.steps):
+                step()
+        if WL.kind != "quota" and not args.partitioned:
+            drain()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        elapsed = time.perf_counter() - t0
+        if WL.kind == "mixed":
+            rev["apply_timed"], rev["submit_timed"], rev["wait_timed"] = rev["apply_s"], rev["submit_s"], rev["wait_s"]
+        if trace is not None:
+            _driver().gckd_set_trace(None, 0)
+        progress(f"timed region: {args.steps} steps in {elapsed * 1e3:.2f} ms"
+                 + (f" (compiled loop {loop_s['s'] * 1e3:.3f} ms)" if native else ""))
+    pipelined = (native or lean_dev) and WL.kind in ("nested", "gdocs", "github") and not args.partitioned
     # the same requests device-resident (items already in HBM, results left there): `value`, what
     # the engine sustains without the PCIe transfers. The timed batches again, after warm-up batches
     # of their own, on the engine's streams.
@@ -683,15 +734,23 @@ def main():
     if pipelined:
         def mkd(k0, count, cap=None):
             cc = coal_for(count, cap)
-            ks = range(k0, k0 + count, cc)
+            ks = [k % n_rot for k in range(k0, k0 + count, cc)]
             return eng.prepare_batches([rot[k].data_ptr() for k in ks], [outs[k][0].data_ptr() for k in ks],
                                        [outs[k][1].data_ptr() for k in ks], n_slice * cc, depth,
                                        [streams[j % depth].cuda_stream for j in range(len(ks))],
                                        engine_streams=bool(args.engine_streams))
         d_warm, d_run = mkd(0, args.warm), mkd(args.warm, args.steps)
         torch.cuda.synchronize()
+        if lean_dev:
+            # with --full the host-buffer region above has checked the timed requests once before this
+            # phase checks them again; without it they are checked once here, untimed, so that
+            # `value` is the rate of a second pass either way
+            mkd(args.warm, min(args.steps, n_rot)).run()
+            torch.cuda.synchronize()
         d_warm.run()
         torch.cuda.synchronize()
+        if lean_dev:  # (--full: the engine's counters cover the host-buffer timed region too)
+            eng.reset_stats()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -711,11 +770,25 @@ def main():
                            "note": "the same rotated requests with the items already in HBM and the results left "
                                    "there (no PCIe in the step): `value`"}
         progress(f"device-resident phase: {td * 1e3:.2f} ms")
+    if args.dump_outputs:
+        # what `value`'s path computed in its last timed step: the result arrays its caller receives
+        k_last = args.warm + args.steps - 1
+        if device_resident is not None:
+            last = outs[k_last % n_rot]
+        elif args.partitioned:
+            last = (out["perm"], out["err"])
+        elif WL.kind == "mixed":
+            last = (perm, err)
+        elif WL.kind == "quota":
+            last = q_out[k_last]
+        else:  # (--driver python: the host-buffer region is `value`)
+            last = (h_perm[k_last * n_slice:(k_last + 1) * n_slice], h_err[k_last * n_slice:(k_last + 1) * n_slice])
+        dump_outputs(args.dump_outputs, {"perm": last[0], "err": last[1]}, rank, world)
     # N > 1: the same device-resident requests with a rank's slices of N consecutive requests in one
     # dispatch (what a node-level dispatcher that aggregates per GPU would do): N x the per-request
     # latency, so reported beside `value`, never as it
     coalesced = None
-    if pipelined and world > 1 and args.coalesce == 1 and coal_max > 1:
+    if args.full and pipelined and world > 1 and args.coalesce == 1 and coal_max > 1:
         c_warm, c_run = mkd(0, args.warm, coal_max), mkd(args.warm, args.steps, coal_max)
         torch.cuda.synchronize()
         c_warm.run()
@@ -740,7 +813,7 @@ def main():
     # weak scaling beside the node figure (N > 1): every rank checks its own whole requests (host
     # buffers, as `value`)
     weak = None
-    if pipelined and world > 1:
+    if args.full and pipelined and world > 1:
         n_w = min(args.steps, 500)
         n_wr = n_w + 2 * depth
         w_items = eng.host_array(n_wr * args.batch, ITEM_DTYPE)
@@ -774,10 +847,13 @@ def main():
         progress("weak-scaling phase done")
     same_results = None
     if WL.kind not in ("mixed", "quota") and not args.partitioned:  # the first timed batch and its results
-        items = rot[args.warm]
+        items = rot[args.warm % n_rot]
         sl0 = slice(args.warm * n_slice, (args.warm + 1) * n_slice)
-        perm, err = torch.from_numpy(h_perm[sl0].copy()), torch.from_numpy(h_err[sl0].copy())
-        if device_resident is not None:  # every timed batch: host path == device-resident path
+        if lean_dev:
+            perm, err = outs[args.warm % n_rot]
+        else:
+            perm, err = torch.from_numpy(h_perm[sl0].copy()), torch.from_numpy(h_err[sl0].copy())
+        if device_resident is not None and not lean_dev:  # every timed batch: host path == device-resident path
             same_results = all(
                 (h_perm[k * n_slice:(k + 1) * n_slice] == outs[k][0].cpu().numpy()).all() and
                 (h_err[k * n_slice:(k + 1) * n_slice] == outs[k][1].cpu().numpy()).all()
@@ -794,7 +870,7 @@ def main():
     # also waits for the CUs the other batches hold, so the roofline uses these; `achieved_job` is
     # the whole device-resident phase.
     st_solo = None
-    if WL.kind not in ("mixed", "quota") and not args.partitioned and not args.no_profile:
+    if args.full and WL.kind not in ("mixed", "quota") and not args.partitioned and not args.no_profile:
         eng.set_profile(True)  # the timed region ran without events (a timed launch holds back the others)
         eng.reset_stats()
         for k in range(min(len(rot), 48)):
@@ -805,7 +881,7 @@ def main():
         eng.set_profile(False)
         progress(f"solo launches done: {int(st_solo['bundle_launches'])} timed, {st_solo['bundle_ms']:.3f} ms, "
                  f"{int(st_solo['aql_batches'])} dispatched into the engine's queues")
-    if args.partitioned and not args.no_profile:
+    if args.full and args.partitioned and not args.no_profile:
         # the partitioned join's own kernels timed by their events (k_label_join on one rank;
         # k_pj_pack + k_pj_decide on several, the exchange between them not included), the
         # global batch again a few times
@@ -817,7 +893,7 @@ def main():
         st_solo = eng.stats()
         eng.set_profile(False)
         progress("solo partitioned batches done")
-    if world > 1:
+    if world > 1 and elapsed is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt[0])
@@ -826,15 +902,16 @@ def main():
     # rank and step (weak)
     strong = WL.kind in ("nested", "gdocs", "github") and not args.partitioned
     total_checks = (args.batch if strong else world * args.batch) * args.steps
-    value = total_checks / elapsed
-    ms_per_step = elapsed / args.steps * 1e3
+    if elapsed is not None:
+        value = total_checks / elapsed
+        ms_per_step = elapsed / args.steps * 1e3
     # `value` (this task's bench contract): inputs already resident in HBM when the timed region
     # starts — the device-resident phase, timed as the host-buffer one (barrier + synchronize on both
     # sides, max over ranks). BASELINE.md:40-41's step with its PCIe transfers is the timed region
     # above, reported beside it as `baseline_pipelined` (and `baseline_step`, one batch at a time).
     baseline_pipelined = None
     if device_resident is not None:
-        baseline_pipelined = {
+        baseline_pipelined = None if elapsed is None else {
             "value": round(value, 1), "unit": "checks/s", "ms_per_step": round(ms_per_step, 4), "inflight": depth,
             "steps": args.steps,
             "definition": "BASELINE.md:40-41 / SURVEY §8(d) step: 65,536-check requests in pinned host memory "
@@ -1022,7 +1099,7 @@ def main():
 
     # `value`'s path is bound by the host link: 20 B of items in and 5 B of results out per check
     pcie = None
-    if WL.kind in ("nested", "gdocs", "github") and not args.partitioned:
+    if WL.kind in ("nested", "gdocs", "github") and not args.partitioned and elapsed is not None:
         per_rank = args.batch * args.steps / world  # checks over this rank's own link
         h2d, d2h = per_rank * 20 / elapsed / 1e9, per_rank * 5 / elapsed / 1e9
         pcie = {"bound": "pcie", "achieved": round(h2d, 2), "peak": 63.0, "unit": "GB/s", "frac": round(h2d / 63.0, 4),
@@ -1234,7 +1311,7 @@ def main():
                     "label_checks_per_batch": round(st_solo["label_checks"] / max(1, st_solo["batches"]), 1)}
 
     check_stage = None
-    if rank == 0 and WL.kind == "mixed":
+    if args.full and rank == 0 and WL.kind == "mixed":
         # the check stage alone, after the timed region (never `value`): the timed batch again on the
         # final snapshot, no Watch batch between, `depth` batches in flight on the engine's streams
         # with the same contexts — what the one-round join and its leftovers sustain

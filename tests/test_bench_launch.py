@@ -52,6 +52,40 @@ def test_launcher_refuses_missing_gpus():
     assert "refusing" in r.stderr
 
 
+def test_full_and_dump_outputs_options_parse():
+    # --full and --dump-outputs are options of every run (the selftest writes nothing)
+    r = _run(["--gpus", "1", "--selftest", "--batch", "1000", "--full", "--dump-outputs", "unused"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])["n_gpus"] == 1
+    assert not os.path.exists(os.path.join(ROOT, "unused"))
+    # the loop trace is of the host-buffer region, which only --full runs
+    r = _run(["--gpus", "1", "--selftest", "--trace-loop"])
+    assert r.returncode != 0 and "--full" in r.stderr
+
+
+def test_dump_outputs_writes_float32_and_samples_reproducibly(tmp_path, monkeypatch):
+    import numpy as np
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    perm = np.arange(1000, dtype=np.uint8) % 4
+    err = np.arange(1000, dtype=np.int32) - 500
+    bench.dump_outputs(str(tmp_path / "a"), {"perm": perm, "err": err})
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("perm", "err")}
+    assert got["perm"].dtype == np.float32 and got["err"].dtype == np.float32
+    assert (got["perm"] == perm).all() and (got["err"] == err).all()
+    # over the size limit: a fixed sample, the same elements every time, within the limit in all
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 100)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"perm": perm, "err": err})
+    b, c = (np.load(tmp_path / d / "err.npy") for d in ("b", "c"))
+    assert b.shape == (100,) and (b == c).all() and np.isin(b, err).all() and (np.diff(b) > 0).all()
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 8 * 100 + 2 * 128
+    # rank r > 0 of several writes beside rank 0
+    bench.dump_outputs(str(tmp_path / "a"), {"perm": perm}, rank=1, world=2)
+    assert (tmp_path / "a" / "perm.rank1.npy").exists()
+
+
 def test_world_size_mismatch_refused():
     r = _run(["--gpus", "2", "--steps", "1"], env={"WORLD_SIZE": "1", "RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr

@@ -235,7 +235,9 @@ F4_CASES = [
     ("duration(\"1h\") - duration(\"61m\") < duration(\"0\")", True),
     ("int(timestamp(\"1970-01-01T00:00:10Z\")) == 10 && int(timestamp(\"1969-12-31T23:59:59.5Z\")) == -1", True),
     ("ip.in_cidr(\"10.0.0.0/8\") && !ip.in_cidr(\"10.2.0.0/16\") && ip.in_cidr(\"10.1.2.3/32\")", True),
-    ("ipaddress(\"2001:db8::1\").in_cidr(\"2001:db8::/32\") && !ipaddress(\"2001:db8::1\").in_cidr(\"10.0.0.0/8\")", True),
+    # (an id of its own: the expression holds "::", the separator of pytest's node ids)
+    pytest.param("ipaddress(\"2001:db8::1\").in_cidr(\"2001:db8::/32\") && !ipaddress(\"2001:db8::1\").in_cidr(\"10.0.0.0/8\")", True,
+                 id="ipv6-in_cidr-True"),
     ("ip == ipaddress(\"10.1.2.3\") && ip != ipaddress(\"10.1.2.4\")", True),
     ("size(s) == 5 && s.size() == 5 && s.startsWith(\"hé\") && s.endsWith(\"llo\") && s.contains(\"él\")", True),
     ("size(l) == 3 && size(m) == 1 && has(m.k) && !has(m.z)", True),

@@ -36,11 +36,11 @@ case "$CMD" in
     tail -3 "$OUT/pytest.log"
     ;;
   bench)
-    timeout -k 10 600 python3 bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+    timeout -k 10 600 python3 bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
     tail -c 600 "$OUT/bench.json"
     ;;
   phases)
-    GCK_LIBRARY=$PWD/gochugaru_amd/libgck_debug.so GCK_DEBUG_PHASES=1 timeout -k 10 600 python3 bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" \
+    GCK_LIBRARY=$PWD/gochugaru_amd/libgck_debug.so GCK_DEBUG_PHASES=1 timeout -k 10 600 python3 bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" \
       || { tail -20 "$OUT/bench.err"; exit 1; }
     grep "\[gck" "$OUT/bench.err" | tail -20
     ;;
@@ -48,7 +48,7 @@ case "$CMD" in
     i=0
     for cfg in "$@"; do
       i=$((i+1))
-      timeout -k 10 300 python3 bench.py --no-oracle --no-cpu $cfg > "$OUT/s$i.json" 2> "$OUT/s$i.err"
+      timeout -k 10 300 python3 bench.py --full --no-oracle --no-cpu $cfg > "$OUT/s$i.json" 2> "$OUT/s$i.err"
       echo "$cfg :: $(python3 -c "import json; d=json.load(open('$OUT/s$i.json')); print(d['value'], d.get('host_buffers', {}).get('value'))")"
     done
     ;;
@@ -63,12 +63,12 @@ case "$CMD" in
     # (under the tracer the queues' dispatch timestamps are not the packets' own: the bench's solo
     # phase is launched through HIP and timed by its events, GCK_AQL_TIMED=0; the timed region and
     # the trace are the AQL-dispatched joins)
-    GCK_AQL_TIMED=0 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o kt --output-format csv -- python3 bench.py --no-cpu --host-steps 0 "$@" > "$OUT/kt.json" 2> "$OUT/kt.err"
-    GCK_AQL_TIMED=0 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/kt1" -o kt1 --output-format csv -- python3 bench.py --no-cpu --host-steps 0 --inflight 1 "$@" > "$OUT/kt1.json" 2> "$OUT/kt1.err"
+    GCK_AQL_TIMED=0 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o kt --output-format csv -- python3 bench.py --full --no-cpu --host-steps 0 "$@" > "$OUT/kt.json" 2> "$OUT/kt.err"
+    GCK_AQL_TIMED=0 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/kt1" -o kt1 --output-format csv -- python3 bench.py --full --no-cpu --host-steps 0 --inflight 1 "$@" > "$OUT/kt1.json" 2> "$OUT/kt1.err"
     echo "kernel trace done"
     # counter passes over the path the bench times: the joins dispatched into the engine's own HSA
     # queues (aql.inc), one batch at a time; GCK_DEBUG_AQL reports a dispatch that would stall
-    SHORT="python3 bench.py --steps 20 --warmup 3 --no-oracle --no-cpu --host-steps 0 --inflight 1 $*"
+    SHORT="python3 bench.py --full --steps 20 --warmup 3 --no-oracle --no-cpu --host-steps 0 --inflight 1 $*"
     GCK_DEBUG_AQL=1 timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o fetch --output-format csv -- $SHORT > "$OUT/fetch.json" 2> "$OUT/fetch.err"
     echo "fetch pass done"
     GCK_DEBUG_AQL=1 timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE -d "$OUT/write" -o write --output-format csv -- $SHORT > "$OUT/write.json" 2> "$OUT/write.err"
@@ -83,7 +83,7 @@ case "$CMD" in
   pmcprobe)
     # a counter pass over the AQL path itself (the engine's own HSA queues), with the dispatch / wait
     # diagnostics of GCK_DEBUG_AQL on stderr; killed after 120 s if it stalls (run it last)
-    SHORT="python3 bench.py --steps 20 --warmup 3 --no-oracle --no-cpu --host-steps 0 --inflight 1 $*"
+    SHORT="python3 bench.py --full --steps 20 --warmup 3 --no-oracle --no-cpu --host-steps 0 --inflight 1 $*"
     GCK_LIBRARY=$PWD/gochugaru_amd/libgck_debug.so GCK_DEBUG_AQL=1 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d "$OUT/aqlfetch" -o aqlfetch --output-format csv -- $SHORT > "$OUT/aqlfetch.json" 2> "$OUT/aqlfetch.err"
     rc=$?
     echo "pmc pass on the AQL path: status $rc"
@@ -102,21 +102,21 @@ case "$CMD" in
     set -e
     timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$OUT/smoke.log" 2>&1
     for r in 1 2; do
-      timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver$r.json" 2> "$OUT/bench_driver$r.err"
+      timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver$r.json" 2> "$OUT/bench_driver$r.err"
     done
-    timeout -k 10 300 python3 bench.py --no-cpu > "$OUT/bench_2000.json" 2> "$OUT/bench_2000.err"
-    timeout -k 10 300 python3 bench.py --config mixed --steps 20 --warmup 5 > "$OUT/mixed20.json" 2> "$OUT/mixed20.err"
-    timeout -k 10 400 python3 bench.py --config mixed --steps 500 --no-cpu > "$OUT/mixed500.json" 2> "$OUT/mixed500.err"
-    timeout -k 10 300 python3 bench.py --config gdocs --steps 20 --warmup 5 > "$OUT/gdocs20.json" 2> "$OUT/gdocs20.err"
-    timeout -k 10 400 python3 bench.py --config github --steps 20 --warmup 5 > "$OUT/github20.json" 2> "$OUT/github20.err"
+    timeout -k 10 300 python3 bench.py --full --no-cpu > "$OUT/bench_2000.json" 2> "$OUT/bench_2000.err"
+    timeout -k 10 300 python3 bench.py --full --config mixed --steps 20 --warmup 5 > "$OUT/mixed20.json" 2> "$OUT/mixed20.err"
+    timeout -k 10 400 python3 bench.py --full --config mixed --steps 500 --no-cpu > "$OUT/mixed500.json" 2> "$OUT/mixed500.err"
+    timeout -k 10 300 python3 bench.py --full --config gdocs --steps 20 --warmup 5 > "$OUT/gdocs20.json" 2> "$OUT/gdocs20.err"
+    timeout -k 10 400 python3 bench.py --full --config github --steps 20 --warmup 5 > "$OUT/github20.json" 2> "$OUT/github20.err"
     GCK_AQL_TIMED=0 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o kt --output-format csv -- \
-      python3 bench.py --steps 20 --warmup 5 --no-cpu > "$OUT/kt.json" 2> "$OUT/kt.err"
+      python3 bench.py --full --steps 20 --warmup 5 --no-cpu > "$OUT/kt.json" 2> "$OUT/kt.err"
     find "$OUT" -name "*kernel_trace.csv" -delete
     find "$OUT" -name "*agent_info.csv" -delete
     tail -2 "$OUT/pytest.log"
     ;;
   mixed)
-    GCK_LIBRARY=$PWD/gochugaru_amd/libgck_debug.so GCK_DEBUG_PHASES=1 timeout -k 10 400 python3 bench.py --config mixed "$@" > "$OUT/mixed.json" 2> "$OUT/mixed.err" \
+    GCK_LIBRARY=$PWD/gochugaru_amd/libgck_debug.so GCK_DEBUG_PHASES=1 timeout -k 10 400 python3 bench.py --full --config mixed "$@" > "$OUT/mixed.json" 2> "$OUT/mixed.err" \
       || { tail -20 "$OUT/mixed.err"; exit 1; }
     grep "gck watch\]\|gck apply\]\|gck relink\|gck group\|apply_publish" "$OUT/mixed.err" | tail -5
     ;;
