@@ -770,6 +770,7 @@ static void build_closure_join(Engine& e, DeviceSnapshot& ds, const std::vector<
   put(root.data(), root.size() * 2);
   const uint32_t o_meta = put(meta.data(), meta.size() * sizeof(CjMeta));
   const uint32_t o_ent = put(ents.data(), ents.size() * sizeof(CjEntry));
+  blob.resize(cj_table_bytes(blob.size()));  // (the join stages it in 16-B chunks)
   if (blob.size() > kCjLdsBytes) return;  // too large to stage in LDS: the bundles take everything
   ds.cj_host = std::move(blob);
   ds.cj_n_desc = (uint32_t)meta.size();

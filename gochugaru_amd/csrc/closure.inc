@@ -74,29 +74,41 @@ struct CjMeta {  // per eligible root
   uint32_t m_rows;        // objects of m's type the hierarchy's labels cover (bidir.inc)
 };
 
+// The join's arguments. The kernel's kernarg segment is (Ctx, CjArgs); every wave of every batch
+// reads its arguments through the scalar cache, which each dispatch's acquire has invalidated, so
+// each 64-B line of the segment a wave touches before its slot loads is a serial miss. Everything
+// the slot fast path reads therefore lies in ONE line — CjArgs bytes 40..103, kernarg 0x180..0x1bf
+// (CjHot below, read once at entry as one 16-dword scalar load) — and the fields around it are read
+// only inside the rare branches that use them (CjKernargs::cold). sizeof stays 184.
 struct CjArgs {
-  const gck_item* items;
-  uint32_t n;
-  uint8_t* out_perm;
-  int32_t* out_err;
+  // ---- cold, bytes 0..39 ----
   uint32_t* deferred;      // indices of the checks left to the bundle stages
   unsigned* n_deferred;
-  const unsigned char* table;  // root[n_fwd] u16 (0xFFFF: not eligible), meta[n_desc], entries[n_desc][n_types]
-  uint32_t n_fwd, n_desc, n_types, table_bytes;
-  uint32_t o_meta, o_entries;  // byte offsets in `table`
   unsigned long long* timing;  // GCK_DEBUG_TIMING (TIMING=1 builds): kCjTimingWords per wave
   // the publication of a device batch (k_publish's work, done by the last block to finish; null
   // h_out: k_publish follows): pub_words counter words, read and zeroed, to h_out, then seq to
   // h_out[pub_words]; `done` (zero between batches) counts the finished blocks
   unsigned* pub;
   unsigned* h_out;
+  // ---- the hot line, bytes 40..103 (CjHot has the same layout) ----
+  const gck_item* items;
+  uint8_t* out_perm;
+  int32_t* out_err;
+  const unsigned char* table;  // root[n_fwd] u16 (0xFFFF: not eligible), meta[n_desc], entries[n_desc][n_types]
+  uint32_t n;
+  uint32_t n_fwd, n_types;
+  uint32_t table_bytes;        // a multiple of 16 (the table is staged in 16-B chunks; cj_table_bytes)
+  uint32_t o_meta, o_entries;  // byte offsets in `table`
+  // kPubCoherent (results written through the L2: engine-stream batches published by the join),
+  // kPubBySignal, and what the kernel would otherwise learn from a cold pointer's null test
+  // (kCjUniform ...: set by cj_seal once the pointers are final)
+  uint32_t mode;
+  uint32_t hot_pad;
+  // ---- cold, bytes 104..183 ----
   unsigned* done;
-  uint32_t pub_words, seq;
-  uint32_t coherent;  // results written through the L2 (engine-stream batches published by the join)
   // host items read in place (a zero-copy batch): an item whose context_slot exceeds slot_limit
   // fails the request — the first such index lands in *bad_slot (DevCounters::bad_slot); null: no check
   unsigned* bad_slot;
-  uint32_t slot_limit;
   // a uniform batch (gck_check_bulk_uniform; null pairs: `items`): every check is the header words
   // u_rp (resource_type | permission << 16), u_ss (subject_type | subject_relation << 16), u_ctx
   // (context slot) and its (resource id, subject id) pair; its result is 2 bits of out_packed (32
@@ -105,8 +117,98 @@ struct CjArgs {
   const uint32_t* pairs;
   unsigned long long* out_packed;
   gck_item* items_out;
+  uint32_t pub_words, seq;
+  uint32_t slot_limit;
   uint32_t u_rp, u_ss, u_ctx;
+  uint32_t n_desc;
+  uint32_t cold_pad[3];
 };
+// CjArgs::mode beside kPubCoherent | kPubBySignal (engine.hip)
+constexpr uint32_t kCjUniform = 4u;   // pairs != null
+constexpr uint32_t kCjBadSlot = 8u;   // bad_slot != null
+constexpr uint32_t kCjSelfPub = 16u;  // h_out != null
+constexpr uint32_t kCjTimed = 32u;    // timing != null
+
+struct CjHot {  // the hot line as the kernel holds it (scalar registers)
+  const gck_item* items;
+  uint8_t* out_perm;
+  int32_t* out_err;
+  const unsigned char* table;
+  uint32_t n, n_fwd, n_types, table_bytes, o_meta, o_entries, mode, hot_pad;
+};
+constexpr size_t kCjHotOff = 40;
+static_assert(sizeof(CjArgs) == 184, "CjArgs size (tests/test_aql_codeobject.py, aql.inc kBuildId)");
+static_assert(sizeof(CjHot) == 64 && offsetof(CjArgs, items) == kCjHotOff && offsetof(CjArgs, done) == kCjHotOff + 64,
+              "CjArgs hot line");
+static_assert(offsetof(CjArgs, out_perm) - kCjHotOff == offsetof(CjHot, out_perm) &&
+                  offsetof(CjArgs, out_err) - kCjHotOff == offsetof(CjHot, out_err) &&
+                  offsetof(CjArgs, table) - kCjHotOff == offsetof(CjHot, table) &&
+                  offsetof(CjArgs, n) - kCjHotOff == offsetof(CjHot, n) &&
+                  offsetof(CjArgs, n_fwd) - kCjHotOff == offsetof(CjHot, n_fwd) &&
+                  offsetof(CjArgs, n_types) - kCjHotOff == offsetof(CjHot, n_types) &&
+                  offsetof(CjArgs, table_bytes) - kCjHotOff == offsetof(CjHot, table_bytes) &&
+                  offsetof(CjArgs, o_meta) - kCjHotOff == offsetof(CjHot, o_meta) &&
+                  offsetof(CjArgs, o_entries) - kCjHotOff == offsetof(CjHot, o_entries) &&
+                  offsetof(CjArgs, mode) - kCjHotOff == offsetof(CjHot, mode),
+              "CjHot mirrors CjArgs bytes 40..103");
+static_assert((sizeof(Ctx) + kCjHotOff) % 64 == 0, "the hot line is one 64-B line of the (Ctx, CjArgs) kernarg segment");
+
+// The mode bits that stand for a cold pointer's null test, once the pointers are final (before
+// the launch, the dispatch or the post).
+inline void cj_seal(CjArgs& j) {
+  j.mode = (j.mode & (kPubCoherent | kPubBySignal)) | (j.pairs ? kCjUniform : 0u) | (j.bad_slot ? kCjBadSlot : 0u) |
+           (j.h_out ? kCjSelfPub : 0u) | (j.timing ? kCjTimed : 0u);
+}
+// The staged bytes of a table of `bytes` bytes (its device buffer is allocated to this size).
+constexpr uint32_t cj_table_bytes(size_t bytes) { return (uint32_t)((bytes + 15) & ~(size_t)15); }
+
+// How cj_block reads a request's arguments: the hot line by value, the rest through cold() inside
+// the branches that need it.
+// k_closure_join: the kernarg segment itself. The segment pointer goes through an empty asm, so
+// that the compiler cannot prove the loads behind it safe to hoist: a cold field's scalar load
+// (and its wait) stays in its branch instead of joining the entry's.
+#define GCK_CONST __attribute__((address_space(4)))
+typedef uint32_t u32x16_a8 __attribute__((ext_vector_type(16), aligned(8)));
+struct CjKernargs {
+  CjHot h;
+  __device__ __forceinline__ static const GCK_CONST unsigned char* seg() {
+    const GCK_CONST unsigned char* p = (const GCK_CONST unsigned char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+  }
+  __device__ __forceinline__ void load_hot() {
+    const u32x16_a8 v = *(const GCK_CONST u32x16_a8*)((const GCK_CONST unsigned char*)__builtin_amdgcn_kernarg_segment_ptr() +
+                                                      sizeof(Ctx) + kCjHotOff);
+    __builtin_memcpy(&h, &v, sizeof(h));
+  }
+  __device__ __forceinline__ const GCK_CONST CjArgs* cold() const { return (const GCK_CONST CjArgs*)(seg() + sizeof(Ctx)); }
+  __device__ __forceinline__ DevCounters* ctr() const {
+    return *(DevCounters* const GCK_CONST*)(seg() + offsetof(Ctx, ctr));
+  }
+  // the batch's block count: gridDim.x, the first word of the code object's hidden arguments
+  // (hidden_block_count_x; tests/test_aql_codeobject.py) — read like a cold field, by the
+  // last-block publication only
+  __device__ __forceinline__ uint32_t nblk() const {
+    const GCK_CONST uint32_t* p = (const GCK_CONST uint32_t*)__builtin_amdgcn_implicitarg_ptr();
+    asm volatile("" : "+s"(p));
+    return p[0];
+  }
+};
+// A resident join's chunk (resident.inc): the request's arguments are in registers already.
+struct CjLocalArgs {
+  CjHot h;
+  const CjArgs* a;
+  DevCounters* c;
+  uint32_t n_chunks;
+  __device__ __forceinline__ uint32_t nblk() const { return n_chunks; }
+  __device__ __forceinline__ const CjArgs* cold() const { return a; }
+  __device__ __forceinline__ DevCounters* ctr() const { return c; }
+};
+__device__ __forceinline__ CjHot cj_hot(const CjArgs& a) {
+  CjHot h;
+  __builtin_memcpy(&h, reinterpret_cast<const unsigned char*>(&a) + kCjHotOff, sizeof(h));
+  return h;
+}
 
 // A uniform batch's check i (CjArgs::pairs): the header and its id pair.
 __device__ __forceinline__ gck_item uniform_item(uint32_t rp, uint32_t ss, uint32_t ctx, uint32_t res, uint32_t sub) {
@@ -168,6 +270,16 @@ __device__ __forceinline__ void block_summary(unsigned* slots, unsigned* clear, 
     slots[2 * blk + 1] = touched;
   }
   if (blk == 0) __hip_atomic_store(clear, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// ... with the two pointers read from the join's cold arguments only by the blocks that write
+template <class A>
+__device__ __forceinline__ void block_summary_cold(const A& a, uint32_t deferred, uint32_t touched, uint32_t blk) {
+  if (deferred | touched) {
+    unsigned* slots = a.cold()->h_out;
+    slots[2 * blk] = deferred;
+    slots[2 * blk + 1] = touched;
+  }
+  if (blk == 0) __hip_atomic_store(a.cold()->done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // per wave: {start, table staged, round 1 done, tasks done, end, tasks, probes, checks taken,
@@ -534,15 +646,18 @@ constexpr uint32_t kStageWords = kCheckWords / kStagePhases; // LDS stage words 
 // CPW: checks per wave (64, or 32: twice the waves, each waiting for the slowest of 64 lines
 // instead of 128).
 // The join of one block of checks: blk is the block's index in the batch (blockIdx.x, or a resident
-// join's chunk, resident.inc) and nblk the batch's block count; load_tab: stage the table in LDS (a
-// resident join stages it once per launch: the same static LDS every call). Counters: ctr.
+// join's chunk, resident.inc) and ax.nblk() the batch's block count; load_tab: stage the table in LDS (a
+// resident join stages it once per launch: the same static LDS every call). Counters: ax.ctr().
 // Returns (every thread) the checks the block left to the bundle stages.
-template <int BITS, uint32_t TAB, uint32_t CPW, bool HALF>
-__device__ __forceinline__ uint32_t cj_block(DevCounters* ctr, const CjArgs& a, const uint32_t blk, const uint32_t nblk,
-                                         const bool load_tab) {
+// Arguments: ax (CjKernargs or CjLocalArgs above) — `a` is its hot line, everything else is read
+// through ax.cold() / ax.ctr() where it is used; t_start: the wave's first timestamp (timing builds).
+template <int BITS, uint32_t TAB, uint32_t CPW, bool HALF, class A>
+__device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, const bool load_tab,
+                                         const unsigned long long t_start) {
   static_assert(CPW == 64 || CPW == 32, "checks per wave");
   static_assert(!HALF || CPW == 32, "half slots: 32 checks per wave");
-  const unsigned long long t_start = (GCK_BUNDLE_TIMING && a.timing) ? wall_clock64() : 0ull;
+  const CjHot& a = ax.h;
+  const bool timed = GCK_BUNDLE_TIMING && (a.mode & kCjTimed);
   __shared__ __attribute__((aligned(16))) unsigned char s_tab[TAB];
   __shared__ uint32_t s_nv[kWaves][64], s_excl[kWaves][65], s_hit[kWaves][64];
   __shared__ unsigned long long s_gp[kWaves][64];  // task base: &t_nbr[row start], or the group itself
@@ -567,7 +682,7 @@ __device__ __forceinline__ uint32_t cj_block(DevCounters* ctr, const CjArgs& a, 
   // the wave's items of a full 32-check wave are requested before the table: both loads in flight
   // together, one memory round instead of two before the slots can be addressed
   const uint32_t w0 = (blk * kWaves + wib) * CPW;
-  const bool uni = a.pairs != nullptr;  // (a kernel argument: a scalar branch)
+  const bool uni = (a.mode & kCjUniform) != 0u;  // (a kernel argument: a scalar branch)
   const uint32_t item_bytes = w0 < a.n ? min(CPW, a.n - w0) * 20u : 0u;
   const bool items_early = !uni && CPW == 32 && ((uintptr_t)a.items & 15u) == 0 && item_bytes == CPW * 20u;
   u32x4 item_chunk{0u, 0u, 0u, 0u};
@@ -575,21 +690,38 @@ __device__ __forceinline__ uint32_t cj_block(DevCounters* ctr, const CjArgs& a, 
     item_chunk = *(const GCK_GLOBAL u32x4*)(reinterpret_cast<const unsigned char*>(a.items) + (size_t)w0 * 20u + lane * 16u);
   // a uniform batch: each lane its own check's 8-B pair, requested before the table as the items
   // are (into the same registers)
-  if (uni && (uint32_t)lane < CPW && w0 + (uint32_t)lane < a.n) {
-    const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(a.pairs + 2ull * (w0 + (uint32_t)lane));
-    item_chunk.x = (uint32_t)pr;
-    item_chunk.y = (uint32_t)(pr >> 32);
+  if (uni) {
+    const uint32_t* pairs = ax.cold()->pairs;
+    if ((uint32_t)lane < CPW && w0 + (uint32_t)lane < a.n) {
+      const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(pairs + 2ull * (w0 + (uint32_t)lane));
+      item_chunk.x = (uint32_t)pr;
+      item_chunk.y = (uint32_t)(pr >> 32);
+    }
   }
-  if (load_tab)
-    for (uint32_t k = threadIdx.x; k < a.table_bytes / 4; k += kBlock)
-      reinterpret_cast<uint32_t*>(s_tab)[k] = gptr(reinterpret_cast<const uint32_t*>(a.table))[k];
+  // the table in 16-B chunks (table_bytes is a multiple of 16, and at most TAB: the launch picks
+  // the variant), every load issued before the first LDS write: one L2 round trip for the whole
+  // table instead of one per pass of a word-by-word loop
+  if (load_tab) {
+    constexpr uint32_t kChunks = (TAB / 16u + kBlock - 1u) / kBlock;
+    u32x4 tc[kChunks];
+#pragma unroll
+    for (uint32_t r = 0; r < kChunks; ++r) {
+      const uint32_t at = (r * kBlock + threadIdx.x) * 16u;
+      if (at < a.table_bytes && at < TAB) tc[r] = *(const GCK_GLOBAL u32x4*)(a.table + at);
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < kChunks; ++r) {
+      const uint32_t at = (r * kBlock + threadIdx.x) * 16u;
+      if (at < a.table_bytes && at < TAB) *reinterpret_cast<u32x4*>(&s_tab[at]) = tc[r];
+    }
+  }
   __syncthreads();
   const uint16_t* root = reinterpret_cast<const uint16_t*>(s_tab);
   const CjMeta* meta = reinterpret_cast<const CjMeta*>(s_tab + a.o_meta);
   const CjEntry* ent = reinterpret_cast<const CjEntry*>(s_tab + a.o_entries);
   const uint32_t i = (blk * kWaves + wib) * CPW + lane;
   const bool active = (uint32_t)lane < CPW && i < a.n;
-  const unsigned long long t_tab = (GCK_BUNDLE_TIMING && a.timing) ? wall_clock64() : 0ull;
+  const unsigned long long t_tab = timed ? wall_clock64() : 0ull;
   // (the task rounds below: row extents of what the slots left, then V(R), G(u), signatures, probes)
   bool take = false, self = false;
   uint32_t fast = 0;  // slot_decide: 2 HAS, 1 NO, 3 the list round, 0 the task rounds
@@ -628,16 +760,22 @@ __device__ __forceinline__ uint32_t cj_block(DevCounters* ctr, const CjArgs& a, 
     for (uint32_t q = 0; q < 5u; ++q) s_item_w[lane * 5u + q] = gptr(src)[q];
   }
   lds_wave_fence();
-  const unsigned long long t_items = (GCK_BUNDLE_TIMING && a.timing) ? wall_clock64() : 0ull;
+  const unsigned long long t_items = timed ? wall_clock64() : 0ull;
   gck_item it{};
-  if (active && uni) {
-    it = uniform_item(a.u_rp, a.u_ss, a.u_ctx, item_chunk.x, item_chunk.y);
+  if (uni) {
+    const auto cold = ax.cold();
+    const uint32_t u_rp = cold->u_rp, u_ss = cold->u_ss, u_ctx = cold->u_ctx;
+    if (active) it = uniform_item(u_rp, u_ss, u_ctx, item_chunk.x, item_chunk.y);
   } else if (active) {
     uint32_t iw[5];
     for (uint32_t q = 0; q < 5u; ++q) iw[q] = s_item_w[lane * 5u + q];
     __builtin_memcpy(&it, iw, sizeof(it));
   }
-  const bool bad_w = a.bad_slot && check_slots(a.bad_slot, a.slot_limit, active, it, w0, lane);
+  bool bad_w = false;
+  if (a.mode & kCjBadSlot) {
+    const auto cold = ax.cold();
+    bad_w = check_slots(cold->bad_slot, cold->slot_limit, active, it, w0, lane);
+  }
   // ---- round 1: both slots of every check the slots can take, line by line ---------------------
   unsigned long long ua = 0, da = 0, lbase = 0;
   if (active && it.permission < a.n_fwd && it.subject_id != kWildcard && it.subject_relation == kEllipsis) {
@@ -701,7 +839,7 @@ __device__ __forceinline__ uint32_t cj_block(DevCounters* ctr, const CjArgs& a, 
     for (uint32_t q = 8; q < kDSlotWords; ++q) dd[q] = 0u;  // (empty intervals, as a fitting slot has them)
     // second halves of the resource slots with more intervals (each lane its own check's)
     const bool more_d = ua && !(dd[0] & kSlotOverflow) && dd[0] > kSlotHalfV;
-    if (__ballot(more_d) != 0 && more_d) {
+    if (__builtin_expect(__ballot(more_d) != 0, 0) && more_d) {
       const u32x4 h0 = slot_load((const GCK_GLOBAL u32x4*)(da + 32u));
       const u32x4 h1 = slot_load((const GCK_GLOBAL u32x4*)(da + 48u));
       dd[8] = h0.x, dd[9] = h0.y, dd[10] = h0.z, dd[11] = h0.w;
@@ -779,10 +917,10 @@ __device__ __forceinline__ uint32_t cj_block(DevCounters* ctr, const CjArgs& a, 
       }
     }
   }
-  const unsigned long long t_slot1 = (GCK_BUNDLE_TIMING && a.timing) ? wall_clock64() : 0ull;
+  const unsigned long long t_slot1 = timed ? wall_clock64() : 0ull;
   // ---- round 1b: the cover lists of users whose covers exceed a slot, one (check, entry) task
   // per lane slot, against the check's intervals staged in LDS ------------------------------------
-  if (__ballot(fast == 3u) != 0) {
+  if (__builtin_expect(__ballot(fast == 3u) != 0, 0)) {
     // the resource slots of the list checks, one per lane, for the (check, entry) tasks below
     lds_wave_fence();
     if (fast == 3u) {
@@ -825,7 +963,17 @@ __device__ __forceinline__ uint32_t cj_block(DevCounters* ctr, const CjArgs& a, 
     lds_wave_fence();
     if (fast == 3u) fast = lds_ld(&s_hit[wib][lane]) ? 2u : 1u;
   }
-  const unsigned long long t_slots = (GCK_BUNDLE_TIMING && a.timing) ? wall_clock64() : 0ull;
+  const unsigned long long t_slots = timed ? wall_clock64() : 0ull;
+  // Everything from here to the results is for checks the slots did not decide. A wave without
+  // one (every wave of config 4) skips it whole — the set-up stores, the scan and the fences as
+  // well as the loops — and the branch is marked unlikely, as the other rare ones are, so that the
+  // compiler lays the slot path out as straight-line code with the rare rounds behind it: a
+  // skipped round in the middle of the path cost the waves of a batch, which start together after
+  // the dispatch has invalidated the instruction cache, a miss each (the timing build showed
+  // 1.2 us between the slot decisions and the extents in waves with no list at all).
+  uint32_t total = 0, probes = 0;
+  unsigned long long t_r1 = t_slots;
+  if (__builtin_expect(__ballot(active && !fast) != 0, 0)) {
   // ---- the task rounds' inputs for the rest: row extents ----------------------------------------
   if (active && !fast) {
     if (it.permission < a.n_fwd && it.subject_id != kWildcard) {
@@ -871,8 +1019,8 @@ __device__ __forceinline__ uint32_t cj_block(DevCounters* ctr, const CjArgs& a, 
   s_gp[wib][lane] = gp;
   s_hit[wib][lane] = 0u;
   const uint32_t incl = wave_incl_scan(nt);
-  const uint32_t total = wave_last(incl);
-  const unsigned long long t_r1 = (GCK_BUNDLE_TIMING && a.timing) ? wall_clock64() : 0ull;
+  total = wave_last(incl);
+  t_r1 = timed ? wall_clock64() : 0ull;
   uint32_t* excl = s_excl[wib];
   excl[lane] = incl - nt;
   if (lane == 63) excl[64] = total;
@@ -882,7 +1030,6 @@ __device__ __forceinline__ uint32_t cj_block(DevCounters* ctr, const CjArgs& a, 
 #pragma unroll
   for (int k = 0; k < kCjV; ++k) vv[k] = (vsrc && (uint32_t)k < nv) ? gptr(vsrc)[k] : 0u;
   bool v_stored = false;
-  uint32_t probes = 0;
   for (uint32_t t0 = 0; t0 < total; t0 += 64u * kCjK) {
     uint32_t g[kCjK], own[kCjK];
 #pragma unroll
@@ -953,7 +1100,8 @@ __device__ __forceinline__ uint32_t cj_block(DevCounters* ctr, const CjArgs& a, 
     }
   }
   lds_wave_fence();
-  const unsigned long long t_tasks = (GCK_BUNDLE_TIMING && a.timing) ? wall_clock64() : 0ull;
+  }
+  const unsigned long long t_tasks = timed ? wall_clock64() : 0ull;
   // the batch counters: summed per block in LDS, one atomic per block and counter (an atomic per
   // wave on the same line serialises at the L2 behind every other wave's). Only probes and the
   // task-round checks are counted here — both zero on the slot path, so a block of slot checks
@@ -969,46 +1117,49 @@ __device__ __forceinline__ uint32_t cj_block(DevCounters* ctr, const CjArgs& a, 
     const uint32_t v = (active && fast) ? (fast == 2u ? (uint32_t)GCK_PERM_HAS : (uint32_t)GCK_PERM_NO)
                        : (active && take) ? (lds_ld(&s_hit[wib][lane]) ? (uint32_t)GCK_PERM_HAS : (uint32_t)GCK_PERM_NO)
                                           : 0u;
-    packed_store(a.out_packed, w0, v, lane, CPW, a.n);
+    packed_store(ax.cold()->out_packed, w0, v, lane, CPW, a.n);
   } else if (active && fast) {
-    store_result(a.out_perm + i, fast == 2u ? (uint8_t)GCK_PERM_HAS : (uint8_t)GCK_PERM_NO, (a.coherent & kPubCoherent) != 0u);
-    store_result(a.out_err + i, (int32_t)GCK_ITEM_OK, (a.coherent & kPubCoherent) != 0u);
+    store_result(a.out_perm + i, fast == 2u ? (uint8_t)GCK_PERM_HAS : (uint8_t)GCK_PERM_NO, (a.mode & kPubCoherent) != 0u);
+    store_result(a.out_err + i, (int32_t)GCK_ITEM_OK, (a.mode & kPubCoherent) != 0u);
   } else if (active && take) {
     store_result(a.out_perm + i, lds_ld(&s_hit[wib][lane]) ? (uint8_t)GCK_PERM_HAS : (uint8_t)GCK_PERM_NO,
-                 (a.coherent & kPubCoherent) != 0u);
-    store_result(a.out_err + i, (int32_t)GCK_ITEM_OK, (a.coherent & kPubCoherent) != 0u);
+                 (a.mode & kPubCoherent) != 0u);
+    store_result(a.out_err + i, (int32_t)GCK_ITEM_OK, (a.mode & kPubCoherent) != 0u);
   }
   {  // checks left to the bundles: one counter add per wave (labels.inc wave_append)
     const bool left = active && !fast && !take;
     const unsigned long long m = __ballot(left);
-    if (m) {
+    if (__builtin_expect(m != 0, 0)) {
       const int leader = __ffsll((long long)m) - 1;
+      const auto cold = ax.cold();
       uint32_t base = 0;
       if (lane == leader) {
-        base = atomicAdd(a.n_deferred, (unsigned)__popcll(m));
+        base = atomicAdd(cold->n_deferred, (unsigned)__popcll(m));
         atomicAdd(&s_cnt[2], (unsigned)__popcll(m));
       }
       base = (uint32_t)__shfl((int)base, leader, 64);
-      if (left) a.deferred[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
+      if (left) cold->deferred[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
       if (left && uni) {  // the check's item where the bundle stages read it (its pair read again: rare)
-        const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(a.pairs + 2ull * i);
-        a.items_out[i] = uniform_item(a.u_rp, a.u_ss, a.u_ctx, (uint32_t)pr, (uint32_t)(pr >> 32));
+        const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(cold->pairs + 2ull * i);
+        cold->items_out[i] = uniform_item(cold->u_rp, cold->u_ss, cold->u_ctx, (uint32_t)pr, (uint32_t)(pr >> 32));
       }
     }
   }
   const uint32_t n_take = (uint32_t)__popcll(__ballot(active && (take || fast)));
   const uint32_t n_task = (uint32_t)__popcll(__ballot(active && take && !fast));
   if (lane == 0 && n_task) atomicAdd(&s_cnt[1], n_task);
-  if (a.h_out && (a.coherent & kPubCoherent)) __builtin_amdgcn_s_waitcnt(0);  // (coherent results: completed before the block arrives)
+  if ((a.mode & kCjSelfPub) && (a.mode & kPubCoherent)) __builtin_amdgcn_s_waitcnt(0);  // (coherent results: completed before the block arrives)
   __syncthreads();
   const uint32_t blk_deferred = s_cnt[2];
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0 && (s_cnt[0] | s_cnt[1])) {
+    DevCounters* ctr = ax.ctr();
     if (s_cnt[0]) atomicAdd(&ctr->probes, (unsigned long long)s_cnt[0]);
     if (s_cnt[1]) atomicAdd(&ctr->closure, (unsigned long long)s_cnt[1]);
   }
-  if (a.coherent & kPubBySignal) {
-    if (threadIdx.x == 0) block_summary(a.h_out, a.done, s_cnt[2], s_cnt[0] | s_cnt[1] | s_cnt[3], blk);
-  } else if (a.h_out && wib == 0) {
+  if (a.mode & kPubBySignal) {
+    if (threadIdx.x == 0) block_summary_cold(ax, s_cnt[2], s_cnt[0] | s_cnt[1] | s_cnt[3], blk);
+  } else if ((a.mode & kCjSelfPub) && wib == 0) {
+    const auto cold = ax.cold();
     // the batch's publication without a k_publish launch (one host launch per batch instead of
     // two: the host submit cost bounds the batches in flight), by wave 0 of each block after the
     // block's barrier (the other waves are done). The counters are device-scope atomics,
@@ -1022,17 +1173,20 @@ __device__ __forceinline__ uint32_t cj_block(DevCounters* ctr, const CjArgs& a, 
     uint32_t last = 0;
     if (lane == 0) {
       __builtin_amdgcn_s_waitcnt(0);  // this thread's counter atomics have completed
-      last = atomicAdd(a.done, 1u) == nblk - 1u;
+      last = atomicAdd(cold->done, 1u) == ax.nblk() - 1u;
     }
     if (__shfl(last, 0, 64)) {
-      for (uint32_t k = lane; k < a.pub_words; k += 64u) a.h_out[k] = atomicExch(&a.pub[k], 0u);
-      if (lane == 0) pub_seq_store(a.h_out + a.pub_words, a.seq, a.coherent);
+      unsigned* h_out = cold->h_out;
+      unsigned* pub = cold->pub;
+      const uint32_t pub_words = cold->pub_words;
+      for (uint32_t k = lane; k < pub_words; k += 64u) h_out[k] = atomicExch(&pub[k], 0u);
+      if (lane == 0) pub_seq_store(h_out + pub_words, cold->seq, a.mode);
     }
   }
-  if (GCK_BUNDLE_TIMING && a.timing) {
+  if (timed) {
     const uint32_t wave_probes = wave_last(wave_incl_scan(probes));
     if (lane == 0) {
-      unsigned long long* t = a.timing + (unsigned long long)kCjTimingWords * (blk * kWaves + wib);
+      unsigned long long* t = ax.cold()->timing + (unsigned long long)kCjTimingWords * (blk * kWaves + wib);
       t[0] = t_start;
       t[1] = t_tab;
       t[2] = t_r1;
@@ -1051,5 +1205,9 @@ __device__ __forceinline__ uint32_t cj_block(DevCounters* ctr, const CjArgs& a, 
 
 template <int BITS, uint32_t TAB, uint32_t CPW = 64, bool HALF = false>
 __global__ void __launch_bounds__(kBlock) k_closure_join(Ctx c, CjArgs a) {
-  cj_block<BITS, TAB, CPW, HALF>(c.ctr, a, blockIdx.x, gridDim.x, true);
+  // (c and a are read through the kernarg segment: CjKernargs)
+  const unsigned long long t_start = GCK_BUNDLE_TIMING ? wall_clock64() : 0ull;
+  CjKernargs ax;
+  ax.load_hot();
+  cj_block<BITS, TAB, CPW, HALF>(ax, blockIdx.x, true, t_start);
 }

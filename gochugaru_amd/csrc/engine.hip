@@ -2739,7 +2739,7 @@ static void bundles_launch(Engine& e, Workspace& w, const gck_item* d_items, uin
     j.n_fwd = ds.n_fwd;
     j.n_desc = ds.cj_n_desc;
     j.n_types = ds.n_types;
-    j.table_bytes = (uint32_t)((ds.cj_host.size() + 3) & ~(size_t)3);
+    j.table_bytes = cj_table_bytes(ds.cj_host.size());  // (build_closure_join pads the table to it)
     j.o_meta = ds.cj_o_meta;
     j.o_entries = ds.cj_o_entries;
     j.timing = a.timing ? a.timing + (size_t)kTimingWords * (n + 1) * 2 : nullptr;
@@ -2756,9 +2756,10 @@ static void bundles_launch(Engine& e, Workspace& w, const gck_item* d_items, uin
       j.h_out = w.d_hpub;
       j.done = w.b_ctrs + kBDone;
       j.seq = ++w.pub_seq;
-      j.coherent = coherent;
+      j.mode = coherent;
       w.b_seq = j.seq;
     }
+    cj_seal(j);  // (the pointers above are final: their null tests as mode bits)
     // a timed batch's events are the kernel's own start and stop (hipExtLaunchKernel), not markers
     // around its dispatch, so they agree with a profiler's kernel duration
     // 32 checks per wave where the slot entries are 24-bit and the table is small: each wave waits
@@ -2775,17 +2776,20 @@ static void bundles_launch(Engine& e, Workspace& w, const gck_item* d_items, uin
       CjArgs j;
     } cj_args{c, j};  // (the kernarg segment: the two by-value parameters in order)
     static_assert(offsetof(decltype(cj_args), j) == 344, "k_closure_join kernarg layout (Ctx, CjArgs)");
+    // (the join's hot arguments are one 64-B line of the segment only in a 64-B aligned block)
+    if (aql_ok && ((uintptr_t)w.aql_kernarg & 63u))
+      throw Error(GCK_E_DEVICE, "engine invariant violated: kernarg block alignment");
     // (half slots: the first 32 B of each resource slot, closure.inc HALF)
     if (fast && aql_ok && j.h_out && aql_kernel(e.aql, "void gck::k_closure_join<24, 2048u, 32u, true>(gck::Ctx, gck::CjArgs)"))
-      aql_summaries(w, cj_args.j.coherent, cj_args.j.h_out, cj_args.j.done, cj_args.j.n_deferred, grid.x);
+      aql_summaries(w, cj_args.j.mode, cj_args.j.h_out, cj_args.j.done, cj_args.j.n_deferred, grid.x);
     // the resident join (resident.inc) takes the request without a dispatch of its own
     const bool res_ok = fast && aql_ok && e.res && !w.b_timed && w.b_sum_blocks == grid.x &&
-                        (cj_args.j.coherent & kPubBySignal);
+                        (cj_args.j.mode & kPubBySignal);
     static const bool dbg_res = debug_env("GCK_DEBUG_RES") != nullptr;  // (why a batch did not go resident)
     if (dbg_res && e.res && !res_ok)
       std::fprintf(stderr, "[gck res] not resident: fast=%d aql_ok=%d own=%d host_out=%d chained=%d clean=%d cav=%d timed=%d sum=%u/%u pub=%u\n",
                    (int)fast, (int)aql_ok, (int)w.b_own_stream, (int)host_out, (int)w.b_chained, (int)ctr_was_clean,
-                   (int)w.cav_on, (int)w.b_timed, w.b_sum_blocks, grid.x, cj_args.j.coherent);
+                   (int)w.cav_on, (int)w.b_timed, w.b_sum_blocks, grid.x, cj_args.j.mode);
     if (res_ok) {
       aql_after_build(e);
       res_post(e, w, cj_args.j, grid.x);

@@ -257,8 +257,10 @@ __global__ void __launch_bounds__(kBlock) k_cj_resident(ResDev* d, ResHost* h, c
     CjArgs a = ra.a;
     a.table = table;
     a.table_bytes = table_bytes;
-    a.coherent |= kPubCoherent;
-    const uint32_t deferred = cj_block<BITS, TAB, CPW, HALF>(ra.ctr, a, chunk, n_chunks, first);
+    a.mode |= kPubCoherent;
+    const CjLocalArgs ax{cj_hot(a), &a, ra.ctr, n_chunks};
+    const uint32_t deferred = cj_block<BITS, TAB, CPW, HALF>(
+        ax, chunk, first, (GCK_BUNDLE_TIMING && (a.mode & kCjTimed)) ? wall_clock64() : 0ull);
     first = false;
     // every wave's stores have completed, then the chunk counts towards its request
     __builtin_amdgcn_s_waitcnt(0);

@@ -34,12 +34,13 @@ def main(path):
                                      (r[:, 9] - r[:, 10]) * TICK_US,
                                      (r[:, 2] - r[:, 9]) * TICK_US, (r[:, 3] - r[:, 2]) * TICK_US,
                                      (r[:, 4] - r[:, 3]) * TICK_US, (r[:, 4] - t0) * TICK_US,
-                                     r[:, 5], r[:, 6], r[:, 7]]))
+                                     r[:, 5], r[:, 6], r[:, 7], (r[:, 4] - r[:, 0]) * TICK_US]))
     a = np.concatenate(recs)
     print(f"launches {len(spans)}  span us (first wave start -> last wave end): {pct(np.array(spans))}")
     names = ["start offset", "table copy", "items", "slots", "lists", "extents", "tasks", "end", "wave end offset"]
     for k, nm in enumerate(names):
         print(f"{nm:>16} us  {pct(a[:, k])}")
+    print(f"{'wave lifetime':>16} us  {pct(a[:, 12])}")
     print(f"{'tasks/wave':>16}     {pct(a[:, 9])}")
     print(f"{'probes/wave':>16}     {pct(a[:, 10])}")
 
