@@ -253,7 +253,7 @@ static AqlState* aql_init(Engine& e) {
     stamps &= hsa_amd_profiling_set_profiler_enabled(st->qs[k], 1) == HSA_STATUS_SUCCESS;
   if (debug_env("GCK_DEBUG_AQL")) {  // where the loader put the kernels' code (device or host memory)
     for (auto& [name, k] : st->kernels) {
-      if (name.find("k_closure_join<24, 2048u") == std::string::npos) continue;
+      if (name != cj_variant(24, true).aql_name) continue;  // (the dispatched closure join)
       hsa_amd_pointer_info_t pi{};
       pi.size = sizeof(pi);
       hsa_agent_t owner{};

@@ -506,6 +506,62 @@ struct SlotSet {
   const uint32_t* list = nullptr;  // user slots: the cover lists (null: none)
 };
 
+// closure.inc k_user_slots_1p / k_user_slots_ids at the snapshot's entry width, on the null stream.
+static void launch_user_slots_ids(uint32_t bits, const uint32_t* off, const uint32_t* nbr, const uint32_t* ids, uint32_t n,
+                                  const uint32_t* lab, const uint32_t* cov_off, const uint32_t* cov_pre, uint32_t n_groups,
+                                  const uint32_t* list_off, uint32_t* list, uint32_t* staged) {
+  hipLaunchKernelGGL(bits == 24 ? k_user_slots_ids<24> : k_user_slots_ids<32>, dim3(grid_for(n)), dim3(kBlock), 0, 0, off,
+                     nbr, ids, n, lab, cov_off, cov_pre, n_groups, list_off, list, staged);
+  HIP_OK(hipGetLastError());
+}
+
+static void launch_user_slots_1p(uint32_t bits, const uint32_t* off, const uint32_t* nbr, uint32_t n, const uint32_t* lab,
+                                 const uint32_t* cov_off, const uint32_t* cov_pre, uint32_t n_groups, uint32_t* slots,
+                                 uint32_t* len) {
+  hipLaunchKernelGGL(bits == 24 ? k_user_slots_1p<24> : k_user_slots_1p<32>, dim3(grid_for(n)), dim3(kBlock), 0, 0, off, nbr,
+                     n, lab, cov_off, cov_pre, n_groups, slots, len);
+  HIP_OK(hipGetLastError());
+}
+
+// The full build of the slots of users [0, n) into `slots`: one pass of the random reads (labels,
+// covers) for every user writes the inline slots and the lengths of the lists of the users whose
+// covers exceed a slot; those lists follow at the scanned offsets. alloc_list(bytes) gives the list
+// array, or declines with null: the listed users then overflow. Returns the list array, and the
+// lists' total length whether or not they were written.
+struct UserLists {
+  uint32_t* list;
+  uint32_t total;
+};
+
+template <class AllocList>
+static UserLists build_user_slots(uint32_t bits, const uint32_t* off, const uint32_t* nbr, uint32_t n, const uint32_t* lab,
+                                  const uint32_t* cov_off, const uint32_t* cov_pre, uint32_t n_groups, uint32_t* slots,
+                                  AllocList alloc_list) {
+  UserLists out{nullptr, 0u};
+  std::vector<void*> tmp;
+  try {
+    uint32_t* len = dalloc<uint32_t>(tmp, (size_t)n + 1);
+    uint32_t* loff = dalloc<uint32_t>(tmp, (size_t)n + 1);
+    HIP_OK(hipStreamSynchronize(nullptr));
+    launch_user_slots_1p(bits, off, nbr, n, lab, cov_off, cov_pre, n_groups, slots, len);
+    device_excl_scan(len, n, loff);
+    HIP_OK(hipMemcpy(&out.total, loff + n, 4, hipMemcpyDeviceToHost));
+    // (u32 offsets; a total that wrapped cannot be told apart, so stay well below 2^31)
+    if (out.total > 0 && out.total < (1u << 31)) out.list = alloc_list((size_t)out.total * 4);
+    if (out.total) {
+      hipLaunchKernelGGL(k_user_lists, dim3(grid_for(n)), dim3(kBlock), 0, 0, off, nbr, n, cov_off, cov_pre, len, loff,
+                         out.list, slots);
+      HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipDeviceSynchronize());
+  } catch (...) {
+    free_list(tmp);
+    throw;
+  }
+  free_list(tmp);
+  return out;
+}
+
 // A Watch batch whose hierarchy labels are unchanged recomputes the user slots of the users it
 // touched only (DeltaHint::Users): their slots are staged, the rest of the current snapshot's slot
 // array is taken over and the staged ones are written into it at publish (SlotPatch); their cover
@@ -555,15 +611,9 @@ static const SlotSet* slots_delta(Engine& e, DeviceSnapshot& ds, std::map<const 
       list = slot_alloc(ds, (size_t)(total + add) * 4);
       if (total) HIP_OK(hipMemcpy(list, old->list, total * 4, hipMemcpyDeviceToDevice));
     }
-    if (n) {
-      if (ds.slot_bits == 24)
-        hipLaunchKernelGGL(k_user_slots_ids<24>, dim3(grid_for(n)), dim3(kBlock), 0, 0, off, nbr, hu->ids, n, closure->lab,
-                           closure->cov_off, closure->cov_pre, n_groups, list ? loff : nullptr, list, staged);
-      else
-        hipLaunchKernelGGL(k_user_slots_ids<32>, dim3(grid_for(n)), dim3(kBlock), 0, 0, off, nbr, hu->ids, n, closure->lab,
-                           closure->cov_off, closure->cov_pre, n_groups, list ? loff : nullptr, list, staged);
-      HIP_OK(hipGetLastError());
-    }
+    if (n)
+      launch_user_slots_ids(ds.slot_bits, off, nbr, hu->ids, n, closure->lab, closure->cov_off, closure->cov_pre, n_groups,
+                            list ? loff : nullptr, list, staged);
     HIP_OK(hipDeviceSynchronize());
   } catch (...) {
     free_list(tmp);
@@ -611,41 +661,16 @@ static SlotSet slots_for(Engine& e, DeviceSnapshot& ds, std::map<const uint32_t*
   if (bytes <= free_b / 2) {
     uint32_t* s = slot_alloc(ds, bytes);
     if (n_rows && kind == SlotKind::kUser) {
-      // the cover lists of the users whose covers exceed a slot: lengths, offsets, then the slots
-      std::vector<void*> tmp;
-      uint32_t* len = dalloc<uint32_t>(tmp, (size_t)n_rows + 1);
-      uint32_t* loff = dalloc<uint32_t>(tmp, (size_t)n_rows + 1);
-      uint32_t* list = nullptr;
-      try {
-        HIP_OK(hipStreamSynchronize(nullptr));
-        // one pass of the random reads (labels, covers) for every user; the listed users' lists after
-        if (ds.slot_bits == 24)
-          hipLaunchKernelGGL(k_user_slots_1p<24>, dim3(grid_for(n_rows)), dim3(kBlock), 0, 0, off, nbr, n_rows, closure->lab,
-                             closure->cov_off, closure->cov_pre, n_groups, s, len);
-        else
-          hipLaunchKernelGGL(k_user_slots_1p<32>, dim3(grid_for(n_rows)), dim3(kBlock), 0, 0, off, nbr, n_rows, closure->lab,
-                             closure->cov_off, closure->cov_pre, n_groups, s, len);
-        HIP_OK(hipGetLastError());
-        device_excl_scan(len, n_rows, loff);
-        uint32_t total = 0;
-        HIP_OK(hipMemcpy(&total, loff + n_rows, 4, hipMemcpyDeviceToHost));
-        size_t free2 = 0;
-        HIP_OK(hipMemGetInfo(&free2, &total_b));
-        // (u32 offsets; a total that wrapped cannot be told apart, so stay well below 2^31)
-        if (total > 0 && total < (1u << 31) && (size_t)total * 4 <= free2 / 2) list = slot_alloc(ds, (size_t)total * 4);
-        ds.slot_recs.push_back({off, closure->lab, closure->cov_pre, s, list, list ? (uint64_t)total : 0ull, n_rows,
-                                (uint8_t)SlotKind::kUser});
-        if (total)
-          hipLaunchKernelGGL(k_user_lists, dim3(grid_for(n_rows)), dim3(kBlock), 0, 0, off, nbr, n_rows, closure->cov_off,
-                             closure->cov_pre, len, loff, list, s);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipDeviceSynchronize());
-      } catch (...) {
-        free_list(tmp);
-        throw;
-      }
-      free_list(tmp);
-      out.list = list;
+      // (the cover lists take at most half of the HBM that is free once the slots are allocated)
+      const UserLists ul = build_user_slots(ds.slot_bits, off, nbr, n_rows, closure->lab, closure->cov_off, closure->cov_pre,
+                                            n_groups, s, [&](size_t list_bytes) -> uint32_t* {
+                                              size_t free2 = 0;
+                                              HIP_OK(hipMemGetInfo(&free2, &total_b));
+                                              return list_bytes <= free2 / 2 ? slot_alloc(ds, list_bytes) : nullptr;
+                                            });
+      ds.slot_recs.push_back({off, closure->lab, closure->cov_pre, s, ul.list, ul.list ? (uint64_t)ul.total : 0ull, n_rows,
+                              (uint8_t)SlotKind::kUser});
+      out.list = ul.list;
     } else if (n_rows) {
       hipLaunchKernelGGL(k_res_slots, dim3(grid_for(n_rows)), dim3(kBlock), 0, 0, off, nbr, n_rows, closure->lab,
                          n_groups, s);

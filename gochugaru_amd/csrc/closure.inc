@@ -369,17 +369,6 @@ __device__ __forceinline__ uint32_t user_cover_count(const uint32_t* t_off, cons
   return m;
 }
 
-// Per user the length of its cover list: 0 when the covers fit the slot (or cannot be used).
-__global__ void __launch_bounds__(kBlock) k_user_list_len(const uint32_t* __restrict__ t_off, const uint32_t* __restrict__ t_nbr,
-                                                          uint32_t n_users, const uint32_t* __restrict__ lab,
-                                                          const uint32_t* __restrict__ cov_off, uint32_t n_groups,
-                                                          uint32_t cap, uint32_t* __restrict__ len) {
-  const uint32_t u = blockIdx.x * kBlock + threadIdx.x;
-  if (u >= n_users) return;
-  const uint32_t m = user_cover_count(t_off, t_nbr, u, lab, cov_off, n_groups);
-  len[u] = (m & kSlotOverflow) || m <= cap ? 0u : m;
-}
-
 // Entry k of a user slot (word 0 is the count): BITS-wide fields packed from bit 32.
 template <int BITS, int K>
 __device__ __forceinline__ uint32_t slot_entry(const uint32_t (&w)[kUSlotWords]) {
@@ -452,20 +441,6 @@ __device__ __forceinline__ void user_slot(const uint32_t* __restrict__ t_off, co
   uint4* out = reinterpret_cast<uint4*>(out_slot);
 #pragma unroll
   for (uint32_t j = 0; j < kUSlotWords / 4; ++j) out[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
-}
-
-// One thread per user: its slot (list_off null: no lists, such users overflow).
-template <int BITS>
-__global__ void __launch_bounds__(kBlock) k_user_slots(const uint32_t* __restrict__ t_off, const uint32_t* __restrict__ t_nbr,
-                                                       uint32_t n_users, const uint32_t* __restrict__ lab,
-                                                       const uint32_t* __restrict__ cov_off,
-                                                       const uint32_t* __restrict__ cov_pre, uint32_t n_groups,
-                                                       const uint32_t* __restrict__ list_off, uint32_t* __restrict__ list,
-                                                       uint32_t* __restrict__ slots) {
-  const uint32_t u = blockIdx.x * kBlock + threadIdx.x;
-  if (u >= n_users) return;
-  user_slot<BITS>(t_off, t_nbr, u, lab, cov_off, cov_pre, n_groups, list_off ? list_off[u] : kNone, list,
-                  slots + (size_t)u * kUSlotWords);
 }
 
 // One pass over every user (the random reads of its groups' labels and covers once): inline slots
@@ -1211,3 +1186,14 @@ __global__ void __launch_bounds__(kBlock) k_closure_join(Ctx c, CjArgs a) {
   ax.load_hot();
   cj_block<BITS, TAB, CPW, HALF>(ax, blockIdx.x, true, t_start);
 }
+
+// The closure join's variants: the kernel a HIP launch takes and, for the one the engine also
+// dispatches into its HSA queues (aql.inc), its demangled name in libgck_kernels.co — side by side,
+// so that the two cannot name different kernels.
+struct CjVariant {
+  void (*kernel)(Ctx, CjArgs);
+  const char* aql_name;  // null: launched through HIP only
+  uint32_t cpw;          // checks per wave
+};
+
+static const CjVariant& cj_variant(uint32_t slot_bits, bool small);  // (engine.hip, beside the join's launch)

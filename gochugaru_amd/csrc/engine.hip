@@ -2428,6 +2428,15 @@ static void publish_launch(Workspace& w, hipStream_t st) {
   w.b_seq = seq;
 }
 
+// A later stage's end (bundles_finish): its counters published, awaited and added to the engine's;
+// the publication zeroed them on the device.
+static void publish_and_collect(Engine& e, Workspace& w) {
+  publish_launch(w, w.b_st);
+  wait_published(w, w.b_st, w.b_seq);
+  add_counters(e, w, *w.h_ctr);
+  w.ctr_clean = true;
+}
+
 static BundleArgs bundle_args(Engine& e, Workspace& w, const gck_item* d_items, uint32_t n, uint8_t* d_perm,
                               int32_t* d_err) {
   BundleArgs a{};
@@ -2488,9 +2497,6 @@ static void launch_wave_bundles(Engine& e, Workspace& w, const Ctx& c, const Bun
   HIP_OK(hipGetLastError());
 }
 
-// Stage A of a bundle batch (n <= max_batch): the persistent wave-bundle kernel over every
-// check, then — for a host batch — the copy of the results into the pinned staging, and the
-// publication the host spins on. Nothing waits here.
 // The request check of host items that no join reads in place (include/gck.h: a context_slot
 // beyond the call's contexts is GCK_E_INVALID_ARGUMENT).
 static void slot_error(uint32_t i, uint32_t slot, uint32_t limit) {
@@ -2507,6 +2513,18 @@ static void validate_slots(const gck_item* items, uint32_t n, uint32_t limit) {
 static bool label_join_on(const Engine& e) {
   const DeviceSnapshot& ds = *e.dev;
   return ds.d_lj && (!(ds.d_cj && !(e.cfg.flags & GCK_FLAG_NO_CLOSURE)) || ds.lj_preferred);
+}
+
+// The snapshot has a one-round join (label or closure) for stage A to begin with.
+static bool join_on(const Engine& e) {
+  return label_join_on(e) || (e.dev->d_cj && !(e.cfg.flags & GCK_FLAG_NO_CLOSURE));
+}
+
+// A batch over host memory can run zero-copy: its join, dispatched into the engine's queues, reads
+// the request from and writes the results into pinned host memory (submit_batch, submit_uniform).
+// Not with check contexts, nor profiled (GCK_AQL=0 or a profiled batch take the DMA path).
+static bool zero_copy_ok(const Engine& e, const Workspace& w) {
+  return e.aql && w.aql_kernarg && !w.cav_on && !(e.cfg.flags & (GCK_FLAG_PROFILE | GCK_FLAG_NO_BUNDLE)) && join_on(e);
 }
 
 // An AQL-dispatched join reports through per-block summaries (closure.inc block_summary): its
@@ -2581,38 +2599,43 @@ static bool aql_build_done(Engine& e) {
   return true;
 }
 
-static void bundles_launch(Engine& e, Workspace& w, const gck_item* d_items, uint32_t n, int64_t now_us,
-                           uint8_t* d_perm, int32_t* d_err, hipStream_t st, bool host_out) {
-  Ctx c = make_ctx(e, w, now_us, st, false);  // (the bundles below wait for the index patch: wait_patch)
-  c.ck_items = d_items;
-  BundleArgs a = bundle_args(e, w, d_items, n, d_perm, d_err);
+// Where stage A of the batch in flight goes: which kernel it begins with, how that kernel is
+// started (HIP launch, dispatch into the engine's HSA queues, a post to the resident join), whether
+// the wave bundles are chained behind it, and who publishes the batch.
+struct Route {
+  bool host_out;   // a host batch moved by DMA: its results are copied to the host buffers (w.b_hperm)
+  bool lj, cj;     // stage A begins with the label join / the closure join (neither: the wave bundles)
+  bool timed;      // its stage A is bracketed by events or dispatch timestamps
+  bool chained;    // the wave bundles over the join's deferred list follow it on the device
+  bool ctr_clean;  // the device counters were clean before it: nothing precedes the join on the stream
+  bool aql_ok;     // the join may be dispatched into the engine's HSA queues
+  bool self_pub;   // the join publishes the batch from its last block (no k_publish)
+};
+
+// The only reader of the engine's flags, Engine::defer_recent, aql_build_done and GCK_AQL_TIMED on
+// the batch path. Called before stage A touches the workspace (it reads w.ctr_clean as the previous
+// batch left it, and counts the batch for the event sampling).
+static Route stage_a_route(Engine& e, Workspace& w) {
+  Route r{};
+  r.host_out = w.b_hperm != nullptr;
   static const char* timing_env = debug_env("GCK_DEBUG_TIMING");
-  if (timing_env) HIP_OK(hipMemsetAsync(w.timing, 0, w.timing_cap * 8, st));
-  const bool ctr_was_clean = w.ctr_clean && !timing_env;
-  if (!w.ctr_clean) HIP_OK(hipMemsetAsync(w.ctr, 0, sizeof(DevCounters) + kBCtrs * sizeof(unsigned), st));  // + b_ctrs
-  w.ctr_clean = false;
+  r.ctr_clean = w.ctr_clean && !timing_env;
   // GCK_FLAG_PROFILE: one event opens stage A, one closes it, on every 4th batch of the workspace
   // (each record is a host API call on the per-batch path)
-  w.b_timed = (e.cfg.flags & GCK_FLAG_PROFILE) && (w.n_batches++ % 4 == 0);
+  r.timed = (e.cfg.flags & GCK_FLAG_PROFILE) && (w.n_batches++ % 4 == 0);
   // the closure-join stage answers the nested-group checks it can (closure.inc); what it leaves is
   // counted in the published counters and bundled by bundles_finish, so the common batch is two
   // launches: the join and the publication
   const DeviceSnapshot& ds = *e.dev;
-  const bool cj_ok = ds.d_cj && !(e.cfg.flags & GCK_FLAG_NO_CLOSURE);
-  const bool lj = label_join_on(e);
-  const bool cj = cj_ok && !lj;
-  // the checks' caveat flags start cleared: by the label join with the caveat plane itself (an AQL
-  // dispatch is not ordered after this stream's work), else here
-  if (w.cav_on && !(lj && ds.lj_cav)) HIP_OK(hipMemsetAsync(w.cav_flag, 0, n, st));
-  w.b_closure = cj || lj;
-  w.b_label = lj;
+  r.lj = label_join_on(e);
+  r.cj = join_on(e) && !r.lj;
   // chained: the wave bundles over the join's deferred list follow it in stage A, reading the
   // list's length on the device — no host round trip in the wait — when recent batches of the
   // engine left checks (a persistent bundle launch over an empty list costs a few microseconds,
   // the round trip tens; engine.hpp Engine::defer_recent)
   // (not with the resident join: its requests are posted to the running launch, and what they
   // leave is bundled after the wait like an AQL-dispatched join's)
-  w.b_chained = w.b_closure && e.defer_recent.load(std::memory_order_relaxed) > 0 && !e.res;
+  r.chained = (r.lj || r.cj) && e.defer_recent.load(std::memory_order_relaxed) > 0 && !e.res;
   // the join publishes the batch itself unless something must follow it first: a host batch's
   // copies, the chained bundles, or — for a device batch on the engine's stream, whose caller has
   // no stream to order its reads after the kernel's end — the end-of-kernel L2 write-back
@@ -2628,206 +2651,222 @@ static void bundles_launch(Engine& e, Workspace& w, const gck_item* d_items, uin
   static const bool aql_timed = !(getenv("GCK_AQL_TIMED") && atoi(getenv("GCK_AQL_TIMED")) == 0);
   // (a batch with check contexts: the label join with the caveat plane, whose Ctx travels in the
   // kernarg block and which clears the checks' caveat flags itself — nothing on the HIP stream)
-  const bool aql_ok = w.b_own_stream && !host_out && !w.b_chained && ctr_was_clean && e.aql &&
-                      w.aql_kernarg && (!w.cav_on || (lj && ds.lj_cav)) && (lj || cj) &&
-                      ((aql_timed && e.aql->tick_hz) || !w.b_timed) && aql_build_done(e);
-  w.b_aql = false;
-  w.b_res = false;
-  w.b_sum_blocks = 0;
+  r.aql_ok = w.b_own_stream && !r.host_out && !r.chained && r.ctr_clean && e.aql && w.aql_kernarg &&
+             (!w.cav_on || (r.lj && ds.lj_cav)) && (r.lj || r.cj) && ((aql_timed && e.aql->tick_hz) || !r.timed) &&
+             aql_build_done(e);
   // (GCK_DEBUG_HIP_SELFPUB: an engine-stream batch launched through HIP publishes itself from its
   // last block as an AQL-dispatched one does — the dispatch-span attribution of tools/aql_span.sh;
   // its results are not written back before the publication, so only device readers may use them)
   static const bool dbg_selfpub = debug_env("GCK_DEBUG_HIP_SELFPUB") != nullptr;
-  const bool self_pub = !host_out && !w.b_chained && (!w.b_own_stream || aql_ok || dbg_selfpub);
-  const uint32_t coherent = 0u;  // (results are published by the kernel end's write-back)
-  // the join into the HSA queue when aql_ok and the code object has this variant
-  auto aql_try = [&](const char* name, const void* args, size_t bytes, uint32_t blocks) {
-    if (!aql_ok) return false;
-    const AqlKernel* k = aql_kernel(e.aql, name);
-    if (!k) return false;
+  r.self_pub = !r.host_out && !r.chained && (!w.b_own_stream || r.aql_ok || dbg_selfpub);
+  return r;
+}
+
+// The arguments LjArgs and CjArgs name alike, for the batch in flight on w: the request, the
+// deferred list, the context-slot check of items read in place, a uniform batch's pairs, and the
+// join's own publication. (A join's `coherent` / `mode` word stays 0: the results are published by
+// the kernel end's write-back.)
+template <typename Args>
+static void join_args(const Route& r, Workspace& w, const BundleArgs& a, Args& j) {
+  j.items = w.b_items;
+  j.n = w.b_n;
+  j.out_perm = w.b_dperm;
+  j.out_err = w.b_derr;
+  j.deferred = w.c_deferred;
+  j.n_deferred = w.b_ctrs + 4;
+  j.timing = a.timing ? a.timing + (size_t)kTimingWords * (w.b_n + 1) * 2 : nullptr;
+  if (w.b_validate) {
+    j.bad_slot = &w.ctr->bad_slot;
+    j.slot_limit = w.cav.n_given;
+  }
+  if (w.u_join) uniform_args(w, j);
+  // self-published (a host-side stream query or synchronisation per batch instead costs ~10 us,
+  // 11 G -> 3-5 G checks/s)
+  if (r.self_pub) {
+    j.pub = reinterpret_cast<unsigned*>(w.ctr);
+    j.pub_words = kPubWords;
+    j.h_out = w.d_hpub;
+    j.done = w.b_ctrs + kBDone;
+    j.seq = ++w.pub_seq;
+    w.b_seq = j.seq;
+  }
+}
+
+// Stage A as the label join (labels.inc): one round of slot lines per check; what it leaves goes to
+// the wave bundles through the same deferred list as the closure join's.
+static void label_join_start(Engine& e, Workspace& w, const Route& r, const Ctx& c, const BundleArgs& a) {
+  const DeviceSnapshot& ds = *e.dev;
+  const uint32_t n = w.b_n;
+  const hipStream_t st = w.b_st;
+  LjArgs j{};
+  join_args(r, w, a, j);
+  lj_table_args(ds, j);
+  j.dirty = ds.lj_dirty;
+  j.dov = ds.lj_dov;
+  j.csrs = ds.csrs;
+  j.afp = ds.lj_afp;
+  j.n_csrs = ds.n_csrs;
+  j.afp_n = ds.lj_afp_n;
+  j.cav_static = ds.cav_static;
+  j.anc = ds.lj_anc;
+  bool cl = false;
+  const bool cav = ds.lj_cav && w.cav_on;  // caveated pairs decided under the check contexts (cav_state)
+  if (cav) {
+    // the dense outcome table and the instances in LDS when they fit (labels.inc LjCavLds)
+    const uint32_t rows = w.cav.n_dist ? (uint32_t)(w.cav.dense.size() / w.cav.n_dist) : 0u;
+    cl = !w.cav_lazy && ds.n_cav <= kLjCavInst && w.cav.dense.size() <= kLjCavDense && w.cav.n_ctx <= kLjCavCtx &&
+         w.cav.n_dist <= 255 && rows < 0xFFFFu;
+    j.cav_n = ds.n_cav;
+    j.cav_rows = rows;
+  }
+  // into the HSA queue when the route allows it and the code object has this variant
+  const LjVariant& v = lj_variant(ds, cl);
+  const AqlKernel* ak = r.aql_ok ? aql_kernel(e.aql, v.aql_name) : nullptr;
+  if (cav && ak) {
+    j.cx = static_cast<const Ctx*>(aql_extra(w));  // (written with the arguments)
+  } else if (cav && e.aql && w.aql_kernarg && w.aql_devargs) {
+    aql_put_extra(*e.aql, w, &c, sizeof(Ctx));  // (through the BAR into VRAM: no copy on the stream)
+    j.cx = static_cast<const Ctx*>(aql_extra(w));
+  } else if (cav) {
+    *w.h_ctx = c;
+    HIP_OK(hipMemcpyAsync(w.d_ctx, w.h_ctx, sizeof(Ctx), hipMemcpyHostToDevice, st));
+    j.cx = w.d_ctx;
+  }
+  if (ak) {
+    if (j.h_out) aql_summaries(w, j.coherent, j.h_out, j.done, j.n_deferred, lj_blocks(n));
     aql_after_build(e);
-    aql_dispatch(*e.aql, w, *k, args, bytes, blocks, w.b_timed);
+    aql_dispatch(*e.aql, w, *ak, &j, sizeof(j), lj_blocks(n), r.timed, cav ? &c : nullptr, cav ? sizeof(Ctx) : 0);
     w.b_aql = true;
-    return true;
-  };
-  if (lj) {
-    // the label join (labels.inc): one round of slot lines per check; what it leaves goes to the
-    // wave bundles through the same deferred list as the closure join's
-    LjArgs j{};
-    j.items = d_items;
-    j.n = n;
-    j.out_perm = d_perm;
-    j.out_err = d_err;
-    j.deferred = w.c_deferred;
-    j.n_deferred = w.b_ctrs + 4;
-    j.table = ds.d_lj;
-    j.n_fwd = ds.n_fwd;
-    j.table_bytes = (uint32_t)((ds.lj_host.size() + 3) & ~(size_t)3);
-    j.o_meta = ds.lj_o_meta;
-    j.dirty = ds.lj_dirty;
-    j.dov = ds.lj_dov;
-    j.csrs = ds.csrs;
-    j.afp = ds.lj_afp;
-    j.n_csrs = ds.n_csrs;
-    j.afp_n = ds.lj_afp_n;
-    j.cav_static = ds.cav_static;
-    j.anc = ds.lj_anc;
-    bool cl = false;
-    const bool cav = ds.lj_cav && w.cav_on;  // caveated pairs decided under the check contexts (cav_state)
-    if (cav) {
-      // the dense outcome table and the instances in LDS when they fit (labels.inc LjCavLds)
-      const uint32_t rows = w.cav.n_dist ? (uint32_t)(w.cav.dense.size() / w.cav.n_dist) : 0u;
-      cl = !w.cav_lazy && ds.n_cav <= kLjCavInst && w.cav.dense.size() <= kLjCavDense && w.cav.n_ctx <= kLjCavCtx &&
-           w.cav.n_dist <= 255 && rows < 0xFFFFu;
-      j.cav_n = ds.n_cav;
-      j.cav_rows = rows;
-    }
-    j.timing = a.timing ? a.timing + (size_t)kTimingWords * (n + 1) * 2 : nullptr;
-    if (w.b_validate) {
-      j.bad_slot = &w.ctr->bad_slot;
-      j.slot_limit = w.cav.n_given;
-    }
-    if (w.u_join) uniform_args(w, j);
-    if (self_pub) {  // self-published (see the closure join below)
-      j.pub = reinterpret_cast<unsigned*>(w.ctr);
-      j.pub_words = kPubWords;
-      j.h_out = w.d_hpub;
-      j.done = w.b_ctrs + kBDone;
-      j.seq = ++w.pub_seq;
-      j.coherent = coherent;
-      w.b_seq = j.seq;
-    }
-    static const char* const lj_names[8] = {"void gck::k_label_join<24, 16u, 32u, false>(gck::LjArgs)",
-                                            "void gck::k_label_join<24, 32u, 32u, false>(gck::LjArgs)",
-                                            "void gck::k_label_join<32, 16u, 32u, false>(gck::LjArgs)",
-                                            "void gck::k_label_join<32, 32u, 32u, false>(gck::LjArgs)",
-                                            "void gck::k_label_join<24, 16u, 32u, true>(gck::LjArgs)",
-                                            "void gck::k_label_join<24, 32u, 32u, true>(gck::LjArgs)",
-                                            "void gck::k_label_join<32, 16u, 32u, true>(gck::LjArgs)",
-                                            "void gck::k_label_join<32, 32u, 32u, true>(gck::LjArgs)"};
-    const int v = (cl ? 4 : 0) + (ds.lj_bits == 24 ? 0 : 2) + (ds.lj_sw == 16 ? 0 : 1);
-    const AqlKernel* ak = aql_ok ? aql_kernel(e.aql, lj_names[v]) : nullptr;
-    if (cav && ak) {
-      j.cx = static_cast<const Ctx*>(aql_extra(w));  // (written with the arguments)
-    } else if (cav && e.aql && w.aql_kernarg && w.aql_devargs) {
-      aql_put_extra(*e.aql, w, &c, sizeof(Ctx));  // (through the BAR into VRAM: no copy on the stream)
-      j.cx = static_cast<const Ctx*>(aql_extra(w));
-    } else if (cav) {
-      *w.h_ctx = c;
-      HIP_OK(hipMemcpyAsync(w.d_ctx, w.h_ctx, sizeof(Ctx), hipMemcpyHostToDevice, st));
-      j.cx = w.d_ctx;
-    }
-    if (ak) {
-      const uint32_t blocks = (n + 32u * kWaves - 1) / (32u * kWaves);
-      if (j.h_out) aql_summaries(w, j.coherent, j.h_out, j.done, j.n_deferred, blocks);
-      aql_after_build(e);
-      aql_dispatch(*e.aql, w, *ak, &j, sizeof(j), blocks, w.b_timed,
-                   cav ? &c : nullptr, cav ? sizeof(Ctx) : 0);
-      w.b_aql = true;
-    } else {
-      lj_launch(ds, j, n, st, w.b_timed ? w.ev0 : nullptr, w.b_timed && !w.b_chained ? w.ev1 : nullptr, cl);
-    }
-  } else if (cj) {
-    CjArgs j{};
-    j.items = d_items;
-    j.n = n;
-    j.out_perm = d_perm;
-    j.out_err = d_err;
-    j.deferred = w.c_deferred;
-    j.n_deferred = w.b_ctrs + 4;
-    j.table = ds.d_cj;
-    j.n_fwd = ds.n_fwd;
-    j.n_desc = ds.cj_n_desc;
-    j.n_types = ds.n_types;
-    j.table_bytes = cj_table_bytes(ds.cj_host.size());  // (build_closure_join pads the table to it)
-    j.o_meta = ds.cj_o_meta;
-    j.o_entries = ds.cj_o_entries;
-    j.timing = a.timing ? a.timing + (size_t)kTimingWords * (n + 1) * 2 : nullptr;
-    if (w.b_validate) {
-      j.bad_slot = &w.ctr->bad_slot;
-      j.slot_limit = w.cav.n_given;
-    }
-    if (w.u_join) uniform_args(w, j);
-    // self-published as the label join (a host-side stream query or synchronisation per batch
-    // instead costs ~10 us, 11 G -> 3-5 G checks/s)
-    if (self_pub) {
-      j.pub = reinterpret_cast<unsigned*>(w.ctr);
-      j.pub_words = kPubWords;
-      j.h_out = w.d_hpub;
-      j.done = w.b_ctrs + kBDone;
-      j.seq = ++w.pub_seq;
-      j.mode = coherent;
-      w.b_seq = j.seq;
-    }
-    cj_seal(j);  // (the pointers above are final: their null tests as mode bits)
-    // a timed batch's events are the kernel's own start and stop (hipExtLaunchKernel), not markers
-    // around its dispatch, so they agree with a profiler's kernel duration
-    // 32 checks per wave where the slot entries are 24-bit and the table is small: each wave waits
-    // for the slowest of 64 lines instead of 128 (solo launch 12.1-12.3 vs 12.8-12.9 us, the same
-    // throughput, profiles/r02/sweep/cpw*)
-    const bool small = j.table_bytes <= kCjLdsBytesSmall;
-    const bool fast = ds.slot_bits == 24 && small;
-    const uint32_t cpw = fast ? 32u : 64u;
-    const dim3 grid((n + cpw * kWaves - 1) / (cpw * kWaves)), block(kBlock);
-    // (a timed batch with chained bundles stops its clock after them: stage A is both)
-    hipEvent_t e0 = w.b_timed ? w.ev0 : nullptr, e1 = w.b_timed && !w.b_chained ? w.ev1 : nullptr;
-    struct {
-      Ctx c;
-      CjArgs j;
-    } cj_args{c, j};  // (the kernarg segment: the two by-value parameters in order)
-    static_assert(offsetof(decltype(cj_args), j) == 344, "k_closure_join kernarg layout (Ctx, CjArgs)");
-    // (the join's hot arguments are one 64-B line of the segment only in a 64-B aligned block)
-    if (aql_ok && ((uintptr_t)w.aql_kernarg & 63u))
-      throw Error(GCK_E_DEVICE, "engine invariant violated: kernarg block alignment");
-    // (half slots: the first 32 B of each resource slot, closure.inc HALF)
-    if (fast && aql_ok && j.h_out && aql_kernel(e.aql, "void gck::k_closure_join<24, 2048u, 32u, true>(gck::Ctx, gck::CjArgs)"))
-      aql_summaries(w, cj_args.j.mode, cj_args.j.h_out, cj_args.j.done, cj_args.j.n_deferred, grid.x);
-    // the resident join (resident.inc) takes the request without a dispatch of its own
-    const bool res_ok = fast && aql_ok && e.res && !w.b_timed && w.b_sum_blocks == grid.x &&
-                        (cj_args.j.mode & kPubBySignal);
-    static const bool dbg_res = debug_env("GCK_DEBUG_RES") != nullptr;  // (why a batch did not go resident)
-    if (dbg_res && e.res && !res_ok)
-      std::fprintf(stderr, "[gck res] not resident: fast=%d aql_ok=%d own=%d host_out=%d chained=%d clean=%d cav=%d timed=%d sum=%u/%u pub=%u\n",
-                   (int)fast, (int)aql_ok, (int)w.b_own_stream, (int)host_out, (int)w.b_chained, (int)ctr_was_clean,
-                   (int)w.cav_on, (int)w.b_timed, w.b_sum_blocks, grid.x, cj_args.j.mode);
-    if (res_ok) {
-      aql_after_build(e);
-      res_post(e, w, cj_args.j, grid.x);
-    } else if (fast && aql_try("void gck::k_closure_join<24, 2048u, 32u, true>(gck::Ctx, gck::CjArgs)", &cj_args,
-                        sizeof(cj_args), grid.x)) {
-    } else if (fast)
-      hipExtLaunchKernelGGL((k_closure_join<24, kCjLdsBytesSmall, 32, true>), grid, block, 0, st, e0, e1, 0, c, j);
-    else if (ds.slot_bits == 24)
-      hipExtLaunchKernelGGL((k_closure_join<24, kCjLdsBytes>), grid, block, 0, st, e0, e1, 0, c, j);
-    else if (small)
-      hipExtLaunchKernelGGL((k_closure_join<32, kCjLdsBytesSmall>), grid, block, 0, st, e0, e1, 0, c, j);
-    else
-      hipExtLaunchKernelGGL((k_closure_join<32, kCjLdsBytes>), grid, block, 0, st, e0, e1, 0, c, j);
-    HIP_OK(hipGetLastError());
+  } else {
+    lj_launch(v, j, n, st, r.timed ? w.ev0 : nullptr, r.timed && !r.chained ? w.ev1 : nullptr);
+  }
+}
+
+// The closure join's variants (closure.inc CjVariant).
+// 32 checks per wave where the slot entries are 24-bit and the table is small: each wave waits
+// for the slowest of 64 lines instead of 128 (solo launch 12.1-12.3 vs 12.8-12.9 us, the same
+// throughput, profiles/r02/sweep/cpw*)
+// (half slots: the first 32 B of each resource slot, closure.inc HALF)
+// (tests/test_aql_codeobject.py reads the names from this text)
+static const CjVariant& cj_variant(uint32_t slot_bits, bool small) {
+  static const CjVariant rows[4] = {
+      {k_closure_join<24, kCjLdsBytesSmall, 32, true>, "void gck::k_closure_join<24, 2048u, 32u, true>(gck::Ctx, gck::CjArgs)", 32u},
+      {k_closure_join<24, kCjLdsBytes>, nullptr, 64u},
+      {k_closure_join<32, kCjLdsBytesSmall>, nullptr, 64u},
+      {k_closure_join<32, kCjLdsBytes>, nullptr, 64u}};
+  return rows[(slot_bits == 24 ? 0 : 2) + (small ? 0 : 1)];
+}
+
+// Stage A as the closure join (closure.inc).
+static void closure_join_start(Engine& e, Workspace& w, const Route& r, const Ctx& c, const BundleArgs& a) {
+  const DeviceSnapshot& ds = *e.dev;
+  const uint32_t n = w.b_n;
+  const hipStream_t st = w.b_st;
+  CjArgs j{};
+  join_args(r, w, a, j);
+  j.table = ds.d_cj;
+  j.n_fwd = ds.n_fwd;
+  j.n_desc = ds.cj_n_desc;
+  j.n_types = ds.n_types;
+  j.table_bytes = cj_table_bytes(ds.cj_host.size());  // (build_closure_join pads the table to it)
+  j.o_meta = ds.cj_o_meta;
+  j.o_entries = ds.cj_o_entries;
+  cj_seal(j);  // (the pointers above are final: their null tests as mode bits)
+  // (only the variant with an AQL name is dispatched or posted; its twins launch through HIP)
+  const CjVariant& v = cj_variant(ds.slot_bits, j.table_bytes <= kCjLdsBytesSmall);
+  const AqlKernel* ak = r.aql_ok && v.aql_name ? aql_kernel(e.aql, v.aql_name) : nullptr;
+  const dim3 grid((n + v.cpw * kWaves - 1) / (v.cpw * kWaves)), block(kBlock);
+  // a timed batch's events are the kernel's own start and stop (hipExtLaunchKernel), not markers
+  // around its dispatch, so they agree with a profiler's kernel duration
+  // (a timed batch with chained bundles stops its clock after them: stage A is both)
+  hipEvent_t e0 = r.timed ? w.ev0 : nullptr, e1 = r.timed && !r.chained ? w.ev1 : nullptr;
+  struct {
+    Ctx c;
+    CjArgs j;
+  } cj_args{c, j};  // (the kernarg segment: the two by-value parameters in order)
+  static_assert(offsetof(decltype(cj_args), j) == 344, "k_closure_join kernarg layout (Ctx, CjArgs)");
+  // (the join's hot arguments are one 64-B line of the segment only in a 64-B aligned block)
+  if (r.aql_ok && ((uintptr_t)w.aql_kernarg & 63u))
+    throw Error(GCK_E_DEVICE, "engine invariant violated: kernarg block alignment");
+  if (ak && j.h_out)
+    aql_summaries(w, cj_args.j.mode, cj_args.j.h_out, cj_args.j.done, cj_args.j.n_deferred, grid.x);
+  // the resident join (resident.inc) takes the request without a dispatch of its own
+  const bool res_ok = ak && e.res && !r.timed && w.b_sum_blocks == grid.x && (cj_args.j.mode & kPubBySignal);
+  if (res_ok) {
+    aql_after_build(e);
+    res_post(e, w, cj_args.j, grid.x);
+  } else if (ak) {
+    aql_after_build(e);
+    aql_dispatch(*e.aql, w, *ak, &cj_args, sizeof(cj_args), grid.x, r.timed);
+    w.b_aql = true;
+  } else {
+    hipExtLaunchKernelGGL(v.kernel, grid, block, 0, st, e0, e1, 0, c, j);
+  }
+  HIP_OK(hipGetLastError());
+}
+
+// Results to the host buffers of a batch moved by DMA: the pinned staging, or the caller's own
+// pinned buffers (submit_batch). Nothing for a device or a zero-copy batch.
+static void results_to_host(Workspace& w) {
+  if (!w.b_hperm) return;
+  HIP_OK(hipMemcpyAsync(w.b_xperm, w.b_dperm, w.b_n, hipMemcpyDeviceToHost, w.b_st));
+  HIP_OK(hipMemcpyAsync(w.b_xerr, w.b_derr, (size_t)w.b_n * 4, hipMemcpyDeviceToHost, w.b_st));
+}
+
+// Stage A of the bundle batch in flight on w (submit_batch; n <= max_batch): the join or the
+// persistent wave-bundle kernel over every check, then — for a host batch — the copy of the
+// results into the pinned staging, and the publication the host spins on. Nothing waits here.
+static void bundles_launch(Engine& e, Workspace& w) {
+  const hipStream_t st = w.b_st;
+  const uint32_t n = w.b_n;
+  Ctx c = make_ctx(e, w, w.b_now, st, false);  // (the bundles below wait for the index patch: wait_patch)
+  c.ck_items = w.b_items;
+  BundleArgs a = bundle_args(e, w, w.b_items, n, w.b_dperm, w.b_derr);
+  const Route r = stage_a_route(e, w);
+  if (a.timing) HIP_OK(hipMemsetAsync(w.timing, 0, w.timing_cap * 8, st));  // (GCK_DEBUG_TIMING)
+  if (!w.ctr_clean) HIP_OK(hipMemsetAsync(w.ctr, 0, sizeof(DevCounters) + kBCtrs * sizeof(unsigned), st));  // + b_ctrs
+  w.ctr_clean = false;
+  // the checks' caveat flags start cleared: by the label join with the caveat plane itself (an AQL
+  // dispatch is not ordered after this stream's work), else here
+  if (w.cav_on && !(r.lj && e.dev->lj_cav)) HIP_OK(hipMemsetAsync(w.cav_flag, 0, n, st));
+  w.b_timed = r.timed;
+  w.b_label = r.lj;
+  w.b_closure = r.lj || r.cj;
+  w.b_chained = r.chained;
+  w.b_aql = false;
+  w.b_res = false;
+  w.b_sum_blocks = 0;
+  if (r.lj) {
+    label_join_start(e, w, r, c, a);
+  } else if (r.cj) {
+    closure_join_start(e, w, r, c, a);
   } else {
     wait_patch(e, w, st);
-    if (w.b_timed) HIP_OK(hipEventRecord(w.ev0, st));
+    if (r.timed) HIP_OK(hipEventRecord(w.ev0, st));
     launch_wave_bundles(e, w, c, a, st);
-    if (w.b_timed) HIP_OK(hipEventRecord(w.ev1, st));
+    if (r.timed) HIP_OK(hipEventRecord(w.ev1, st));
   }
-  if (w.b_chained) {
+  if (r.chained) {
     BundleArgs b = a;
     b.idx = w.c_deferred;
     b.n_dev = w.b_ctrs + 4;
     wait_patch(e, w, st);
     launch_wave_bundles(e, w, c, b, st);
-    if (w.b_timed) HIP_OK(hipEventRecord(w.ev1, st));
+    if (r.timed) HIP_OK(hipEventRecord(w.ev1, st));
   }
-  if (host_out) {
-    HIP_OK(hipMemcpyAsync(w.b_xperm, d_perm, n, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(w.b_xerr, d_err, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  results_to_host(w);
+  if (!w.b_aql && !w.b_res && (!r.self_pub || !w.b_closure)) publish_launch(w, st);
+  // GCK_DEBUG_RES: why a batch did not go to the resident join (sum: the blocks that report through
+  // summary slots, which a resident request needs; 0: the join publishes from its last block)
+  static const bool dbg_res = debug_env("GCK_DEBUG_RES") != nullptr;
+  if (dbg_res && e.res && !w.b_res) {
+    const bool fast = r.cj && cj_variant(e.dev->slot_bits, cj_table_bytes(e.dev->cj_host.size()) <= kCjLdsBytesSmall).aql_name;
+    std::fprintf(stderr,
+                 "[gck res] batch n=%u not resident: lj=%d cj=%d fast=%d aql_ok=%d aql=%d chained=%d clean=%d own=%d "
+                 "host_out=%d cav=%d timed=%d sum=%u\n",
+                 n, (int)r.lj, (int)r.cj, (int)fast, (int)r.aql_ok, (int)w.b_aql, (int)r.chained, (int)r.ctr_clean,
+                 (int)w.b_own_stream, (int)r.host_out, (int)w.cav_on, (int)r.timed, w.b_sum_blocks);
   }
-  if (!w.b_aql && !w.b_res && (!self_pub || !w.b_closure)) publish_launch(w, st);
-  static const bool dbg_res_any = debug_env("GCK_DEBUG_RES") != nullptr;
-  if (dbg_res_any && e.res && !w.b_res)
-    std::fprintf(stderr, "[gck res] batch n=%u not resident: lj=%d cj=%d aql_ok=%d aql=%d chained=%d clean=%d own=%d host_out=%d\n",
-                 n, (int)lj, (int)cj, (int)aql_ok, (int)w.b_aql, (int)w.b_chained, (int)ctr_was_clean,
-                 (int)w.b_own_stream, (int)host_out);
 }
 
 static void debug_dump(Engine& e, Workspace& w, uint32_t n);
@@ -2837,8 +2876,13 @@ constexpr uint32_t kChainLeftovers = 1;  // leftovers of a batch that make the n
 // Stages B and C of a bundle batch after stage A was published: the checks stage A deferred
 // (giant, or rooted high enough to need exact depth) through the workgroup bundles and/or the
 // grid-wide path, synchronously. Returns the device time of the batch.
-static float bundles_finish(Engine& e, Workspace& w, const gck_item* d_items, uint32_t n, int64_t now_us,
-                            uint8_t* d_perm, int32_t* d_err, hipStream_t st, bool host_out) {
+static float bundles_finish(Engine& e, Workspace& w) {
+  const gck_item* const d_items = w.b_items;
+  const uint32_t n = w.b_n;
+  const int64_t now_us = w.b_now;
+  uint8_t* const d_perm = w.b_dperm;
+  int32_t* const d_err = w.b_derr;
+  const hipStream_t st = w.b_st;
   if (w.b_aql) aql_wait(*e.aql, w);  // (the kernel has ended: its publication is complete)
   if (w.b_res) res_wait(e, w);       // (the resident join has finished the request's last chunk)
   if ((w.b_aql || w.b_res) && w.b_sum_blocks) aql_collect(w);
@@ -2891,14 +2935,8 @@ static float bundles_finish(Engine& e, Workspace& w, const gck_item* d_items, ui
     if (w.b_timed) HIP_OK(hipEventRecord(w.ev0, st));
     launch_wave_bundles(e, w, c, a, st);
     if (w.b_timed) HIP_OK(hipEventRecord(w.ev1, st));
-    if (host_out) {
-      HIP_OK(hipMemcpyAsync(w.b_xperm, d_perm, n, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipMemcpyAsync(w.b_xerr, d_err, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    }
-    publish_launch(w, st);
-    wait_published(w, st, w.b_seq);
-    add_counters(e, w, *w.h_ctr);
-    w.ctr_clean = true;
+    results_to_host(w);
+    publish_and_collect(e, w);
     if (w.b_timed) {
       float am = 0.f;
       elapsed_ms(&am, w.ev0, w.ev1);
@@ -2943,10 +2981,7 @@ static float bundles_finish(Engine& e, Workspace& w, const gck_item* d_items, ui
                          dim3(bundle_block<kGiantWaves>()), 0, st, c, g);
     HIP_OK(hipGetLastError());
     if (w.b_timed) HIP_OK(hipEventRecord(w.ev1, st));
-    publish_launch(w, st);
-    wait_published(w, st, w.b_seq);
-    add_counters(e, w, *w.h_ctr);
-    w.ctr_clean = true;
+    publish_and_collect(e, w);
     if (w.b_timed) elapsed_ms(&gm, w.ev0, w.ev1);
     ms += gm;
     n_def2 = w.h_bctrs[3];
@@ -2978,10 +3013,7 @@ static float bundles_finish(Engine& e, Workspace& w, const gck_item* d_items, ui
                        d_err);
     HIP_OK(hipGetLastError());
   }
-  if (host_out) {  // the deferred checks' results, in place
-    HIP_OK(hipMemcpyAsync(w.b_xperm, d_perm, n, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(w.b_xerr, d_err, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  }
+  results_to_host(w);  // the deferred checks' results, in place
   HIP_OK(hipStreamSynchronize(st));
   return ms;
 }
@@ -3240,9 +3272,7 @@ static void submit_batch(Engine& e, Workspace& w, const gck_item* items, uint32_
   w.b_copy_perm = nullptr;
   w.b_copy_err = nullptr;
   w.b_validate = false;
-  const bool join = label_join_on(e) || (e.dev->d_cj && !(e.cfg.flags & GCK_FLAG_NO_CLOSURE));
-  if (host && e.aql && w.aql_kernarg && !w.cav_on && !(e.cfg.flags & (GCK_FLAG_PROFILE | GCK_FLAG_NO_BUNDLE)) &&
-      join) {
+  if (host && zero_copy_ok(e, w)) {
     // the join reads every item once, in place: it also checks the context slots (no host pass
     // over the items on the submitting thread)
     w.b_validate = true;
@@ -3279,19 +3309,17 @@ static void submit_batch(Engine& e, Workspace& w, const gck_item* items, uint32_
   }
   w.b_bundles = !(e.cfg.flags & GCK_FLAG_NO_BUNDLE);
   if (w.cav_on && !w.b_bundles) HIP_OK(hipMemsetAsync(w.cav_flag, 0, n, w.b_st));  // (bundles_launch: its own)
-  if (w.b_bundles) bundles_launch(e, w, w.b_items, n, now_us, w.b_dperm, w.b_derr, w.b_st, host);
+  if (w.b_bundles) bundles_launch(e, w);
   w.state = 1;
 }
 
 // The rest of a pass whose stage A is queued (bundle path), or the whole pass (grid-wide path).
 static float finish_pass(Engine& e, Workspace& w) {
-  const bool host = w.b_hperm != nullptr;
-  if (w.b_bundles) return bundles_finish(e, w, w.b_items, w.b_n, w.b_now, w.b_dperm, w.b_derr, w.b_st, host);
+  if (w.b_bundles) return bundles_finish(e, w);
   float ms = 0.f;
   check_range_wide(e, w, w.b_items, w.b_n, w.b_now, w.b_dperm, w.b_derr, w.b_st, &ms);
-  if (host) {
-    HIP_OK(hipMemcpyAsync(w.b_xperm, w.b_dperm, w.b_n, hipMemcpyDeviceToHost, w.b_st));
-    HIP_OK(hipMemcpyAsync(w.b_xerr, w.b_derr, (size_t)w.b_n * 4, hipMemcpyDeviceToHost, w.b_st));
+  if (w.b_hperm) {
+    results_to_host(w);
     HIP_OK(hipStreamSynchronize(w.b_st));
   }
   return ms;
@@ -3326,8 +3354,7 @@ static void caveat_passes(Engine& e, Workspace& w) {
     HIP_OK(hipMemsetAsync(w.cav_flag, 0, w.b_n, st));
     upload_cav_map(w, st);  // (ends with a synchronisation: the pass may be dispatched into an HSA queue)
     w.b_cav_req = w.b_cav_err = 0;
-    if (w.b_bundles)
-      bundles_launch(e, w, w.b_items, w.b_n, w.b_now, w.b_dperm, w.b_derr, st, w.b_hperm != nullptr);
+    if (w.b_bundles) bundles_launch(e, w);
     w.b_ms += finish_pass(e, w);
     std::lock_guard<std::mutex> lk(e.stats_mu);
     e.stats.caveat_passes++;
@@ -3337,8 +3364,7 @@ static void caveat_passes(Engine& e, Workspace& w) {
                      w.b_dperm, w.b_derr);
   HIP_OK(hipGetLastError());
   if (w.b_hperm) {
-    HIP_OK(hipMemcpyAsync(w.b_xperm, w.b_dperm, w.b_n, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(w.b_xerr, w.b_derr, (size_t)w.b_n * 4, hipMemcpyDeviceToHost, st));
+    results_to_host(w);
     HIP_OK(hipStreamSynchronize(st));
   }
 }
@@ -3391,6 +3417,18 @@ void drain_batches(Engine& e) {
   }
 }
 
+// Synchronous batches over device buffers on one held workspace (device_check, lookups).
+static void check_range(Engine& e, Workspace& w, const gck_item* d_items, size_t n, int64_t now_us, uint8_t* d_perm,
+                        int32_t* d_err, hipStream_t st, float* ms) {
+  for (size_t pos = 0; pos < n; pos += w.max_batch) {
+    const uint32_t len = (uint32_t)std::min(n - pos, w.max_batch);
+    submit_batch(e, w, d_items + pos, len, now_us, d_perm + pos, d_err + pos, st, false);
+    finish_batch(e, w);
+    w.state = 0;
+    *ms += w.b_ms;
+  }
+}
+
 void device_check(Engine& e, Workspace& w, const gck_item* d_items, size_t n, int64_t now_us, uint8_t* d_perm,
                   int32_t* d_err, void* stream, CavCall cav) {
   HIP_OK(hipSetDevice(e.device));
@@ -3401,24 +3439,19 @@ void device_check(Engine& e, Workspace& w, const gck_item* d_items, size_t n, in
   stage_caveats(w, std::move(cav), st);
   if (now_us == 0) now_us = wall_now_us();
   float ms = 0.f;
-  for (size_t pos = 0; pos < n; pos += w.max_batch) {
-    const uint32_t len = (uint32_t)std::min(n - pos, w.max_batch);
-    submit_batch(e, w, d_items + pos, len, now_us, d_perm + pos, d_err + pos, st, false);
-    finish_batch(e, w);
-    w.state = 0;
-    ms += w.b_ms;
-  }
+  check_range(e, w, d_items, n, now_us, d_perm, d_err, st, &ms);
   std::lock_guard<std::mutex> sl(e.stats_mu);
   e.stats.kernel_ms = ms;
 }
 
-// Host buffers: chunks of max_batch on two workspaces in turn, so that a chunk's copies and
-// host staging overlap the previous chunk's kernels.
-void device_check_host(Engine& e, Workspace* w0, Workspace* w1, const gck_item* items, size_t n, int64_t now_us,
-                       uint8_t* perm, int32_t* err, const CavCall& cav) {
-  HIP_OK(hipSetDevice(e.device));
-  if (now_us == 0) now_us = wall_now_us();
-  const size_t mb = w0->max_batch;
+// A synchronous request of n checks over host buffers: chunks of mb on two workspaces in turn, so
+// that a chunk's copies and host staging overlap the previous chunk's kernels (one workspace — a
+// pool of one, or a single chunk — runs them one after the other). submit(w, pos, len) queues the
+// chunk at request offset pos on w; complete(w) takes what w's finished chunk left (finish_batch
+// and copy_out have run) before w is used again.
+template <class Submit, class Complete>
+static void run_chunks(Engine& e, Workspace* w0, Workspace* w1, size_t n, size_t mb, const CavCall& cav, Submit submit,
+                       Complete complete) {
   const size_t n_chunks = (n + mb - 1) / mb;
   Workspace* ws[2] = {w0, (w1 && n_chunks > 1) ? w1 : w0};
   std::lock_guard<std::mutex> g0(ws[0]->m);
@@ -3426,39 +3459,29 @@ void device_check_host(Engine& e, Workspace* w0, Workspace* w1, const gck_item* 
   if (ws[1] != ws[0]) g1.reset(new std::lock_guard<std::mutex>(ws[1]->m));
   stage_caveats(*ws[0], CavCall(cav), ws[0]->stream);
   if (ws[1] != ws[0]) stage_caveats(*ws[1], CavCall(cav), ws[1]->stream);
-  // several chunks: the context slots are checked here, before any GPU work, so that a bad item
-  // fails the call with its request index and no chunk is left writing the caller's buffers (a
-  // single chunk's zero-copy join checks its own items in place)
-  if (n_chunks > 1) validate_slots(items, (uint32_t)n, ws[0]->cav.n_given);
   float ms = 0.f;
   Workspace* prev = nullptr;
+  auto finish = [&](Workspace& w) {
+    finish_batch(e, w);
+    copy_out(w);
+    complete(w);
+    w.state = 0;
+    w.u_on = false;
+    ms += w.b_ms;
+  };
   try {
     for (size_t k = 0; k < n_chunks; ++k) {
       Workspace& w = *ws[k & 1];
       const size_t pos = k * mb;
-      const uint32_t len = (uint32_t)std::min(n - pos, mb);
       if (prev == &w) {  // one workspace (a pool of one): the previous chunk completes first
-        finish_batch(e, w);
-        copy_out(w);
-        w.state = 0;
-        ms += w.b_ms;
+        finish(w);
         prev = nullptr;
       }
-      submit_batch(e, w, items + pos, len, now_us, perm + pos, err + pos, nullptr, true);
-      if (prev) {
-        finish_batch(e, *prev);
-        copy_out(*prev);
-        prev->state = 0;
-        ms += prev->b_ms;
-      }
+      submit(w, pos, (uint32_t)std::min(n - pos, mb));
+      if (prev) finish(*prev);
       prev = &w;
     }
-    if (prev) {
-      finish_batch(e, *prev);
-      copy_out(*prev);
-      prev->state = 0;
-      ms += prev->b_ms;
-    }
+    if (prev) finish(*prev);
   } catch (...) {
     // a chunk failed: every other chunk still in flight completes (its kernels end and its
     // completion signal is consumed) before the workspaces go back to the pool
@@ -3470,11 +3493,30 @@ void device_check_host(Engine& e, Workspace* w0, Workspace* w1, const gck_item* 
         }
       }
       x->state = 0;
+      x->u_on = false;
     }
     throw;
   }
   std::lock_guard<std::mutex> sl(e.stats_mu);
   e.stats.kernel_ms = ms;
+}
+
+// Host buffers: chunks of max_batch (run_chunks).
+void device_check_host(Engine& e, Workspace* w0, Workspace* w1, const gck_item* items, size_t n, int64_t now_us,
+                       uint8_t* perm, int32_t* err, const CavCall& cav) {
+  HIP_OK(hipSetDevice(e.device));
+  if (now_us == 0) now_us = wall_now_us();
+  const size_t mb = w0->max_batch;
+  run_chunks(
+      e, w0, w1, n, mb, cav,
+      [&](Workspace& w, size_t pos, uint32_t len) {
+        // several chunks: the context slots are checked here, before any GPU work, so that a bad item
+        // fails the call with its request index and no chunk is left writing the caller's buffers (a
+        // single chunk's zero-copy join checks its own items in place)
+        if (pos == 0 && n > mb) validate_slots(items, (uint32_t)n, w.cav.n_given);
+        submit_batch(e, w, items + pos, len, now_us, perm + pos, err + pos, nullptr, true);
+      },
+      [](Workspace&) {});
 }
 
 void device_submit(Engine& e, Workspace* w, const gck_item* items, size_t n, int64_t now_us, uint8_t* perm,
@@ -3498,8 +3540,7 @@ static void submit_uniform(Engine& e, Workspace& w, const gck_uniform& h, const 
                            int64_t now_us, unsigned long long* packed) {
   const uint32_t rp = (uint32_t)h.resource_type | (uint32_t)h.permission << 16;
   const uint32_t ss = (uint32_t)h.subject_type | (uint32_t)h.subject_relation << 16;
-  const bool join = label_join_on(e) || (e.dev->d_cj && !(e.cfg.flags & GCK_FLAG_NO_CLOSURE));
-  if (e.aql && w.aql_kernarg && !w.cav_on && !(e.cfg.flags & (GCK_FLAG_PROFILE | GCK_FLAG_NO_BUNDLE)) && join) {
+  if (zero_copy_ok(e, w)) {
     const size_t words = ((size_t)n + 31u) / 32u;
     const bool pin_in = host_pinned(e, pairs, (size_t)n * 8u), pin_out = host_pinned(e, packed, words * 8u);
     if (!pin_in) std::memcpy(w.h_items, pairs, (size_t)n * 8u);
@@ -3599,56 +3640,16 @@ void device_check_uniform(Engine& e, Workspace* w0, Workspace* w1, const gck_uni
   if (now_us == 0) now_us = wall_now_us();
   const size_t mb = w0->max_batch >= 32 ? (w0->max_batch & ~(size_t)31) : w0->max_batch;
   if (n > mb && mb % 32 != 0) throw Error(GCK_E_CAPACITY, "a uniform request above max_batch needs max_batch >= 32");
-  const size_t n_chunks = (n + mb - 1) / mb;
-  Workspace* ws[2] = {w0, (w1 && n_chunks > 1) ? w1 : w0};
-  std::lock_guard<std::mutex> g0(ws[0]->m);
-  std::unique_ptr<std::lock_guard<std::mutex>> g1;
-  if (ws[1] != ws[0]) g1.reset(new std::lock_guard<std::mutex>(ws[1]->m));
-  stage_caveats(*ws[0], CavCall(cav), ws[0]->stream);
-  if (ws[1] != ws[0]) stage_caveats(*ws[1], CavCall(cav), ws[1]->stream);
   std::vector<gck_item_error> errs;
-  size_t pos_of[2] = {0, 0};
-  float ms = 0.f;
-  Workspace* prev = nullptr;
-  auto complete = [&](Workspace& w) {
-    finish_batch(e, w);
-    copy_out(w);
-    uniform_collect(w, (uint32_t)pos_of[&w == ws[0] ? 0 : 1], errs);
-    w.state = 0;
-    w.u_on = false;
-    ms += w.b_ms;
-  };
-  try {
-    for (size_t k = 0; k < n_chunks; ++k) {
-      Workspace& w = *ws[k & 1];
-      const size_t pos = k * mb;
-      const uint32_t len = (uint32_t)std::min(n - pos, mb);
-      if (prev == &w) {
-        complete(w);
-        prev = nullptr;
-      }
-      pos_of[&w == ws[0] ? 0 : 1] = pos;
-      submit_uniform(e, w, h, pairs + 2 * pos, len, now_us, reinterpret_cast<unsigned long long*>(packed + pos / 32));
-      if (prev) complete(*prev);
-      prev = &w;
-    }
-    if (prev) complete(*prev);
-  } catch (...) {
-    for (Workspace* x : {ws[0], ws[1]}) {
-      if (x->state == 1) {
-        try {
-          finish_batch(e, *x);
-        } catch (...) {
-        }
-      }
-      x->state = 0;
-      x->u_on = false;
-    }
-    throw;
-  }
+  size_t pos_of[2] = {0, 0};  // the request offset of the chunk on w0 / on the other workspace
+  run_chunks(
+      e, w0, w1, n, mb, cav,
+      [&](Workspace& w, size_t pos, uint32_t len) {
+        pos_of[&w == w0 ? 0 : 1] = pos;
+        submit_uniform(e, w, h, pairs + 2 * pos, len, now_us, reinterpret_cast<unsigned long long*>(packed + pos / 32));
+      },
+      [&](Workspace& w) { uniform_collect(w, (uint32_t)pos_of[&w == w0 ? 0 : 1], errs); });
   uniform_errors(errs, out_errs, cap, n_errs);
-  std::lock_guard<std::mutex> sl(e.stats_mu);
-  e.stats.kernel_ms = ms;
 }
 
 // Completes a submitted batch. Takes no engine lock: a writer that wants to replace the
@@ -3670,18 +3671,6 @@ void device_wait(Engine& e, Workspace* w) {
   }
   std::lock_guard<std::mutex> sl(e.stats_mu);
   e.stats.kernel_ms = w->b_ms;
-}
-
-// Synchronous batches over device buffers on one held workspace (lookups).
-static void check_range(Engine& e, Workspace& w, const gck_item* d_items, size_t n, int64_t now_us, uint8_t* d_perm,
-                        int32_t* d_err, hipStream_t st, float* ms) {
-  for (size_t pos = 0; pos < n; pos += w.max_batch) {
-    const uint32_t len = (uint32_t)std::min(n - pos, w.max_batch);
-    submit_batch(e, w, d_items + pos, len, now_us, d_perm + pos, d_err + pos, st, false);
-    finish_batch(e, w);
-    w.state = 0;
-    *ms += w.b_ms;
-  }
 }
 
 // The partitioned batch's workspace: its own, outside the pool (a partitioned batch spans many

@@ -15,7 +15,7 @@
 //              subjects and usersets of hubs (`group#member`, `team#member`, `org#is_member`);
 //              its objects are the vertices of one hierarchy (x -> y when x lists y#h');
 //   subject    the hub vertices that list user u directly, closed upwards in the hierarchy:
-//              A(u). Stored as tree covers in a 64-B user slot (closure.inc, k_user_slots): v is
+//              A(u). Stored as tree covers in a 64-B user slot (closure.inc, k_user_slots_1p): v is
 //              in A(u) iff some cover entry of u lies in v's preorder interval [pre(v), end(v));
 //   resource   per (permission p, resource R) and per operand ("term") of p: the users D the
 //              operand reaches without entering a hub, the hub vertices V where it enters one
@@ -1111,36 +1111,47 @@ __global__ void __launch_bounds__(kBlock) k_transpose_scatter_base(const uint32_
   if (x < n_sub && part_owner(x, world) == rank) nbr_t[atomicAdd(&cursor[part_local(x, world)], 1u)] = base + o;
 }
 
-// The label join over a batch (the snapshot's slot width and entry bits pick the variant); e0 / e1:
-// the kernel's own start / stop events, or null.
-// cl: the batch's caveat tables fit LDS (k_label_join<..., 32, true>).
-static void lj_launch(const DeviceSnapshot& ds, const LjArgs& j, uint32_t n, hipStream_t st, hipEvent_t e0, hipEvent_t e1,
-                      bool cl = false) {
-  if (cl) {
-    const dim3 grid((n + 32u * kWaves - 1) / (32u * kWaves)), block(kBlock);
-    if (ds.lj_bits == 24 && ds.lj_sw == 16)
-      hipExtLaunchKernelGGL((k_label_join<24, 16, 32, true>), grid, block, 0, st, e0, e1, 0, j);
-    else if (ds.lj_bits == 24)
-      hipExtLaunchKernelGGL((k_label_join<24, 32, 32, true>), grid, block, 0, st, e0, e1, 0, j);
-    else if (ds.lj_sw == 16)
-      hipExtLaunchKernelGGL((k_label_join<32, 16, 32, true>), grid, block, 0, st, e0, e1, 0, j);
-    else
-      hipExtLaunchKernelGGL((k_label_join<32, 32, 32, true>), grid, block, 0, st, e0, e1, 0, j);
-    HIP_OK(hipGetLastError());
-    return;
-  }
-  // (32 checks per wave: 16 measured slower on configs 2 and 3 — 6.0 vs 8.3 and 8.3 vs 9.9 G
-  // checks/s, profiles/r04/lj_cpw/)
-  const dim3 grid((n + 32u * kWaves - 1) / (32u * kWaves)), block(kBlock);
-  if (ds.lj_bits == 24 && ds.lj_sw == 16)
-    hipExtLaunchKernelGGL((k_label_join<24, 16, 32>), grid, block, 0, st, e0, e1, 0, j);
-  else if (ds.lj_bits == 24)
-    hipExtLaunchKernelGGL((k_label_join<24, 32, 32>), grid, block, 0, st, e0, e1, 0, j);
-  else if (ds.lj_sw == 16)
-    hipExtLaunchKernelGGL((k_label_join<32, 16, 32>), grid, block, 0, st, e0, e1, 0, j);
-  else
-    hipExtLaunchKernelGGL((k_label_join<32, 32, 32>), grid, block, 0, st, e0, e1, 0, j);
+// The label join's variants: the kernel a HIP launch takes and its demangled name in
+// libgck_kernels.co, by which the engine dispatches it into its HSA queues (aql.inc) — side by
+// side, so that the two cannot name different kernels (tests/test_aql_codeobject.py reads the
+// names from this text).
+struct LjVariant {
+  void (*kernel)(LjArgs);
+  const char* aql_name;
+};
+
+// The snapshot's entry bits and slot width pick the variant, and cl: the batch's caveat tables fit
+// LDS (k_label_join<..., 32, true>). (The rows in the order the launch ladder had them: the order the
+// kernels are instantiated in, and so laid out in the code object.)
+static const LjVariant& lj_variant(const DeviceSnapshot& ds, bool cl) {
+  static const LjVariant rows[8] = {
+      {k_label_join<24, 16, 32, true>, "void gck::k_label_join<24, 16u, 32u, true>(gck::LjArgs)"},
+      {k_label_join<24, 32, 32, true>, "void gck::k_label_join<24, 32u, 32u, true>(gck::LjArgs)"},
+      {k_label_join<32, 16, 32, true>, "void gck::k_label_join<32, 16u, 32u, true>(gck::LjArgs)"},
+      {k_label_join<32, 32, 32, true>, "void gck::k_label_join<32, 32u, 32u, true>(gck::LjArgs)"},
+      {k_label_join<24, 16, 32, false>, "void gck::k_label_join<24, 16u, 32u, false>(gck::LjArgs)"},
+      {k_label_join<24, 32, 32, false>, "void gck::k_label_join<24, 32u, 32u, false>(gck::LjArgs)"},
+      {k_label_join<32, 16, 32, false>, "void gck::k_label_join<32, 16u, 32u, false>(gck::LjArgs)"},
+      {k_label_join<32, 32, 32, false>, "void gck::k_label_join<32, 32u, 32u, false>(gck::LjArgs)"}};
+  return rows[(cl ? 0 : 4) + (ds.lj_bits == 24 ? 0 : 2) + (ds.lj_sw == 16 ? 0 : 1)];
+}
+
+// (32 checks per wave: 16 measured slower on configs 2 and 3 — 6.0 vs 8.3 and 8.3 vs 9.9 G
+// checks/s, profiles/r04/lj_cpw/)
+static uint32_t lj_blocks(uint32_t n) { return (n + 32u * kWaves - 1) / (32u * kWaves); }
+
+// The label join over a batch through HIP; e0 / e1: the kernel's own start / stop events, or null.
+static void lj_launch(const LjVariant& v, const LjArgs& j, uint32_t n, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  hipExtLaunchKernelGGL(v.kernel, dim3(lj_blocks(n)), dim3(kBlock), 0, st, e0, e1, 0, j);
   HIP_OK(hipGetLastError());
+}
+
+// The arguments that name the snapshot's join table (LjArgs::table ...).
+static void lj_table_args(const DeviceSnapshot& ds, LjArgs& j) {
+  j.table = ds.d_lj;
+  j.n_fwd = ds.n_fwd;
+  j.table_bytes = (uint32_t)((ds.lj_host.size() + 3) & ~(size_t)3);
+  j.o_meta = ds.lj_o_meta;
 }
 
 // ---- host side: hubs, hierarchy labels, user slots, flattened resource slots --------------------
@@ -2334,7 +2345,7 @@ static void build_labels(Engine& e, DeviceSnapshot& ds, const std::vector<DevNod
     if (need > free_b / 2) return;
   }
   pc.mark("sizing");
-  // user slots over the hierarchy (closure.inc k_user_slots: the covers of the vertices listing
+  // user slots over the hierarchy (closure.inc k_user_slots_1p: the covers of the vertices listing
   // each subject, inline or as a list)
   const uint32_t* uslot = nullptr;
   const uint32_t* ulist = nullptr;
@@ -2360,8 +2371,6 @@ static void build_labels(Engine& e, DeviceSnapshot& ds, const std::vector<DevNod
       uint32_t* d_doff = dalloc<uint32_t>(tmp, (size_t)nu + 1);
       uint32_t* d_dnbr = dalloc<uint32_t>(tmp, std::max<uint64_t>(n_pairs, 1));
       uint32_t* d_cnt = dalloc<uint32_t>(tmp, std::max<uint32_t>(nu, 1));
-      uint32_t* len = dalloc<uint32_t>(tmp, (size_t)nu + 1);
-      uint32_t* loff = dalloc<uint32_t>(tmp, (size_t)nu + 1);
       HIP_OK(hipStreamSynchronize(nullptr));
       if (!lab.empty()) HIP_OK(hipMemcpy(d_lab, lab.data(), lab.size() * 4, hipMemcpyHostToDevice));
       HIP_OK(hipMemcpy(d_coff, cov_off.data(), cov_off.size() * 4, hipMemcpyHostToDevice));
@@ -2381,24 +2390,9 @@ static void build_labels(Engine& e, DeviceSnapshot& ds, const std::vector<DevNod
       HIP_OK(hipGetLastError());
       uint32_t* s = lalloc((size_t)std::max<uint32_t>(nu, 1) * kUSlotWords * 4);
       uint32_t* list = nullptr;
-      if (nu) {  // (closure.inc k_user_slots_1p / k_user_lists: one pass of the covers' random reads)
-        if (bits == 24)
-          hipLaunchKernelGGL(k_user_slots_1p<24>, dim3(grid_for(nu)), dim3(kBlock), 0, 0, d_doff, d_dnbr, nu, d_lab,
-                             d_coff, d_cpre, NV, s, len);
-        else
-          hipLaunchKernelGGL(k_user_slots_1p<32>, dim3(grid_for(nu)), dim3(kBlock), 0, 0, d_doff, d_dnbr, nu, d_lab,
-                             d_coff, d_cpre, NV, s, len);
-        HIP_OK(hipGetLastError());
-        device_excl_scan(len, nu, loff);
-        uint32_t total = 0;
-        HIP_OK(hipMemcpy(&total, loff + nu, 4, hipMemcpyDeviceToHost));
-        if (total > 0 && total < (1u << 31)) list = lalloc((size_t)total * 4);
-        if (total)
-          hipLaunchKernelGGL(k_user_lists, dim3(grid_for(nu)), dim3(kBlock), 0, 0, d_doff, d_dnbr, nu, d_coff, d_cpre, len,
-                             loff, list, s);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipDeviceSynchronize());
-      }
+      // (bidir.inc build_user_slots; the sizing above has already bounded the slots, and the lists
+      // are allocated whatever is free)
+      if (nu) list = build_user_slots(bits, d_doff, d_dnbr, nu, d_lab, d_coff, d_cpre, NV, s, lalloc).list;
       uslot = s;
       ulist = list;
     } catch (...) {

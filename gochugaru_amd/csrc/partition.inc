@@ -644,11 +644,8 @@ static void part_run(Engine& e, const Xport& X, const gck_item* d_items, size_t 
     j.out_err = d_err;
     j.deferred = p.idx;
     j.n_deferred = p.cnt;
-    j.table = ds.d_lj;
-    j.n_fwd = ds.n_fwd;
-    j.table_bytes = (uint32_t)((ds.lj_host.size() + 3) & ~(size_t)3);
-    j.o_meta = ds.lj_o_meta;
-    lj_launch(ds, j, (uint32_t)n, st, prof ? w.ev0 : nullptr, prof ? w.ev1 : nullptr);
+    lj_table_args(ds, j);
+    lj_launch(lj_variant(ds, false), j, (uint32_t)n, st, prof ? w.ev0 : nullptr, prof ? w.ev1 : nullptr);
     HIP_OK(hipMemcpyAsync(p.h_cnt, p.cnt, 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     if (prof) HIP_OK(hipEventElapsedTime(&join_ms, w.ev0, w.ev1));

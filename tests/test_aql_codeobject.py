@@ -74,6 +74,29 @@ def test_dispatched_kernels_present_with_their_kernarg_layout():
         assert seg == hid + 256 and seg <= 1024, (dm, seg)  # the whole hidden block; aql.inc kAqlKernargBytes
 
 
+def test_variant_tables_name_the_kernels_checked_here():
+    """The engine dispatches by the names in its two variant tables (labels.inc lj_variant,
+    engine.hip cj_variant): exactly the kernels whose layout the test above checks. KERNELS stays
+    written out here, the independent witness; this reads the tables' source text."""
+    csrc = os.path.join(ROOT, "gochugaru_amd", "csrc")
+    names = set()
+    for fn, func in (("labels.inc", "lj_variant"), ("engine.hip", "cj_variant")):
+        with open(os.path.join(csrc, fn)) as f:
+            src = f.read()
+        body = re.search(r"static const \w+& %s\([^)]*\) \{\n\s*static const \w+ rows\[\d+\] = \{(.*?)\};" % func,
+                         src, re.S)
+        assert body, f"{fn}: the variant table of {func} was not found"
+        rows = re.findall(r'"(void gck::[^"]+)"', body.group(1))
+        assert rows and len(rows) == len(set(rows)), (fn, rows)
+        names.update(rows)
+    assert names == set(KERNELS), (sorted(names - set(KERNELS)), sorted(set(KERNELS) - names))
+    # and no other place in the sources spells a dispatched join's name
+    for fn in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, fn)) as f:
+            n = len(re.findall(r'"void gck::k_(?:label|closure)_join<', f.read()))
+        assert n == {"labels.inc": 8, "engine.hip": 1}.get(fn, 0), (fn, n)
+
+
 def test_code_object_carries_the_build_id():
     """aql.inc kBuildId: the code object exports the variable aql_init compares with the library's."""
     if not os.path.exists(CO) or not os.path.exists(READELF):

@@ -60,6 +60,34 @@ def test_context_slot_beyond_contexts_fails_the_request(family, zero_copy):
     e.close()
 
 
+@pytest.mark.parametrize("kw", [{}, {"workspaces": 1}, {"profile": True}],
+                         ids=["two-workspaces", "one-workspace", "dma"])
+def test_context_slot_beyond_contexts_fails_a_request_of_several_chunks(kw):
+    """A request above max_batch runs in chunks over two workspaces (one when the pool holds one):
+    a bad context_slot in any chunk fails the call with the item's index in the request before a
+    chunk runs, and the engine then answers the good request, one batch per chunk."""
+    max_batch = 64
+    e, items, want = _setup("nested", max_batch=max_batch, **kw)
+    reps = -(-(3 * max_batch + 1) // len(items))  # (at least 4 chunks, the last one partial if it may be)
+    items, want = np.tile(items, reps), want * reps
+    n_chunks = -(-len(items) // max_batch)
+    assert n_chunks >= 4
+    before = e.stats()["batches"]
+    for bad_at in (37, 2 * max_batch + 5):  # in chunk 0, in chunk 2
+        for n_ctx, slot in ((0, 1), (1, 2)):
+            bad = items.copy()
+            bad[bad_at]["context_slot"] = slot
+            bad[-1]["context_slot"] = slot + 5  # (a later offender: the first one is reported)
+            with pytest.raises(E.GckError) as ei:
+                e.check_bulk(bad, now_us=gen.NOW_US, contexts=['{"x": 1}'] * n_ctx or None)
+            assert ei.value.code == E.GCK_E_INVALID_ARGUMENT
+            assert f"item {bad_at}: context_slot {slot} beyond the {n_ctx} contexts" in str(ei.value), str(ei.value)
+    perm, err = e.check_bulk(items, now_us=gen.NOW_US)
+    assert [(int(p), int(x)) for p, x in zip(perm, err)] == want
+    assert e.stats()["batches"] - before == n_chunks  # (no chunk of a failed request ran)
+    e.close()
+
+
 @pytest.mark.parametrize("family", sorted(FAMILIES))
 def test_pipelined_host_batches_match_the_oracle(family):
     """8 host batches in flight over pinned buffers through the compiled loop (what bench.py times

@@ -123,13 +123,17 @@ def test_uniform_on_every_engine_path():
 
 def test_uniform_chunks_above_max_batch():
     """A request above max_batch runs in chunks of max_batch (rounded to 32 checks) over two
-    workspaces; the words and the error indices are the request's."""
+    workspaces (one after the other when the pool holds one); the words and the error indices are
+    the request's."""
     schema, tuples, _ = gen.nested(5, n_users=400, n_groups=160, n_docs=200)
     rng = np.random.default_rng(3)
     checks = [f"doc:d{rng.integers(0, 205)}#view@user:u{rng.integers(0, 405)}" for _ in range(5000)]
     e = _engine(schema, tuples, max_batch=1000)
     assert _run_family(e, schema, tuples, checks, 50, pinned=True) == 1
     assert _run_family(e, schema, tuples, checks, 50, pinned=False) == 1
+    e.close()
+    e = _engine(schema, tuples, max_batch=1000, workspaces=1)
+    assert _run_family(e, schema, tuples, checks, 50, pinned=True) == 1
     e.close()
 
 
