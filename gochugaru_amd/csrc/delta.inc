@@ -892,7 +892,7 @@ void device_apply_build(Engine& e, const std::vector<UpdateGroup>& groups, Watch
   unsigned char* host = staging_reserve(e, o_tot + jobs.size() * 8);
   std::vector<void*>& fresh = wb.fresh;
   int64_t& tuple_delta = wb.tuple_delta;
-  std::vector<DeltaHint::Fwd> fwd;  // (the merged classes, for the label tables: labels.inc)
+  std::vector<DeltaHint::Fwd> fwd;  // (the merged classes, for the label tables: labels_build.inc)
   try {
     // ---- merged arrays at their upper bound, the job table, the upload -------------------------
     uint32_t lb = 0, mb = 0;

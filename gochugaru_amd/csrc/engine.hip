@@ -97,6 +97,39 @@ struct SlotPatch {
   uint32_t n;
 };
 
+// The label join's tables (labels_build.inc build_labels): built as one value and committed to the
+// snapshot whole, or taken over whole from the previous snapshot (`lj = old.lj`).
+struct LjTables {
+  std::vector<unsigned char> host;  // root table + LjMeta[] (uploaded in the program block); empty: no label join
+  uint32_t o_meta = 0, sw = 0, bits = 24;  // offset of LjMeta[] in `host`, slot words, user-slot entry width
+  bool preferred = false;  // the labels cover every closure-join root and more: they take stage A
+  bool cav = false;        // some label root holds caveated pairs (labels.inc kLjCav)
+  std::vector<uint64_t> key;   // what the tables were built from (reused while unchanged)
+  std::vector<uint64_t> dkey;  // ... of it, the CSRs that feed only the resource slots' user lists
+  std::vector<const uint32_t*> hgt;  // the roots' heights arrays the tables were built against
+  std::vector<void*> ptrs;     // their arrays (in allocs or hallocs; labels_build.inc lj_alloc)
+  uint64_t bytes = 0;          // ... and their size
+  // subjects a Watch batch changed a direct grant of since the tables were built (bit per subject;
+  // null: none): their checks go to the wave bundles (labels_build.inc lj_dirty_path)
+  uint32_t* dirty = nullptr;
+  uint64_t dirty_n = 0;        // changed grants marked (an upper bound of the dirty subjects)
+  uint32_t users = 0;
+  // the arrow forest of the label roots' resources (labels_build.inc lj_forest: every object the
+  // flattening of a resource visits is an ancestor of it): per vertex (pre, end), per type its
+  // first vertex (kNone: not in the forest); null: no forest, a dirty subject's checks all defer
+  uint32_t* af = nullptr;
+  // the forest's parent edges (labels.inc lj_chain_walk): tupleset CSR << 32 | the parent's forest
+  // index (kNone: a root), per forest vertex; null: no chain programs
+  unsigned long long* afp = nullptr;
+  uint32_t afp_n = 0;
+  uint32_t* anc = nullptr;  // per forest vertex its ancestors, kAncWords each (labels.inc lj_chain_wave)
+  std::vector<uint32_t> af_base, af_rows;
+  std::vector<std::pair<uint32_t, uint16_t>> dtype;  // direct-grant CSR -> the type of its rows
+  // per dirty subject the forest intervals of the objects whose grants of it changed (kDovWords
+  // each, labels.inc): its checks defer only when one holds the resource (shared like `dirty`)
+  uint32_t* dov = nullptr;
+};
+
 struct DeviceSnapshot {
   std::vector<void*> allocs;
   std::vector<void*> hallocs;  // hipExtMallocWithFlags (physically contiguous) arrays: hipFree
@@ -124,40 +157,12 @@ struct DeviceSnapshot {
   std::vector<unsigned char> cj_host;
   uint32_t cj_n_desc = 0, cj_o_meta = 0, cj_o_entries = 0;
   const unsigned char* d_cj = nullptr;
-  // label-join stage (labels.inc): root table + LjMeta[] (in the program block), slot words
-  std::vector<unsigned char> lj_host;
-  uint32_t lj_o_meta = 0, lj_sw = 0, lj_bits = 24;
-  bool lj_preferred = false;  // the labels cover every closure-join root and more: they take stage A
-  bool lj_cav = false;        // some label root holds caveated pairs (labels.inc kLjCav)
+  LjTables lj;                // label-join stage (labels.inc); d_lj: `lj.host` in the program block
   uint32_t n_cav = 0;         // caveat instances in cav_static / cav_row
-  std::vector<uint64_t> lj_key;  // what the label tables were built from (labels.inc: reused while unchanged)
-  std::vector<uint64_t> lj_dkey; // ... of it, the CSRs that feed only the resource slots' user lists
-  std::vector<const uint32_t*> lj_hgt;  // the roots' heights arrays the tables were built against
-  std::vector<void*> lj_ptrs;    // their arrays (in allocs or hallocs)
-  // subjects a Watch batch changed a direct grant of since the tables were built (bit per subject;
-  // null: none): their checks go to the wave bundles (labels.inc, lj_dirty_path)
-  uint32_t* lj_dirty = nullptr;
-  uint64_t lj_dirty_n = 0;       // changed grants marked (an upper bound of the dirty subjects)
-  uint32_t lj_users = 0;
-  // the arrow forest of the label roots' resources (labels.inc lj_forest: every object the
-  // flattening of a resource visits is an ancestor of it): per vertex (pre, end), per type its
-  // first vertex (kNone: not in the forest); null: no forest, a dirty subject's checks all defer
-  uint32_t* lj_af = nullptr;
-  // the forest's parent edges (labels.inc lj_chain_walk): tupleset CSR << 32 | the parent's forest
-  // index (kNone: a root), per forest vertex; null: no chain programs
-  unsigned long long* lj_afp = nullptr;
-  uint32_t lj_afp_n = 0;
-  uint32_t* lj_anc = nullptr;  // per forest vertex its ancestors, kAncWords each (labels.inc lj_chain_wave)
-  std::vector<uint32_t> lj_af_base, lj_af_rows;
-  std::vector<std::pair<uint32_t, uint16_t>> lj_dtype;  // direct-grant CSR -> the type of its rows
-  // per dirty subject the forest intervals of the objects whose grants of it changed (kDovWords
-  // each, labels.inc): its checks defer only when one holds the resource (shared like lj_dirty)
-  uint32_t* lj_dov = nullptr;
   std::vector<void*> adopt_h;    // arrays of the current snapshot this one takes over at publish
                                  // (device_publish: contiguous ones move to hallocs, others to allocs)
   std::vector<SlotRec> slot_recs;
   std::vector<SlotPatch> slot_patches;  // applied by device_publish
-  uint64_t lj_bytes = 0;
   const unsigned char* d_lj = nullptr;
   uint32_t node_bits = 1, q_bits = 1, q_bits_deep = 1;  // query-id bits of the visited keys (make_key)
   uint64_t bytes = 0;
@@ -1701,6 +1706,7 @@ static void scan_wild(const Engine& e, DevCSR& d, uint64_t ne) {
 #include "closure.inc"
 #include "bidir.inc"
 #include "labels.inc"
+#include "labels_build.inc"
 #include "aql.inc"
 #include "resident.inc"
 
@@ -1874,7 +1880,7 @@ static DeviceSnapshot* device_build(Engine& e, std::vector<HostCSR>& csrs, bool 
     const size_t o_cst = put(cst.data(), cst.size());
     const size_t o_crow = put(crow.data(), crow.size() * 4);
     const size_t o_cj = ds->cj_host.empty() ? 0 : put(ds->cj_host.data(), ds->cj_host.size());
-    const size_t o_lj = ds->lj_host.empty() ? 0 : put(ds->lj_host.data(), ds->lj_host.size());
+    const size_t o_lj = ds->lj.host.empty() ? 0 : put(ds->lj.host.data(), ds->lj.host.size());
     std::vector<unsigned long long> hp(ds->hgt.size());  // heights array of each forward node
     for (size_t n = 0; n < hp.size(); ++n) hp[n] = (unsigned long long)(uintptr_t)ds->hgt[n];
     const size_t o_hgt = put(hp.data(), hp.size() * 8);
@@ -1903,7 +1909,7 @@ static DeviceSnapshot* device_build(Engine& e, std::vector<HostCSR>& csrs, bool 
     ds->cav_row = reinterpret_cast<uint32_t*>(d_blob + o_crow);
     ds->d_hgt = reinterpret_cast<const unsigned long long*>(d_blob + o_hgt);
     ds->d_cj = ds->cj_host.empty() ? nullptr : d_blob + o_cj;
-    ds->d_lj = ds->lj_host.empty() ? nullptr : d_blob + o_lj;
+    ds->d_lj = ds->lj.host.empty() ? nullptr : d_blob + o_lj;
     ds->node_bits = std::max<uint32_t>(1, ceil_log2(sc.nodes.size()));
     if (ds->node_bits > 12) throw Error(GCK_E_SCHEMA, "schema too large for the visited-key layout");
     ds->q_bits = 31 - ds->node_bits;
@@ -2512,7 +2518,7 @@ static void validate_slots(const gck_item* items, uint32_t n, uint32_t limit) {
 // Stage A of a batch begins with the label join (labels.inc) rather than the closure join.
 static bool label_join_on(const Engine& e) {
   const DeviceSnapshot& ds = *e.dev;
-  return ds.d_lj && (!(ds.d_cj && !(e.cfg.flags & GCK_FLAG_NO_CLOSURE)) || ds.lj_preferred);
+  return ds.d_lj && (!(ds.d_cj && !(e.cfg.flags & GCK_FLAG_NO_CLOSURE)) || ds.lj.preferred);
 }
 
 // The snapshot has a one-round join (label or closure) for stage A to begin with.
@@ -2652,7 +2658,7 @@ static Route stage_a_route(Engine& e, Workspace& w) {
   // (a batch with check contexts: the label join with the caveat plane, whose Ctx travels in the
   // kernarg block and which clears the checks' caveat flags itself — nothing on the HIP stream)
   r.aql_ok = w.b_own_stream && !r.host_out && !r.chained && r.ctr_clean && e.aql && w.aql_kernarg &&
-             (!w.cav_on || (r.lj && ds.lj_cav)) && (r.lj || r.cj) && ((aql_timed && e.aql->tick_hz) || !r.timed) &&
+             (!w.cav_on || (r.lj && ds.lj.cav)) && (r.lj || r.cj) && ((aql_timed && e.aql->tick_hz) || !r.timed) &&
              aql_build_done(e);
   // (GCK_DEBUG_HIP_SELFPUB: an engine-stream batch launched through HIP publishes itself from its
   // last block as an AQL-dispatched one does — the dispatch-span attribution of tools/aql_span.sh;
@@ -2701,16 +2707,16 @@ static void label_join_start(Engine& e, Workspace& w, const Route& r, const Ctx&
   LjArgs j{};
   join_args(r, w, a, j);
   lj_table_args(ds, j);
-  j.dirty = ds.lj_dirty;
-  j.dov = ds.lj_dov;
+  j.dirty = ds.lj.dirty;
+  j.dov = ds.lj.dov;
   j.csrs = ds.csrs;
-  j.afp = ds.lj_afp;
+  j.afp = ds.lj.afp;
   j.n_csrs = ds.n_csrs;
-  j.afp_n = ds.lj_afp_n;
+  j.afp_n = ds.lj.afp_n;
   j.cav_static = ds.cav_static;
-  j.anc = ds.lj_anc;
+  j.anc = ds.lj.anc;
   bool cl = false;
-  const bool cav = ds.lj_cav && w.cav_on;  // caveated pairs decided under the check contexts (cav_state)
+  const bool cav = ds.lj.cav && w.cav_on;  // caveated pairs decided under the check contexts (cav_state)
   if (cav) {
     // the dense outcome table and the instances in LDS when they fit (labels.inc LjCavLds)
     const uint32_t rows = w.cav.n_dist ? (uint32_t)(w.cav.dense.size() / w.cav.n_dist) : 0u;
@@ -2828,7 +2834,7 @@ static void bundles_launch(Engine& e, Workspace& w) {
   w.ctr_clean = false;
   // the checks' caveat flags start cleared: by the label join with the caveat plane itself (an AQL
   // dispatch is not ordered after this stream's work), else here
-  if (w.cav_on && !(r.lj && e.dev->lj_cav)) HIP_OK(hipMemsetAsync(w.cav_flag, 0, n, st));
+  if (w.cav_on && !(r.lj && e.dev->lj.cav)) HIP_OK(hipMemsetAsync(w.cav_flag, 0, n, st));
   w.b_timed = r.timed;
   w.b_label = r.lj;
   w.b_closure = r.lj || r.cj;

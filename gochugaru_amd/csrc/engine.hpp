@@ -207,7 +207,7 @@ struct Engine {
   int device = 0;
   uint32_t part_rank = 0, part_world = 1;  // partitioned graph (gck_set_partition)
   bool part_set = false;                   // gck_set_partition was called (any world, one rank too)
-  // the schema's hub nodes and the relations of their hierarchy (labels.inc partition_rules): what
+  // the schema's hub nodes and the relations of their hierarchy (labels_build.inc partition_rules): what
   // a rank keeps beyond the rows it owns (part_keep)
   std::vector<char> part_hub_node, part_hub_rel;
   std::vector<uint8_t> part_sub_node;  // the hubs' nodes (partition.inc part_dest)
@@ -310,7 +310,7 @@ inline bool part_keep(const Engine& e, uint16_t rel, uint32_t obj, uint32_t sid,
   // level loop expands hub nodes there: partition.inc part_dest)
   return srel != kEllipsis || sid == kWildcard || part_owner(sid, e.part_world) == e.part_rank;
 }
-void partition_rules(Engine& e);  // labels.inc: e.part_hub_node / part_hub_rel from the schema
+void partition_rules(Engine& e);  // labels_build.inc: e.part_hub_node / part_hub_rel from the schema
 
 // snapshot.cpp
 void add_tuples_text(Engine& e, const char* text, size_t len);

@@ -47,13 +47,13 @@ constexpr uint32_t kLjDeep = 0x80000000u;         // lab[2v + 1] of a hub root's
 // user kLjCavWild. Plain users are < 2^31 (interned ids), so a pair never equals a plain entry.
 constexpr uint32_t kLjCav = 0x80000000u;
 constexpr uint32_t kLjCavWild = 0x7FFFFFFFu;
-// Per dirty subject (DeviceSnapshot::lj_dov), two lines: word 0 the appends made (low 31 bits) |
+// Per dirty subject (LjTables::dov), two lines: word 0 the appends made (low 31 bits) |
 // kDovOver once one did not fit, word 1 unused, then kDovPairs (lo, hi) arrow-forest intervals of
 // the objects whose direct grants of the subject changed since the tables were built — pairs 0-6
 // in the first line, 7-14 in the second.
 constexpr uint32_t kDovWords = 32, kDovPairs = 15, kDovOver = 0x80000000u;
 
-// The chain program of a root (build_labels lj_chain_of): per term, the direct-user CSR classes its
+// The chain program of a root (labels_build.inc lj_chain_of): per term, the direct-user CSR classes its
 // flattening reads at each depth of the resource's arrow-forest chain (R, R's parent, ...), so that a
 // dirty subject's check whose overlay hits (a changed grant on the chain) is decided in the join
 // from the current revision's rows instead of going to the bundles. A level is one set of schema
@@ -62,7 +62,7 @@ constexpr uint32_t kDovWords = 32, kDovPairs = 15, kDovOver = 0x80000000u;
 constexpr uint32_t kLjChainCls = 8, kLjChainLvls = 8, kLjChainDepth = 64;
 constexpr uint8_t kLjChainEnd = 0xFF;
 struct LjChainLvl {
-  uint32_t af_base;             // forest index of object 0 of the level's type (DeviceSnapshot::lj_af_base)
+  uint32_t af_base;             // forest index of object 0 of the level's type (LjTables::af_base)
   uint16_t csr[kLjChainCls];    // direct-user classes (plain or caveated) read on the level's object
   uint16_t arrow;               // the tupleset CSR whose row leads to the next depth (0xFFFF: none)
   uint8_t n, next;              // classes; the next depth's level (kLjChainEnd: the term's walk ends)
@@ -83,7 +83,7 @@ struct LjMeta {  // one label root (a permission) and its subject type
   uint8_t n_terms, neg;  // neg bit t: term t is subtracted (exclusion operand)
   uint8_t cav;           // the terms may hold caveated pairs (kLjCav)
   uint8_t pack;          // inline slots hold 24-bit fields (LjEnt24), not 32-bit words
-  // the resources' (pre, end) in the arrow forest (DeviceSnapshot::lj_af; null: none): a dirty
+  // the resources' (pre, end) in the arrow forest (LjTables::af; null: none): a dirty
   // subject's check stays with the slots unless a changed object's interval holds pre(R)
   const uint32_t* apre;
   // the chain program (null: a dirty subject's overlay hit defers the check)
@@ -110,7 +110,7 @@ struct LjArgs {
   // evaluation's request set, cav_flag), or null: a caveated pair is then CONDITIONAL
   const Ctx* cx;
   // subjects whose direct grants changed since the tables were built (a bit each; null: none):
-  // their checks go to the bundles (labels.inc lj_dirty_path)
+  // their checks go to the bundles (labels_build.inc lj_dirty_path)
   const uint32_t* dirty;
   // the caveat instances and the dense outcome table's rows (k_label_join<..., CL>: staged in LDS)
   uint32_t cav_n, cav_rows;
@@ -126,12 +126,12 @@ struct LjArgs {
   gck_item* items_out;
   uint32_t u_rp, u_ss, u_ctx;
   // the chain walk of a dirty subject's overlay hit (LjMeta::chain): the current revision's CSRs
-  // and the forest's parent edges (DeviceSnapshot::lj_afp: tupleset CSR << 32 | parent's index)
+  // and the forest's parent edges (LjTables::afp: tupleset CSR << 32 | parent's index)
   const DevCSR* csrs;
   const unsigned long long* afp;
   uint32_t n_csrs, afp_n;  // (the walk's bounds: every index it reads is checked against them)
   const uint8_t* cav_static;  // per caveat instance its outcome under its stored context (the walk)
-  const uint32_t* anc;        // per forest vertex its ancestors (kAncWords, DeviceSnapshot::lj_anc; null: none)
+  const uint32_t* anc;        // per forest vertex its ancestors (kAncWords, LjTables::anc; null: none)
 };
 // per wave: {start, items and table staged, slot lines staged, decided, end, list checks, ext checks,
 // deferred: no label root / a slot overflow / a dirty subject without the overlay / an overlay hit}
@@ -402,7 +402,7 @@ __device__ __forceinline__ uint32_t lj_chain_walk(const LjChain* ch, uint32_t n_
   return w;
 }
 
-// Per forest vertex one 64-B line (DeviceSnapshot::lj_anc): word 0 the number of its ancestors
+// Per forest vertex one 64-B line (LjTables::anc): word 0 the number of its ancestors
 // (kAncOver: more than kAncWords - 1, the line holds the first ones), words 1.. its parent, the
 // parent's parent, ... as forest indices — the whole chain of a resource in one round.
 constexpr uint32_t kAncWords = 16, kAncOver = 0x80000000u;
@@ -1133,7 +1133,7 @@ static const LjVariant& lj_variant(const DeviceSnapshot& ds, bool cl) {
       {k_label_join<24, 32, 32, false>, "void gck::k_label_join<24, 32u, 32u, false>(gck::LjArgs)"},
       {k_label_join<32, 16, 32, false>, "void gck::k_label_join<32, 16u, 32u, false>(gck::LjArgs)"},
       {k_label_join<32, 32, 32, false>, "void gck::k_label_join<32, 32u, 32u, false>(gck::LjArgs)"}};
-  return rows[(cl ? 0 : 4) + (ds.lj_bits == 24 ? 0 : 2) + (ds.lj_sw == 16 ? 0 : 1)];
+  return rows[(cl ? 0 : 4) + (ds.lj.bits == 24 ? 0 : 2) + (ds.lj.sw == 16 ? 0 : 1)];
 }
 
 // (32 checks per wave: 16 measured slower on configs 2 and 3 — 6.0 vs 8.3 and 8.3 vs 9.9 G
@@ -1150,313 +1150,8 @@ static void lj_launch(const LjVariant& v, const LjArgs& j, uint32_t n, hipStream
 static void lj_table_args(const DeviceSnapshot& ds, LjArgs& j) {
   j.table = ds.d_lj;
   j.n_fwd = ds.n_fwd;
-  j.table_bytes = (uint32_t)((ds.lj_host.size() + 3) & ~(size_t)3);
-  j.o_meta = ds.lj_o_meta;
-}
-
-// ---- host side: hubs, hierarchy labels, user slots, flattened resource slots --------------------
-
-// Tree labels and covers of a DAG given as parents per vertex (the same construction as
-// bidir.inc build_ancestors, over any vertex set): lab[2v] = pre(v) | overflow << 31,
-// lab[2v + 1] = end(v), cov_off / cov_pre the covers' preorder numbers. False on a cycle.
-static bool hier_labels(uint32_t n, const std::vector<uint32_t>& poff, const std::vector<uint32_t>& pnbr,
-                        const std::vector<uint32_t>& coff_all, const std::vector<uint32_t>& cnbr_all,
-                        std::vector<uint32_t>& lab, std::vector<uint32_t>& cov_off, std::vector<uint32_t>& cov_pre) {
-  TopoLevels T;
-  if (!topo_levels(n, poff, coff_all.data(), cnbr_all.data(), T)) return false;
-  tree_labels(n, poff, pnbr, T, kLjCoverMax, host_threads(), lab, cov_off, cov_pre);
-  return true;
-}
-
-// Strongly connected components of the hierarchy (iterative Tarjan over the child lists):
-// comp[v] in [0, n_comp). Vertices of one component reach each other, so they share their upward
-// closure; the labels are built over the condensed DAG. (Checks whose resource reaches a cycle sit
-// at the depth budget and are deferred by the height guard; everything else stays exact.)
-// `trivial`: vertices known to lie on no cycle (Kahn's order reached them: their parents all
-// came first), each its own component without a visit — a remaining vertex's children are
-// remaining too (an edge into a Kahn-ordered vertex would have held it back), so Tarjan runs over
-// the remaining ones alone: the cycles and what lies below them.
-static uint32_t hier_scc(uint32_t n, const std::vector<uint32_t>& coff, const std::vector<uint32_t>& cnbr,
-                         const std::vector<char>& trivial, std::vector<uint32_t>& comp) {
-  constexpr uint32_t kUnset = 0xFFFFFFFFu;
-  std::vector<uint32_t> index(n, kUnset), low(n, 0), stack, it_pos(n, 0), call;
-  std::vector<char> on(n, 0);
-  comp.assign(n, kUnset);
-  uint32_t next_index = 0, n_comp = 0;
-  for (uint32_t s = 0; s < n; ++s)
-    if (trivial[s]) index[s] = next_index++, comp[s] = n_comp++;
-  for (uint32_t s = 0; s < n; ++s) {
-    if (index[s] != kUnset) continue;
-    call.push_back(s);
-    index[s] = low[s] = next_index++;
-    stack.push_back(s);
-    on[s] = 1;
-    it_pos[s] = coff[s];
-    while (!call.empty()) {
-      const uint32_t v = call.back();
-      if (it_pos[v] < coff[v + 1]) {
-        const uint32_t w = cnbr[it_pos[v]++];
-        if (index[w] == kUnset) {
-          index[w] = low[w] = next_index++;
-          stack.push_back(w);
-          on[w] = 1;
-          it_pos[w] = coff[w];
-          call.push_back(w);
-        } else if (on[w]) {
-          low[v] = std::min(low[v], index[w]);
-        }
-        continue;
-      }
-      call.pop_back();
-      if (!call.empty()) low[call.back()] = std::min(low[call.back()], low[v]);
-      if (low[v] == index[v]) {
-        for (;;) {
-          const uint32_t w = stack.back();
-          stack.pop_back();
-          on[w] = 0;
-          comp[w] = n_comp;
-          if (w == v) break;
-        }
-        ++n_comp;
-      }
-    }
-  }
-  return n_comp;
-}
-
-// Tree labels and covers of any hierarchy (cycles condensed): per vertex lab[2v] / lab[2v + 1]
-// and its cover (cov_off / cov_pre), those of its component.
-static void hier_labels_any(uint32_t n, const std::vector<uint32_t>& poff, const std::vector<uint32_t>& pnbr,
-                            const std::vector<uint32_t>& coff, const std::vector<uint32_t>& cnbr, std::vector<uint32_t>& lab,
-                            std::vector<uint32_t>& cov_off, std::vector<uint32_t>& cov_pre, uint32_t& n_cyclic) {
-  n_cyclic = 0;
-  PhaseClock pc("hier");
-  if (hier_labels(n, poff, pnbr, coff, cnbr, lab, cov_off, cov_pre)) return;
-  pc.mark("acyclic_try");
-  std::vector<char> trivial(n, 0);
-  {  // Kahn's order over the whole hierarchy: what it reaches lies on no cycle
-    std::vector<uint32_t> indeg(n), q;
-    q.reserve(n);
-    for (uint32_t v = 0; v < n; ++v)
-      if (!(indeg[v] = poff[v + 1] - poff[v])) q.push_back(v);
-    for (size_t qi = 0; qi < q.size(); ++qi) {
-      trivial[q[qi]] = 1;
-      for (uint32_t k = coff[q[qi]]; k < coff[q[qi] + 1]; ++k)
-        if (--indeg[cnbr[k]] == 0) q.push_back(cnbr[k]);
-    }
-  }
-  std::vector<uint32_t> comp;
-  const uint32_t nc = hier_scc(n, coff, cnbr, trivial, comp);
-  pc.mark("scc");
-  std::vector<uint32_t> csize(nc, 0);
-  for (uint32_t v = 0; v < n; ++v) ++csize[comp[v]];
-  for (uint32_t v = 0; v < n; ++v) n_cyclic += csize[comp[v]] > 1 ? 1u : 0u;
-  // the condensed DAG (parent comp -> child comp, deduplicated): the edges bucketed by parent
-  // component (a counting sort), each bucket sorted and deduplicated in parallel, then the
-  // parents lists from the children lists
-  std::vector<uint32_t> bo((size_t)nc + 1, 0), bk;
-  for (uint32_t v = 0; v < n; ++v)
-    for (uint32_t k = coff[v]; k < coff[v + 1]; ++k)
-      if (comp[v] != comp[cnbr[k]]) ++bo[comp[v] + 1];
-  for (uint32_t c = 0; c < nc; ++c) bo[c + 1] += bo[c];
-  bk.resize(bo[nc]);
-  {
-    std::vector<uint32_t> at(bo.begin(), bo.end() - 1);
-    for (uint32_t v = 0; v < n; ++v)
-      for (uint32_t k = coff[v]; k < coff[v + 1]; ++k)
-        if (comp[v] != comp[cnbr[k]]) bk[at[comp[v]]++] = comp[cnbr[k]];
-  }
-  std::vector<uint32_t> blen(nc, 0);
-  parallel_chunks(nc, host_threads(), [&](unsigned, size_t lo, size_t hi) {
-    for (size_t c = lo; c < hi; ++c) {
-      std::sort(bk.begin() + bo[c], bk.begin() + bo[c + 1]);
-      blen[c] = (uint32_t)(std::unique(bk.begin() + bo[c], bk.begin() + bo[c + 1]) - (bk.begin() + bo[c]));
-    }
-  });
-  std::vector<uint32_t> qcoff((size_t)nc + 1, 0);
-  for (uint32_t c = 0; c < nc; ++c) qcoff[c + 1] = qcoff[c] + blen[c];
-  std::vector<uint32_t> qcnbr(qcoff[nc]), qpoff((size_t)nc + 1, 0), qpnbr(qcoff[nc]);
-  for (uint32_t c = 0; c < nc; ++c) {
-    std::copy(bk.begin() + bo[c], bk.begin() + bo[c] + blen[c], qcnbr.begin() + qcoff[c]);
-    for (uint32_t k = 0; k < blen[c]; ++k) ++qpoff[bk[bo[c] + k] + 1];
-  }
-  for (uint32_t c = 0; c < nc; ++c) qpoff[c + 1] += qpoff[c];
-  {
-    std::vector<uint32_t> pa(qpoff.begin(), qpoff.end() - 1);
-    for (uint32_t c = 0; c < nc; ++c)  // (parents in ascending order, as the sorted edge list gave them)
-      for (uint32_t k = qcoff[c]; k < qcoff[c + 1]; ++k) qpnbr[pa[qcnbr[k]]++] = c;
-  }
-  pc.mark("condense");
-  std::vector<uint32_t> clab, ccoff, ccpre;
-  if (!hier_labels(nc, qpoff, qpnbr, qcoff, qcnbr, clab, ccoff, ccpre))
-    throw Error(GCK_E_DEVICE, "engine invariant violated: condensed hierarchy is cyclic");
-  lab.assign(2 * (size_t)n, 0);
-  cov_off.assign((size_t)n + 1, 0);
-  const unsigned nt = host_threads();
-  parallel_chunks(n, nt, [&](unsigned, size_t lo, size_t hi) {
-    for (size_t v = lo; v < hi; ++v) {
-      const uint32_t c = comp[v];
-      lab[2 * v] = clab[2 * (size_t)c];
-      lab[2 * v + 1] = clab[2 * (size_t)c + 1];
-      cov_off[v + 1] = ccoff[c + 1] - ccoff[c];
-    }
-  });
-  for (uint32_t v = 0; v < n; ++v) cov_off[v + 1] += cov_off[v];
-  cov_pre.resize(cov_off[n]);
-  parallel_chunks(n, nt, [&](unsigned, size_t lo, size_t hi) {
-    for (size_t v = lo; v < hi; ++v)
-      std::copy(ccpre.begin() + ccoff[comp[v]], ccpre.begin() + ccoff[comp[v] + 1], cov_pre.begin() + cov_off[v]);
-  });
-  pc.mark("labels_expand");
-}
-
-namespace {
-
-struct HostRows {  // a host copy of one CSR of the snapshot
-  std::vector<uint32_t> off, nbr;
-  std::vector<uint32_t> cav;  // ext CSRs: caveat instance and expiry per edge
-  std::vector<int64_t> exp;
-  uint32_t n_rows = 0;
-};
-
-// One flattened term of one resource: users reached without entering a hub, hub vertices entered,
-// a wildcard.
-struct Flat {
-  std::vector<uint32_t> D, V;
-  std::vector<uint32_t> C;  // (user | kLjCav, instance) pairs: reached only through a partial caveat
-  bool wild = false, over = false;
-};
-
-struct LabelPlan {
-  uint32_t p;                    // the root (a permission node, or a hub: no terms)
-  std::vector<uint32_t> terms;   // operand nodes
-  uint8_t neg = 0;
-  bool cav = false;              // a term reads caveated relationships (the caveat plane)
-  uint32_t sw_need = 16;         // slot words the sample asked for
-};
-
-}  // namespace
-
-// Hubs of a node program (over its forward nodes [0, nf)): targets of usersets and arrows that are
-// unions of stored subjects and computed usersets, whose usersets point at hubs again, with no
-// caveated / expiring edge (`ext(item index)`). loc[h]: the nodes of hub h on its own object.
-template <class Ext>
-static void find_hubs(const std::vector<DevNode>& nodes, const std::vector<DevItem>& items, uint32_t nf, Ext&& ext,
-                      std::vector<char>& hub, std::vector<std::vector<uint32_t>>& loc) {
-  std::vector<char> target(nf, 0);
-  hub.assign(nf, 0);
-  loc.assign(nf, {});
-  for (uint32_t n = 0; n < nf; ++n)
-    for (uint32_t k = 0; k < nodes[n].count; ++k) {
-      const DevItem& it = items[nodes[n].first + k];
-      if ((it.kind == IT_KIND && it.srel != kEllipsis) || it.kind == IT_ARROW)
-        if (it.target != kNoNode && it.target < nf) target[it.target] = 1;
-    }
-  for (uint32_t h = 0; h < nf; ++h) {
-    if (!target[h]) continue;
-    std::vector<uint32_t> stack{h}, out;
-    std::vector<char> seen(nf, 0);
-    seen[h] = 1;
-    bool ok = true;
-    while (!stack.empty() && ok) {
-      const uint32_t n = stack.back();
-      stack.pop_back();
-      out.push_back(n);
-      const DevNode& nd = nodes[n];
-      if (nd.kind != NK_RELATION && nd.kind != NK_UNION && nd.kind != NK_NIL) ok = false;
-      for (uint32_t k = 0; k < nd.count && ok; ++k) {
-        const DevItem& it = items[nd.first + k];
-        if (nd.kind == NK_UNION) {
-          if (it.kind != IT_COMPUTED || it.target >= nf) ok = false;
-          else if (!seen[it.target]) seen[it.target] = 1, stack.push_back(it.target);
-        } else if (it.kind != IT_KIND || ext(nd.first + k)) {
-          ok = false;
-        }
-      }
-    }
-    if (ok) {
-      hub[h] = 1;
-      loc[h] = std::move(out);
-    }
-  }
-  for (bool changed = true; changed;) {  // a hub's usersets must point at hubs
-    changed = false;
-    for (uint32_t h = 0; h < nf; ++h) {
-      if (!hub[h]) continue;
-      for (uint32_t n : loc[h])
-        for (uint32_t k = 0; k < nodes[n].count && hub[h]; ++k) {
-          const DevItem& it = items[nodes[n].first + k];
-          if (nodes[n].kind == NK_RELATION && it.srel != kEllipsis && (it.target >= nf || !hub[it.target])) {
-            hub[h] = 0;
-            changed = true;
-          }
-        }
-    }
-  }
-}
-
-// The ingest rules of a partitioned graph (SURVEY §8e; engine.hpp part_keep), from the schema
-// alone, so that every rank filters the export stream (client/client.go:472-499) and the Watch
-// stream the same way: the hubs a label join can meet are those of the schema whose relations
-// allow no caveat or expiration; the relations of those hubs are the hierarchy — their userset
-// (and wildcard) tuples are replicated on every rank, their direct-subject tuples are kept also by
-// the subject's owner (the subject side of the join, the user slots).
-void partition_rules(Engine& e) {
-  e.part_hub_node.clear();
-  e.part_hub_rel.clear();
-  e.part_sub_node.clear();
-  if (!e.schema) return;
-  const Schema& sc = *e.schema;
-  const uint32_t nf = (uint32_t)sc.nodes.size();
-  auto ext = [&](uint32_t i) {
-    const DevItem& it = sc.items[i];
-    const uint16_t rel = sc.item_rel[i];
-    if (rel >= sc.rels.size()) return true;
-    for (const Allowed& a : sc.rels[rel].allowed)
-      if (a.stype == it.stype && a.srel == it.srel && (!a.caveat.empty() || a.expiration)) return true;
-    return false;
-  };
-  std::vector<char> hub;
-  std::vector<std::vector<uint32_t>> loc;
-  find_hubs(sc.nodes, sc.items, nf, ext, hub, loc);
-  // A hub relation's direct tuples live with their subjects' owners, which is right only if every
-  // node that reads its rows is one of the hubs' nodes (routed there, partition.inc part_dest). A
-  // hub whose relation is also read elsewhere — e.g. as an arrow's tupleset by a permission outside
-  // the hub — is no hub of the partition (its rows stay with their objects' owners, its roots go to
-  // the level loop); dropping one changes which nodes are hub nodes, so repeat until none is read
-  // from outside.
-  for (bool changed = true; changed;) {
-    changed = false;
-    e.part_hub_rel.assign(sc.rels.size(), 0);
-    e.part_sub_node.assign(nf, 0);
-    for (uint32_t h = 0; h < nf; ++h)
-      if (hub[h])
-        for (uint32_t n : loc[h]) {
-          e.part_sub_node[n] = 1;
-          if (n < sc.rels.size() && sc.nodes[n].kind == NK_RELATION) e.part_hub_rel[n] = 1;
-        }
-    std::vector<char> bad(sc.rels.size(), 0);
-    for (uint32_t n = 0; n < nf; ++n) {
-      if (e.part_sub_node[n]) continue;
-      for (uint32_t k = 0; k < sc.nodes[n].count; ++k) {
-        const uint32_t i = sc.nodes[n].first + k;
-        const uint8_t kind = sc.items[i].kind;
-        if (kind != IT_KIND && kind != IT_ARROW) continue;
-        const uint16_t rel = sc.item_rel[i];
-        if (rel < bad.size() && e.part_hub_rel[rel]) bad[rel] = 1;
-      }
-    }
-    for (uint32_t h = 0; h < nf; ++h) {
-      if (!hub[h]) continue;
-      for (uint32_t n : loc[h])
-        if (n < bad.size() && bad[n]) {
-          hub[h] = 0;
-          changed = true;
-          break;
-        }
-    }
-  }
-  e.part_hub_node.assign(hub.begin(), hub.end());
+  j.table_bytes = (uint32_t)((ds.lj.host.size() + 3) & ~(size_t)3);
+  j.o_meta = ds.lj.o_meta;
 }
 
 // The marks of one Watch batch in one launch: a job per merged direct-grant class (its subjects'
@@ -1530,1195 +1225,6 @@ __global__ void __launch_bounds__(kBlock) k_deep_diff(const uint32_t* __restrict
                                                       uint32_t n, uint32_t max_depth, unsigned* __restrict__ flag) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i < n && (a[i] >= max_depth) != (b[i] >= max_depth)) *flag = 1u;
-}
-
-// May a Watch batch keep the current label tables although some of their CSRs changed? When every
-// changed one is a direct-grant CSR (`dkey`, the users listed in resource slots) that the batch
-// merged (Engine::delta_hint), no wildcard grant changed, no root's resource crossed the depth
-// budget: the checks of the subjects whose grants
-// changed then go to the wave bundles (k_label_join reads the dirty set), everything else the
-// tables answer as before — a 0.1 % churn of direct grants (BASELINE config 5) rebuilds nothing.
-// Not on a partitioned graph (its slots live on several ranks).
-// `own_only`: the direct-grant CSRs every root reads only on its resource's own object (a changed
-// wildcard grant there changes that resource alone). `why`: the reason a rebuild is needed.
-static bool lj_dirty_path(const Engine& e, const DeviceSnapshot& ds, const std::vector<uint64_t>& dkey,
-                          const std::vector<const uint32_t*>& hkey, uint32_t max_depth,
-                          const std::vector<uint32_t>& own_only, const std::vector<uint32_t>& hroots,
-                          const char*& why) {
-  const DeviceSnapshot& old = *e.dev;
-  why = "not a Watch batch";
-  if (!e.delta_hint || e.part_world > 1) return false;
-  why = "other grant CSRs";
-  if (old.lj_dkey.size() != dkey.size() || old.lj_hgt.size() != hkey.size()) return false;
-  uint64_t marks = 0;
-  for (size_t q = 0; q < dkey.size(); q += 4) {
-    if (old.lj_dkey[q] != dkey[q]) return false;  // (another CSR)
-    if (old.lj_dkey[q + 1] == dkey[q + 1] && old.lj_dkey[q + 2] == dkey[q + 2]) continue;
-    const DeltaHint::Fwd* f = nullptr;
-    for (const DeltaHint::Fwd& x : e.delta_hint->fwd)
-      if ((uint64_t)(uintptr_t)x.nbr == dkey[q + 1]) f = &x;
-    why = "a grant CSR the batch did not merge";
-    if (!f) return false;
-    why = "a wildcard grant read beyond its own object";
-    if (f->wild && !std::binary_search(own_only.begin(), own_only.end(), (uint32_t)dkey[q])) return false;
-    marks += f->D;
-  }
-  // (No rebuild for dirtiness: a dirty subject's checks cost the bundles' time, as without the
-  // tables, while a rebuild — 0.45 s for config 2's 2.2M resources — would not pay for itself in
-  // ten thousand batches.)
-  (void)marks;
-  // heights: a changed array must leave every resource on the same side of the budget
-  for (size_t k = 0; k < hkey.size(); ++k) {
-    if (old.lj_hgt[k] == hkey[k]) continue;
-    if (!old.lj_hgt[k] || !hkey[k]) return false;
-    const uint32_t p = hroots[k];  // (no resource of the root near the budget before or after)
-    if (p < old.hmax.size() && p < ds.hmax.size() && old.hmax[p] < max_depth && ds.hmax[p] < max_depth) continue;
-    uint32_t n = 0;
-    for (uint32_t p = 0; p < ds.hgt.size(); ++p)
-      if (ds.hgt[p] == hkey[k]) n = ds.hcount[p];
-    uint32_t n_old = 0;
-    for (uint32_t p = 0; p < old.hgt.size(); ++p)
-      if (old.hgt[p] == old.lj_hgt[k]) n_old = old.hcount[p];
-    why = "heights";
-    if (n != n_old) return false;
-    std::vector<void*> tmp;
-    unsigned hv = 0;
-    try {
-      unsigned* flag = dalloc<unsigned>(tmp, 1);
-      HIP_OK(hipMemset(flag, 0, 4));
-      if (n) hipLaunchKernelGGL(k_deep_diff, dim3(grid_for(n)), dim3(kBlock), 0, 0, old.lj_hgt[k], hkey[k], n, max_depth, flag);
-      HIP_OK(hipGetLastError());
-      HIP_OK(hipMemcpy(&hv, flag, 4, hipMemcpyDeviceToHost));
-    } catch (...) {
-      free_list(tmp);
-      throw;
-    }
-    free_list(tmp);
-    if (hv) return false;
-  }
-  return true;
-}
-
-// Marks the subjects whose direct grants the batch changed (lj_dirty_path held): the dirty set is
-// shared with the current snapshot — bits are only ever set, and a check of the current revision
-// that sees one goes to the bundles, which answer it from that revision's CSRs.
-static void lj_mark_dirty(Engine& e, DeviceSnapshot& ds, const std::vector<uint64_t>& dkey,
-                          const std::map<uint32_t, std::vector<uint32_t>>& own_roots) {
-  const DeviceSnapshot& old = *e.dev;
-  const uint32_t n_users = ds.lj_users;
-  if (!ds.lj_dirty) {
-    const size_t bytes = ((size_t)n_users / 32 + 1) * 4;
-    uint32_t* q = slot_alloc(ds, bytes);
-    HIP_OK(hipMemset(q, 0, bytes));
-    ds.lj_ptrs.push_back(q);
-    ds.lj_bytes += bytes;
-    ds.bytes += bytes;
-    ds.lj_dirty = q;
-  }
-  if (ds.lj_af && !ds.lj_dov) {  // the changed objects of each dirty subject (kDovWords per subject)
-    const size_t bytes = ((size_t)n_users + 1) * kDovWords * 4;
-    uint32_t* q = slot_alloc(ds, bytes);
-    HIP_OK(hipMemset(q, 0, bytes));
-    ds.lj_ptrs.push_back(q);
-    ds.lj_bytes += bytes;
-    ds.bytes += bytes;
-    ds.lj_dov = q;
-  }
-  LjMarks m{};
-  m.n_users = n_users;
-  m.bits = ds.lj_dirty;
-  m.dov = ds.lj_dov;
-  auto flush = [&]() {
-    if (!m.n) return;
-    hipLaunchKernelGGL(k_lj_marks, dim3(m.start[m.n]), dim3(kBlock), 0, 0, m);
-    m.n = 0;
-  };
-  auto add = [&](const DeltaHint::Fwd& f, uint32_t* rslot, uint32_t r_rows, const uint32_t* xlab, uint32_t x_rows,
-                 uint32_t wmode) {
-    if (m.n == (uint32_t)kLjMarkJobs) flush();
-    LjMarkJob& J = m.j[m.n];
-    J = LjMarkJob{f.keys, f.ins, f.found, rslot, xlab, f.D, r_rows, ds.lj_sw, x_rows, wmode};
-    m.start[m.n + 1] = m.start[m.n] + grid_for(f.D);
-    ++m.n;
-  };
-  // the forest labels of a direct-grant CSR's rows (its relation's resource type)
-  auto xlab_of = [&](uint32_t c, uint32_t& rows) -> const uint32_t* {
-    rows = 0;
-    if (!ds.lj_af) return nullptr;
-    for (auto& [cc, t] : ds.lj_dtype)
-      if (cc == c && t < ds.lj_af_base.size() && ds.lj_af_base[t] != kNone) {
-        rows = ds.lj_af_rows[t];
-        return ds.lj_af + 2 * (size_t)ds.lj_af_base[t];
-      }
-    return nullptr;
-  };
-  for (size_t q = 0; q < dkey.size(); q += 4) {
-    if (old.lj_dkey[q + 1] == dkey[q + 1] && old.lj_dkey[q + 2] == dkey[q + 2]) continue;
-    uint32_t x_rows = 0;
-    const uint32_t* xlab = xlab_of((uint32_t)dkey[q], x_rows);
-    for (const DeltaHint::Fwd& f : e.delta_hint->fwd)
-      if ((uint64_t)(uintptr_t)f.nbr == dkey[q + 1] && f.D) {
-        add(f, nullptr, 0u, xlab, x_rows, 0u);
-        ds.lj_dirty_n += f.D;
-        auto ro = own_roots.find((uint32_t)dkey[q]);
-        if (f.wild && ro != own_roots.end())  // (lj_dirty_path: read on the resource's own object only)
-          for (uint32_t p : ro->second) {
-            const uint16_t d = reinterpret_cast<const uint16_t*>(ds.lj_host.data())[p];
-            if (d == 0xFFFFu) continue;
-            LjMeta M;
-            std::memcpy(&M, ds.lj_host.data() + ds.lj_o_meta + (size_t)d * sizeof(LjMeta), sizeof(LjMeta));
-            // (a chain program: the walk reads the wildcard's current grants, lj_redecide)
-            const uint32_t wmode = !M.chain || !ds.lj_afp ? 0u : M.n_terms < 3u ? 1u : 2u;
-            if (M.n_terms) add(f, const_cast<uint32_t*>(M.rslot), M.r_rows, nullptr, 0u, wmode);
-          }
-      }
-  }
-  flush();
-  // (no synchronisation: the marks are ordered on the null stream before the publication, and
-  // the delta arena they read is rewritten only by the next batch, behind them on that stream)
-  HIP_OK(hipGetLastError());
-}
-
-// Builds the label join's tables for the snapshot into ds (lj_*), or nothing when no permission
-// qualifies. Runs after build_bidir (heights are known; the closure join, when the snapshot has
-// one of its roots, keeps the stage: the two are not combined).
-static void build_labels(Engine& e, DeviceSnapshot& ds, const std::vector<DevNode>& nodes,
-                         const std::vector<DevItem>& items, const std::vector<DevCSR>& table,
-                         const std::vector<CsrInfo>& info) {
-  ds.lj_host.clear();
-  ds.lj_sw = 0;
-  ds.lj_preferred = false;
-  ds.lj_cav = false;
-  if (e.cfg.flags & (GCK_FLAG_NO_LABELS | GCK_FLAG_NO_SLOTS)) return;
-  // a partitioned graph (world > 1) holds this rank's rows and the replicated hub hierarchy: it
-  // builds the slots of the subjects and resources it owns, indexed by part_local (the resource
-  // side flattens within its own rows and the hubs, and defers a resource whose walk leaves them)
-  const uint32_t P = e.part_world, prank = e.part_rank;
-  PhaseClock pc("labels");
-  const Schema& sc = *e.schema;
-  const uint32_t nf = ds.n_fwd;
-  const uint32_t R = (uint32_t)sc.rels.size();
-  const uint32_t max_depth = e.cfg.max_depth ? e.cfg.max_depth : 50;
-  auto count_of = [&](uint32_t type) { return e.interner[type].count; };
-  auto ext_edges = [&](const DevItem& it) { return it.csr_ext != kNone && info[it.csr_ext].n_edges > 0; };
-  auto has_rows = [&](uint32_t c) { return c != kNone && info[c].n_edges > 0; };
-  // 1. hubs: targets of usersets and arrows that are unions of stored subjects and usersets of hubs
-  std::vector<char> hub;
-  std::vector<std::vector<uint32_t>> loc;  // the hub's nodes on its own object (computed usersets)
-  find_hubs(nodes, items, nf, [&](uint32_t i) { return ext_edges(items[i]); }, hub, loc);
-  if (e.part_world > 1)  // a partitioned graph replicates the hierarchy of the schema's hubs only
-    for (uint32_t h = 0; h < nf; ++h) hub[h] &= h < e.part_hub_node.size() ? e.part_hub_node[h] : 0;
-  // the subject type: the most common direct subject type of the stored relations
-  std::vector<uint64_t> by_type(sc.types.size(), 0);
-  for (uint32_t n = 0; n < nf; ++n)
-    if (nodes[n].kind == NK_RELATION)
-      for (uint32_t k = 0; k < nodes[n].count; ++k) {
-        const DevItem& it = items[nodes[n].first + k];
-        if (it.kind == IT_KIND && it.srel == kEllipsis && it.csr_plain != kNone) by_type[it.stype] += info[it.csr_plain].n_edges;
-      }
-  const uint32_t U = (uint32_t)(std::max_element(by_type.begin(), by_type.end()) - by_type.begin());
-  if (by_type.empty() || by_type[U] == 0) return;
-  // 2. roots: permissions whose operands flatten (unions, computed usersets, arrows, stored
-  //    relations; hubs end a path)
-  std::vector<uint32_t> dfeed;  // CSRs of direct subjects: they feed only the resource slots' user lists
-  std::vector<std::pair<uint32_t, uint16_t>> dfeed_type;  // ... and the type of their rows
-  auto flattenable = [&](uint32_t t, std::vector<uint32_t>& csrs, std::vector<uint32_t>& hubs_hit, bool& cav) {
-    std::vector<uint32_t> stack{t};
-    std::vector<char> seen(nf, 0);
-    seen[t] = 1;
-    while (!stack.empty()) {
-      const uint32_t n = stack.back();
-      stack.pop_back();
-      if (hub[n]) {
-        hubs_hit.push_back(n);
-        continue;
-      }
-      const DevNode& nd = nodes[n];
-      if (nd.kind == NK_NIL) continue;
-      if (nd.kind != NK_RELATION && nd.kind != NK_UNION) return false;
-      for (uint32_t k = 0; k < nd.count; ++k) {
-        const DevItem& it = items[nd.first + k];
-        uint32_t next = kNone;
-        if (nd.kind == NK_RELATION) {
-          if (it.kind != IT_KIND) return false;
-          if (ext_edges(it)) {
-            // caveated (or expiring) relationships to direct subjects: the caveat plane of the
-            // slots; through a userset they would condition a whole hub: not flattened
-            if (it.srel != kEllipsis) return false;
-            csrs.push_back(it.csr_ext);
-            dfeed.push_back(it.csr_ext);
-            dfeed_type.push_back({it.csr_ext, nd.type});
-            cav = true;
-          }
-          if (has_rows(it.csr_plain)) {
-            csrs.push_back(it.csr_plain);
-            if (it.srel == kEllipsis) {
-              dfeed.push_back(it.csr_plain);
-              dfeed_type.push_back({it.csr_plain, nd.type});
-            }
-          }
-          if (it.srel != kEllipsis) next = it.target;
-        } else if (it.kind == IT_COMPUTED) {
-          next = it.target;
-        } else if (it.kind == IT_ARROW) {
-          if (ext_edges(it)) return false;
-          if (it.target == kNoNode) continue;
-          if (has_rows(it.csr_plain)) csrs.push_back(it.csr_plain);
-          next = it.target;
-        } else {
-          return false;  // a nested join (IT_SUB)
-        }
-        if (next != kNone) {
-          if (next >= nf) return false;
-          if (!seen[next]) seen[next] = 1, stack.push_back(next);
-        }
-      }
-    }
-    return true;
-  };
-  std::vector<LabelPlan> plans;
-  std::vector<uint32_t> csrs_all, hubs_all;
-  for (uint32_t p = 0; p < nf && p < R && p < 0xFFFFu; ++p) {
-    const DevNode& nd = nodes[p];
-    LabelPlan pl;
-    pl.p = p;
-    if (hub[p]) {  // a hub root (group#member@user): its own vertex is the only V, no slot
-      hubs_all.push_back(p);
-      plans.push_back(std::move(pl));
-      continue;
-    }
-    if (!sc.rels[p].is_perm) continue;
-    if (nd.kind == NK_EXCLUDE || nd.kind == NK_INTERSECT) {
-      if (nd.count > (uint32_t)kLjTerms) continue;
-      for (uint32_t k = 0; k < nd.count; ++k) {
-        pl.terms.push_back(items[nd.first + k].target);
-        if (nd.kind == NK_EXCLUDE && k > 0) pl.neg |= (uint8_t)(1u << k);
-      }
-    } else if (nd.kind == NK_UNION || nd.kind == NK_RELATION) {
-      pl.terms.push_back(p);
-    } else {
-      continue;
-    }
-    std::vector<uint32_t> cs, hs;
-    bool ok = true;
-    for (uint32_t t : pl.terms) ok = ok && t < nf && flattenable(t, cs, hs, pl.cav);
-    if (!ok) continue;
-    csrs_all.insert(csrs_all.end(), cs.begin(), cs.end());
-    hubs_all.insert(hubs_all.end(), hs.begin(), hs.end());
-    plans.push_back(std::move(pl));
-  }
-  if (plans.empty()) return;
-  // nothing to gain where the closure join already answers every root the labels would (a
-  // partitioned engine needs them: its checks go through the partitioned label join)
-  if (!ds.cj_host.empty() && !e.part_set) {
-    bool all_cj = true;
-    for (const LabelPlan& pl : plans)
-      all_cj &= pl.p * 2 + 1 < ds.cj_host.size() && reinterpret_cast<const uint16_t*>(ds.cj_host.data())[pl.p] != 0xFFFFu;
-    if (all_cj) return;
-  }
-  // the hubs the roots reach, closed over the hubs' usersets
-  // (hierarchy edges are read on the host; the subjects the hubs list directly stay on the device)
-  std::vector<char> used(nf, 0);
-  for (size_t k = 0; k < hubs_all.size(); ++k) {
-    const uint32_t h = hubs_all[k];
-    if (used[h]) continue;
-    used[h] = 1;
-    for (uint32_t n : loc[h])
-      for (uint32_t j = 0; j < nodes[n].count; ++j) {
-        const DevItem& it = items[nodes[n].first + j];
-        if (it.srel == kEllipsis) continue;
-        if (has_rows(it.csr_plain)) csrs_all.push_back(it.csr_plain);
-        hubs_all.push_back(it.target);
-      }
-  }
-  pc.mark("plans");
-  // 3. host copies of every CSR the flattening and the hierarchy read
-  std::sort(csrs_all.begin(), csrs_all.end());
-  csrs_all.erase(std::unique(csrs_all.begin(), csrs_all.end()), csrs_all.end());
-  // the tables depend on these CSRs (and the hubs' direct-subject ones), the roots' heights and the
-  // object counts: a Watch batch that changed none of them keeps the previous snapshot's tables;
-  // one that changed only direct grants (`dfeed`: the users listed in resource slots) keeps them
-  // too, and marks the subjects it changed (lj_dirty_path)
-  std::sort(dfeed.begin(), dfeed.end());
-  dfeed.erase(std::unique(dfeed.begin(), dfeed.end()), dfeed.end());
-  std::vector<uint64_t> key, dkey;
-  std::vector<const uint32_t*> hkey;
-  std::vector<uint32_t> hroots;
-  {
-    std::vector<uint32_t> all = csrs_all;
-    for (uint32_t h = 0; h < nf; ++h)
-      if (used[h])
-        for (uint32_t n : loc[h])
-          for (uint32_t j = 0; j < nodes[n].count; ++j) {
-            const DevItem& it = items[nodes[n].first + j];
-            if (nodes[n].kind == NK_RELATION && it.srel == kEllipsis && it.stype == U && has_rows(it.csr_plain))
-              all.push_back(it.csr_plain);
-          }
-    std::sort(all.begin(), all.end());
-    all.erase(std::unique(all.begin(), all.end()), all.end());
-    for (uint32_t c : all) {
-      std::vector<uint64_t>& k = std::binary_search(dfeed.begin(), dfeed.end(), c) ? dkey : key;
-      k.insert(k.end(), {c, (uint64_t)(uintptr_t)table[c].nbr, info[c].n_edges, table[c].n_rows});
-    }
-    for (const LabelPlan& pl : plans) {
-      key.push_back(pl.p);
-      hkey.push_back(pl.p < ds.hgt.size() ? ds.hgt[pl.p] : nullptr);
-      hroots.push_back(pl.p);
-    }
-    for (const TypeInterner& ti : e.interner) key.push_back(ti.count);
-    key.push_back(max_depth);
-  }
-  auto adopt_tables = [&](const DeviceSnapshot& old) {
-    // (taken over at publish: the current snapshot keeps them, and its checks keep running, until
-    // the new one replaces it — engine.hip device_publish)
-    ds.adopt_h.insert(ds.adopt_h.end(), old.lj_ptrs.begin(), old.lj_ptrs.end());
-    ds.lj_ptrs = old.lj_ptrs;
-    ds.lj_host = old.lj_host;
-    ds.lj_o_meta = old.lj_o_meta;
-    ds.lj_sw = old.lj_sw;
-    ds.lj_bits = old.lj_bits;
-    ds.lj_preferred = old.lj_preferred;
-    ds.lj_cav = old.lj_cav;
-    ds.lj_dirty = old.lj_dirty;
-    ds.lj_dirty_n = old.lj_dirty_n;
-    ds.lj_users = old.lj_users;
-    ds.lj_af = old.lj_af;
-    ds.lj_afp = old.lj_afp;
-    ds.lj_afp_n = old.lj_afp_n;
-    ds.lj_anc = old.lj_anc;
-    ds.lj_af_base = old.lj_af_base;
-    ds.lj_af_rows = old.lj_af_rows;
-    ds.lj_dtype = old.lj_dtype;
-    ds.lj_dov = old.lj_dov;
-    ds.lj_key = key;
-    ds.lj_dkey = dkey;
-    ds.lj_hgt = hkey;
-    ds.lj_bytes = old.lj_bytes;
-    ds.bytes += old.lj_bytes;
-  };
-  if (e.dev && !e.dev->lj_host.empty() && e.dev->lj_key == key && e.dev->lj_dkey == dkey && e.dev->lj_hgt == hkey) {
-    adopt_tables(*e.dev);
-    return;
-  }
-  // which roots read each direct-grant CSR on their resource's own object (through computed
-  // usersets only), and which CSRs some root reads further away (through an arrow or a userset)
-  std::map<uint32_t, std::vector<uint32_t>> own_roots;
-  std::vector<uint32_t> own_only;
-  {
-    std::set<uint32_t> remote;
-    for (const LabelPlan& pl : plans)
-      for (uint32_t t : pl.terms) {
-        std::vector<std::pair<uint32_t, bool>> st{{t, false}};
-        std::vector<uint8_t> seen(nf, 0);
-        seen[t] = 1;
-        while (!st.empty()) {
-          const auto [n, far] = st.back();
-          st.pop_back();
-          if (hub[n]) continue;
-          const DevNode& nd = nodes[n];
-          for (uint32_t k = 0; k < nd.count; ++k) {
-            const DevItem& it = items[nd.first + k];
-            uint32_t next = kNone;
-            bool nfar = far;
-            if (nd.kind == NK_RELATION && it.kind == IT_KIND) {
-              if (it.srel == kEllipsis) {
-                for (uint32_t c : {it.csr_plain, it.csr_ext})
-                  if (has_rows(c)) {
-                    if (far) remote.insert(c);
-                    else own_roots[c].push_back(pl.p);
-                  }
-              } else {
-                next = it.target, nfar = true;
-              }
-            } else if (nd.kind == NK_UNION && it.kind == IT_COMPUTED) {
-              next = it.target;
-            } else if (nd.kind == NK_UNION && it.kind == IT_ARROW && it.target != kNoNode) {
-              next = it.target, nfar = true;
-            }
-            if (next < nf && !(seen[next] & (nfar ? 2 : 1))) {
-              seen[next] |= nfar ? 2 : 1;
-              st.push_back({next, nfar});
-            }
-          }
-        }
-      }
-    for (auto& [c, v] : own_roots) {
-      std::sort(v.begin(), v.end());
-      v.erase(std::unique(v.begin(), v.end()), v.end());
-      if (!remote.count(c)) own_only.push_back(c);
-    }
-  }
-  const char* why = "";
-  if (e.dev && !e.dev->lj_host.empty() && e.dev->lj_key == key &&
-      lj_dirty_path(e, ds, dkey, hkey, max_depth, own_only, hroots, why)) {
-    adopt_tables(*e.dev);
-    lj_mark_dirty(e, ds, dkey, own_roots);
-    pc.mark("dirty");
-    return;
-  }
-  if (pc.on && e.dev && !e.dev->lj_host.empty())
-    pc.line += std::string(" rebuild=\"") + (e.dev->lj_key == key ? why : "structure") + "\"";
-  auto lalloc = [&](size_t bytes) {
-    uint32_t* q = slot_alloc(ds, bytes);
-    ds.lj_ptrs.push_back(q);
-    ds.lj_bytes += bytes;
-    return q;
-  };
-  std::unordered_map<uint32_t, HostRows> rows;
-  for (uint32_t c : csrs_all) {
-    HostRows& h = rows[c];
-    h.n_rows = table[c].n_rows;
-    h.off.resize((size_t)h.n_rows + 1);
-    HIP_OK(hipMemcpy(h.off.data(), table[c].off, h.off.size() * 4, hipMemcpyDeviceToHost));
-    h.nbr.resize(info[c].n_edges);
-    if (!h.nbr.empty()) HIP_OK(hipMemcpy(h.nbr.data(), table[c].nbr, h.nbr.size() * 4, hipMemcpyDeviceToHost));
-    if (table[c].is_ext && !h.nbr.empty()) {
-      h.cav.resize(h.nbr.size());
-      h.exp.resize(h.nbr.size());
-      HIP_OK(hipMemcpy(h.cav.data(), table[c].cav, h.cav.size() * 4, hipMemcpyDeviceToHost));
-      HIP_OK(hipMemcpy(h.exp.data(), table[c].exp_us, h.exp.size() * 8, hipMemcpyDeviceToHost));
-    }
-  }
-  pc.mark("host_copies");
-  // 4. the hierarchy: one vertex per object of every hub used, x -> y when x lists y#h'
-  std::vector<uint64_t> base(nf, 0);
-  uint64_t nv64 = 0;
-  for (uint32_t h = 0; h < nf; ++h)
-    if (used[h]) base[h] = nv64, nv64 += count_of(nodes[h].type);
-  if (nv64 >= (1ull << 31)) return;
-  const uint32_t NV = (uint32_t)nv64;
-  std::vector<std::pair<uint32_t, uint32_t>> edges;    // (parent, child)
-  std::vector<std::pair<uint32_t, uint64_t>> dsrc;     // (direct-subject CSR of a hub, its vertex base)
-  for (uint32_t h = 0; h < nf; ++h) {
-    if (!used[h]) continue;
-    const uint32_t nh = count_of(nodes[h].type);
-    for (uint32_t n : loc[h]) {
-      if (nodes[n].kind != NK_RELATION) continue;
-      for (uint32_t j = 0; j < nodes[n].count; ++j) {
-        const DevItem& it = items[nodes[n].first + j];
-        if (!has_rows(it.csr_plain)) continue;
-        if (it.srel == kEllipsis) {
-          if (it.stype == U) dsrc.push_back({it.csr_plain, base[h]});  // (other types never match a U check)
-          continue;
-        }
-        const HostRows& hr = rows.at(it.csr_plain);
-        const uint32_t nt = count_of(nodes[it.target].type);
-        for (uint32_t x = 0; x < hr.n_rows && x < nh; ++x)
-          for (uint32_t q = hr.off[x]; q < hr.off[x + 1]; ++q) {
-            const uint32_t y = hr.nbr[q];
-            if (y < nt) edges.push_back({(uint32_t)(base[h] + x), (uint32_t)(base[it.target] + y)});
-          }
-      }
-    }
-  }
-  pc.mark("edges");
-  std::vector<uint32_t> poff((size_t)NV + 1, 0), pnbr(edges.size()), coff((size_t)NV + 1, 0), cnbr(edges.size());
-  for (auto& ed : edges) ++poff[ed.second + 1], ++coff[ed.first + 1];
-  for (uint32_t v = 0; v < NV; ++v) poff[v + 1] += poff[v], coff[v + 1] += coff[v];
-  {
-    std::vector<uint32_t> pa(poff.begin(), poff.end() - 1), ca(coff.begin(), coff.end() - 1);
-    for (auto& ed : edges) pnbr[pa[ed.second]++] = ed.first, cnbr[ca[ed.first]++] = ed.second;
-  }
-  edges.clear();
-  edges.shrink_to_fit();
-  std::vector<uint32_t> lab, cov_off, cov_pre;
-  uint32_t n_cyclic = 0;
-  hier_labels_any(NV, poff, pnbr, coff, cnbr, lab, cov_off, cov_pre, n_cyclic);
-  // a hub root's vertices at or above the depth budget are deferred (the end word's top bit)
-  bool any_hub_root = false;
-  for (const LabelPlan& pl : plans) {
-    if (!pl.terms.empty()) continue;
-    any_hub_root = true;
-    const uint32_t p = pl.p;
-    if (p < ds.hgt.size() && ds.hgt[p] && ds.hcount[p]) {
-      std::vector<uint32_t> hh(ds.hcount[p]);
-      HIP_OK(hipMemcpy(hh.data(), ds.hgt[p], hh.size() * 4, hipMemcpyDeviceToHost));
-      const uint32_t nh = count_of(nodes[p].type);
-      for (uint32_t x = 0; x < nh; ++x)
-        if (x >= hh.size() || hh[x] >= max_depth) lab[2 * (base[p] + x) + 1] |= kLjDeep;
-    }
-  }
-  const uint32_t bits = NV < (1u << 24) - 1u ? 24u : 32u;
-  const uint32_t n_users = count_of(U);
-  const uint32_t n_users_loc = part_local_count(n_users, prank, P);  // (P = 1: n_users)
-  // a hub that lists the wildcard holds every subject: not labelled
-  {
-    std::vector<void*> tmp;
-    unsigned* flag = dalloc<unsigned>(tmp, 1);
-    unsigned hw = 0;
-    try {
-      HIP_OK(hipMemset(flag, 0, 4));
-      for (auto& [c, b] : dsrc)
-        hipLaunchKernelGGL(k_any_wildcard, dim3(grid_for(info[c].n_edges)), dim3(kBlock), 0, 0, table[c].nbr,
-                           (unsigned long long)info[c].n_edges, flag);
-      HIP_OK(hipGetLastError());
-      HIP_OK(hipMemcpy(&hw, flag, 4, hipMemcpyDeviceToHost));
-    } catch (...) {
-      free_list(tmp);
-      throw;
-    }
-    free_list(tmp);
-    if (hw) return;
-  }
-  pc.mark("hierarchy");
-  // 4b. the arrow forest (a dirty subject's checks, k_label_join round 2): the objects a
-  // resource's flattening visits are those its arrows and non-hub usersets lead to; when every
-  // object leads to at most one other (a document's folder, a folder's parent) they form a forest,
-  // and the grants flattened into R's slot are those of R and its ancestors. Preorder intervals
-  // over it let the join test "X is R or an ancestor of R" in one compare: a changed grant of the
-  // subject on X touches R's slot only then. No forest (an object with two such edges, a cycle, a
-  // partitioned graph): a dirty subject's checks defer, as before.
-  std::vector<uint32_t> af_base(sc.types.size(), kNone), af_rows(sc.types.size(), 0), af_lab;
-  std::vector<uint32_t> par, via;  // per forest vertex: its parent (kNone: a root), the CSR of that edge
-  if (P == 1) {
-    struct Trav {
-      uint32_t csr;
-      uint16_t src, dst;
-    };
-    std::vector<Trav> trav;
-    std::vector<char> vtype(sc.types.size(), 0);
-    for (const LabelPlan& pl : plans) {
-      if (pl.terms.empty()) continue;
-      vtype[nodes[pl.p].type] = 1;
-      for (uint32_t t : pl.terms) {
-        std::vector<uint32_t> st{t};
-        std::vector<char> seen(nf, 0);
-        seen[t] = 1;
-        while (!st.empty()) {
-          const uint32_t n = st.back();
-          st.pop_back();
-          if (hub[n]) continue;
-          const DevNode& nd = nodes[n];
-          for (uint32_t k = 0; k < nd.count; ++k) {
-            const DevItem& it = items[nd.first + k];
-            uint32_t next = kNone;
-            if (nd.kind == NK_UNION && it.kind == IT_COMPUTED) next = it.target;
-            else if ((nd.kind == NK_UNION && it.kind == IT_ARROW) || (nd.kind == NK_RELATION && it.kind == IT_KIND && it.srel != kEllipsis)) {
-              if (it.target == kNoNode || it.target >= nf) continue;
-              next = it.target;
-              if (!hub[next] && has_rows(it.csr_plain)) trav.push_back({it.csr_plain, nd.type, nodes[next].type});
-            }
-            if (next < nf && !seen[next]) seen[next] = 1, st.push_back(next);
-          }
-        }
-      }
-    }
-    for (const Trav& tv : trav) vtype[tv.src] = vtype[tv.dst] = 1;
-    uint64_t nva = 0;
-    for (size_t t = 0; t < vtype.size(); ++t)
-      if (vtype[t]) af_base[t] = (uint32_t)nva, af_rows[t] = count_of((uint32_t)t), nva += af_rows[t];
-    bool forest = nva > 0 && nva < (1ull << 31);
-    if (forest) par.assign(nva, kNone), via.assign(nva, kNone);
-    std::sort(trav.begin(), trav.end(), [](const Trav& a, const Trav& b) { return a.csr < b.csr; });
-    trav.erase(std::unique(trav.begin(), trav.end(), [](const Trav& a, const Trav& b) { return a.csr == b.csr; }), trav.end());
-    for (const Trav& tv : trav) {
-      if (!forest) break;
-      const HostRows& hr = rows.at(tv.csr);
-      const uint32_t nx = std::min(hr.n_rows, af_rows[tv.src]), ny = af_rows[tv.dst];
-      for (uint32_t x = 0; x < nx && forest; ++x)
-        for (uint32_t q = hr.off[x]; q < hr.off[x + 1]; ++q) {
-          const uint32_t y = hr.nbr[q];
-          if (y == kWildcard || y >= ny) continue;
-          const uint32_t v = af_base[tv.src] + x, p = af_base[tv.dst] + y;
-          if (v == p || (par[v] != kNone && par[v] != p)) {
-            forest = false;
-            break;
-          }
-          par[v] = p;
-          via[v] = tv.csr;
-        }
-    }
-    if (forest) {  // preorder over the children, from every parentless vertex
-      const uint32_t NVa = (uint32_t)nva;
-      std::vector<uint32_t> coff2((size_t)NVa + 1, 0), cn2;
-      for (uint32_t v = 0; v < NVa; ++v)
-        if (par[v] != kNone) ++coff2[par[v] + 1];
-      for (uint32_t v = 0; v < NVa; ++v) coff2[v + 1] += coff2[v];
-      cn2.resize(coff2[NVa]);
-      {
-        std::vector<uint32_t> at(coff2.begin(), coff2.end() - 1);
-        for (uint32_t v = 0; v < NVa; ++v)
-          if (par[v] != kNone) cn2[at[par[v]]++] = v;
-      }
-      af_lab.assign(2 * (size_t)NVa, 0);
-      uint32_t ctr = 0, done = 0;
-      std::vector<std::pair<uint32_t, uint32_t>> stk;  // (vertex, next child)
-      for (uint32_t r0 = 0; r0 < NVa; ++r0) {
-        if (par[r0] != kNone) continue;
-        stk.push_back({r0, coff2[r0]});
-        af_lab[2 * (size_t)r0] = ctr++;
-        while (!stk.empty()) {
-          auto& [v, c] = stk.back();
-          if (c < coff2[v + 1]) {
-            const uint32_t ch = cn2[c++];
-            af_lab[2 * (size_t)ch] = ctr++;
-            stk.push_back({ch, coff2[ch]});
-          } else {
-            af_lab[2 * (size_t)v + 1] = ctr;
-            ++done;
-            stk.pop_back();
-          }
-        }
-      }
-      if (done != NVa) forest = false;  // (a cycle: vertices no root reaches)
-    }
-    if (!forest) {
-      af_lab.clear();
-      par.clear();
-      via.clear();
-      std::fill(af_base.begin(), af_base.end(), kNone);
-    }
-    if (pc.on) pc.line += std::string(" forest=") + (forest ? std::to_string(nva) : "none");
-  }
-  // 5. resource slots: flatten every term of every root over every resource
-  std::vector<const uint32_t*> hgt_dev(plans.size(), nullptr);
-  auto flatten = [&](uint32_t r, uint32_t t, Flat& f, std::vector<uint64_t>& stack, std::vector<uint64_t>& seen) {
-    f.D.clear();
-    f.V.clear();
-    f.C.clear();
-    f.wild = f.over = false;
-    stack.assign(1, ((uint64_t)t << 32) | r);
-    seen.clear();
-    while (!stack.empty()) {
-      const uint64_t s = stack.back();
-      stack.pop_back();
-      const uint32_t n = (uint32_t)(s >> 32), x = (uint32_t)s;
-      if (hub[n]) {
-        if (x < count_of(nodes[n].type)) f.V.push_back((uint32_t)(base[n] + x));
-        if (f.V.size() > kLjFlatCap) return f.over = true, void();
-        continue;
-      }
-      if (P > 1 && part_owner(x, P) != prank) return f.over = true, void();  // another rank's rows
-      if (std::find(seen.begin(), seen.end(), s) != seen.end()) continue;
-      seen.push_back(s);
-      if (seen.size() > 256) return f.over = true, void();  // (a long arrow chain: the bundles walk it)
-      const DevNode& nd = nodes[n];
-      for (uint32_t k = 0; k < nd.count; ++k) {
-        const DevItem& it = items[nd.first + k];
-        if (nd.kind == NK_UNION && it.kind == IT_COMPUTED) {
-          stack.push_back(((uint64_t)it.target << 32) | x);
-          continue;
-        }
-        if (nd.kind == NK_RELATION && it.srel == kEllipsis && it.stype == U && has_rows(it.csr_ext)) {
-          // caveated / expiring direct subjects: a caveat decided by the stored context alone is a
-          // plain edge or none (Engine::caveat_static); a partial one a caveated pair; an expiring
-          // relationship is for the bundles (its visibility depends on the check's time)
-          const HostRows& hx = rows.at(it.csr_ext);
-          if (x < hx.n_rows)
-            for (uint32_t q = hx.off[x]; q < hx.off[x + 1]; ++q) {
-              if (hx.exp[q] != 0) return f.over = true, void();
-              const uint32_t y = hx.nbr[q], cv = hx.cav[q];
-              const uint8_t st = cv < e.caveat_static.size() ? e.caveat_static[cv] : (uint8_t)cel::PARTIAL;
-              if (st == cel::FALSE) continue;
-              if (st == cel::TRUE) {
-                if (y == kWildcard) f.wild = true;
-                else f.D.push_back(y);
-              } else {
-                f.C.push_back(y == kWildcard ? kLjCavWild : y);
-                f.C.push_back(cv);
-              }
-            }
-          if (f.C.size() > 2 * kLjFlatCap) return f.over = true, void();
-        }
-        if (!has_rows(it.csr_plain) || (nd.kind == NK_UNION && (it.kind != IT_ARROW || it.target == kNoNode))) continue;
-        const HostRows& hr = rows.at(it.csr_plain);
-        if (x >= hr.n_rows) continue;
-        for (uint32_t q = hr.off[x]; q < hr.off[x + 1]; ++q) {
-          const uint32_t y = hr.nbr[q];
-          if (nd.kind == NK_RELATION && it.srel == kEllipsis) {
-            if (it.stype != U) break;
-            if (y == kWildcard) f.wild = true;
-            else f.D.push_back(y);
-          } else if (y != kWildcard) {
-            stack.push_back(((uint64_t)it.target << 32) | y);
-          }
-        }
-        if (f.D.size() > kLjFlatCap || stack.size() > 16 * kLjFlatCap) return f.over = true, void();
-      }
-    }
-    std::sort(f.D.begin(), f.D.end());
-    f.D.erase(std::unique(f.D.begin(), f.D.end()), f.D.end());
-    if (!f.C.empty()) {  // caveated pairs once each (kept beside a plain grant of the same user:
-                         // the check still evaluates the caveat, which may fail)
-      std::vector<std::pair<uint32_t, uint32_t>> cp;
-      for (size_t q = 0; q < f.C.size(); q += 2) cp.push_back({f.C[q], f.C[q + 1]});
-      std::sort(cp.begin(), cp.end());
-      cp.erase(std::unique(cp.begin(), cp.end()), cp.end());
-      f.C.clear();
-      for (auto& [u, cv] : cp) f.C.push_back(u | kLjCav), f.C.push_back(cv);
-    }
-    // V as intervals, nested ones dropped (an interval inside another adds nothing)
-    std::vector<std::pair<uint32_t, uint32_t>> iv;
-    for (uint32_t v : f.V) iv.push_back({lab[2 * (size_t)v] & ~kSlotOverflow, lab[2 * (size_t)v + 1] & ~kLjDeep});
-    std::sort(iv.begin(), iv.end(), [](auto& a, auto& b) { return a.first < b.first || (a.first == b.first && a.second > b.second); });
-    f.V.clear();
-    uint32_t reach = 0;
-    bool any = false;
-    for (auto& [lo, hi] : iv) {
-      if (any && hi <= reach) continue;
-      f.V.push_back(lo);
-      f.V.push_back(hi - lo);
-      reach = hi;
-      any = true;
-    }
-  };
-  // per root: its heights (a resource at or above the budget is deferred) and a sample of its
-  // slot sizes (16 words when nearly every resource fits, else 32)
-  std::vector<std::vector<uint32_t>> hgt_host(plans.size());
-  for (size_t k = 0; k < plans.size(); ++k) {
-    const uint32_t p = plans[k].p;
-    if (plans[k].terms.empty()) continue;
-    if (p < ds.hgt.size() && ds.hgt[p] && ds.hcount[p]) {
-      hgt_host[k].resize(ds.hcount[p]);
-      HIP_OK(hipMemcpy(hgt_host[k].data(), ds.hgt[p], (size_t)ds.hcount[p] * 4, hipMemcpyDeviceToHost));
-    }
-  }
-  // inline slots of 24-bit fields (LjEnt24) when every entry fits: users (below the caveated-pair
-  // flag when a root has caveated pairs), hierarchy preorder numbers and lengths, caveat instances
-  bool any_cav = false;
-  for (const LabelPlan& pl : plans) any_cav |= pl.cav;
-  const bool can_pack = NV < 0xFFFFFFu && n_users < (any_cav ? 0x7FFFFFu : 0xFFFFFFu) &&
-                        e.caveat_static.size() < 0xFFFFFFu;
-  bool pack = false;
-  auto words_in = [&](const std::vector<Flat>& fs, bool& inline_ok, bool p24) {
-    uint32_t fields = 0;
-    inline_ok = true;
-    for (const Flat& f : fs) {
-      fields += (uint32_t)(f.D.size() + f.C.size() + f.V.size());
-      inline_ok &= f.D.size() + f.C.size() <= kLjMaxD && f.V.size() / 2 <= kLjMaxV;
-    }
-    return p24 ? (32u + 24u * fields + 31u) / 32u : 1u + fields;
-  };
-  auto words_of = [&](const std::vector<Flat>& fs, bool& inline_ok) { return words_in(fs, inline_ok, pack); };
-  // the slot width and the encoding from a sample of every root's resources: 16 words when nearly
-  // every resource fits, else 32; 24-bit fields only where they buy something — a narrower slot,
-  // or clearly fewer extension records (their decoding costs ALU per entry: config 3, whose
-  // records fit 16 words either way, ran 7 % slower packed)
-  uint32_t sw32 = 16, sw24 = 16;
-  uint64_t n_all = 0, ext32 = 0, ext24 = 0;
-  for (LabelPlan& pl : plans) {
-    if (pl.terms.empty()) continue;
-    const uint32_t n_res = part_local_count(count_of(nodes[pl.p].type), prank, P);  // (this rank's)
-    const uint32_t n_samp = std::min<uint32_t>(n_res, 4096);
-    uint32_t fit32 = 0, fit24 = 0;
-    std::vector<std::pair<uint32_t, uint32_t>> wds;  // (words unpacked, packed) of the inline ones
-    std::vector<Flat> fs(pl.terms.size());
-    std::vector<uint64_t> st, seen;
-    for (uint32_t k = 0; k < n_samp; ++k) {
-      const uint32_t r = (uint32_t)(((uint64_t)k * 2654435761ull) % std::max<uint32_t>(n_res, 1)) * P + prank;
-      bool over = false;
-      for (size_t t = 0; t < pl.terms.size(); ++t) flatten(r, pl.terms[t], fs[t], st, seen), over |= fs[t].over;
-      if (over) continue;
-      bool ok;
-      const uint32_t w32 = words_in(fs, ok, false), w24 = words_in(fs, ok, true);
-      if (!ok) {
-        ++ext32, ++ext24, ++n_all;
-        continue;
-      }
-      fit32 += w32 <= 16, fit24 += w24 <= 16;
-      wds.push_back({w32, w24});
-      ++n_all;
-    }
-    const uint32_t need32 = fit32 >= n_samp - n_samp / 32 ? 16u : 32u;
-    const uint32_t need24 = fit24 >= n_samp - n_samp / 32 ? 16u : 32u;
-    for (auto& [a, b] : wds) ext32 += a > need32, ext24 += b > need24;
-    pl.sw_need = need32;
-    sw32 = std::max(sw32, need32);
-    sw24 = std::max(sw24, need24);
-  }
-  // packed when it removes extension records (config 2: 3 % -> 0.15 % of the resources), or
-  // narrows the slot without adding them (config 3 at 16 words: 0.01 % -> 0.3 %, and a wave waits
-  // for its slowest lane's extra round trip — 9.0 vs 9.9 G checks/s unpacked)
-  pack = can_pack && ((ext24 + n_all / 50 < ext32) || (sw24 < sw32 && ext24 <= ext32 + n_all / 1000));
-  if (const char* f = debug_env("GCK_DEBUG_LJ_PACK")) pack = can_pack && atoi(f) != 0;  // (an A/B of the encoding)
-  uint32_t sw = pack ? sw24 : sw32;
-  if (pc.on)
-    pc.line += " sample[n=" + std::to_string(n_all) + " ext32=" + std::to_string(ext32) + " ext24=" + std::to_string(ext24) +
-               " sw32=" + std::to_string(sw32) + " sw24=" + std::to_string(sw24) + "]";
-  // memory: every root's slots plus the user slots must take at most half of the free HBM
-  {
-    uint64_t need = (uint64_t)n_users_loc * kUSlotWords * 4;
-    for (const LabelPlan& pl : plans)
-      if (!pl.terms.empty()) need += (uint64_t)part_local_count(count_of(nodes[pl.p].type), prank, P) * sw * 4;
-    size_t free_b = 0, total_b = 0;
-    HIP_OK(hipMemGetInfo(&free_b, &total_b));
-    if (need > free_b / 2) return;
-  }
-  pc.mark("sizing");
-  // user slots over the hierarchy (closure.inc k_user_slots_1p: the covers of the vertices listing
-  // each subject, inline or as a list)
-  const uint32_t* uslot = nullptr;
-  const uint32_t* ulist = nullptr;
-  const uint32_t* lab_dev = nullptr;
-  {
-    std::vector<void*> tmp;
-    try {
-      // (kept with the snapshot when a hub root reads its vertex's interval from it)
-      // (+64 B: k_label_join loads kLines - 1 lines from a hub root's label line, and the second
-      // one of the array's last line would lie past the end)
-      uint32_t* d_lab = any_hub_root ? lalloc(std::max<size_t>(lab.size(), 1) * 4 + 64)
-                                     : dalloc<uint32_t>(tmp, std::max<size_t>(lab.size(), 1));
-      if (any_hub_root) HIP_OK(hipMemset(d_lab + lab.size(), 0, 64));
-      lab_dev = d_lab;
-      uint32_t* d_coff = dalloc<uint32_t>(tmp, cov_off.size());
-      uint32_t* d_cpre = dalloc<uint32_t>(tmp, std::max<size_t>(cov_pre.size(), 1));
-      // subject -> the vertices listing it, a CSR over the subject type built on the device from
-      // every hub's direct-subject CSRs: counts, scan, scatter with each hub's vertex base
-      uint64_t n_pairs = 0;
-      for (auto& [c, b] : dsrc) n_pairs += info[c].n_edges;
-      if (n_pairs >= (1ull << 32)) throw Error(GCK_E_CAPACITY, "label join: too many direct memberships");
-      const uint32_t nu = n_users_loc;  // the subjects whose slots this rank holds
-      uint32_t* d_doff = dalloc<uint32_t>(tmp, (size_t)nu + 1);
-      uint32_t* d_dnbr = dalloc<uint32_t>(tmp, std::max<uint64_t>(n_pairs, 1));
-      uint32_t* d_cnt = dalloc<uint32_t>(tmp, std::max<uint32_t>(nu, 1));
-      HIP_OK(hipStreamSynchronize(nullptr));
-      if (!lab.empty()) HIP_OK(hipMemcpy(d_lab, lab.data(), lab.size() * 4, hipMemcpyHostToDevice));
-      HIP_OK(hipMemcpy(d_coff, cov_off.data(), cov_off.size() * 4, hipMemcpyHostToDevice));
-      if (!cov_pre.empty()) HIP_OK(hipMemcpy(d_cpre, cov_pre.data(), cov_pre.size() * 4, hipMemcpyHostToDevice));
-      // (a partitioned graph: the subjects this rank owns, at their part_local index)
-      HIP_OK(hipMemset(d_cnt, 0, (size_t)std::max<uint32_t>(nu, 1) * 4));
-      for (auto& [c, b] : dsrc)
-        hipLaunchKernelGGL(k_count_subjects_part, dim3(grid_for(info[c].n_edges)), dim3(kBlock), 0, 0, table[c].nbr,
-                           (unsigned long long)info[c].n_edges, n_users, prank, P, d_cnt);
-      HIP_OK(hipGetLastError());
-      device_excl_scan(d_cnt, nu, d_doff);
-      HIP_OK(hipMemcpy(d_cnt, d_doff, (size_t)std::max<uint32_t>(nu, 1) * 4, hipMemcpyDeviceToDevice));
-      for (auto& [c, b] : dsrc)
-        hipLaunchKernelGGL(k_transpose_scatter_base, dim3(grid_for(info[c].n_edges)), dim3(kBlock), 0, 0, table[c].off,
-                           table[c].nbr, table[c].n_rows, (unsigned long long)info[c].n_edges, n_users, d_cnt, d_dnbr,
-                           (uint32_t)b, prank, P);
-      HIP_OK(hipGetLastError());
-      uint32_t* s = lalloc((size_t)std::max<uint32_t>(nu, 1) * kUSlotWords * 4);
-      uint32_t* list = nullptr;
-      // (bidir.inc build_user_slots; the sizing above has already bounded the slots, and the lists
-      // are allocated whatever is free)
-      if (nu) list = build_user_slots(bits, d_doff, d_dnbr, nu, d_lab, d_coff, d_cpre, NV, s, lalloc).list;
-      uslot = s;
-      ulist = list;
-    } catch (...) {
-      free_list(tmp);
-      throw;
-    }
-    free_list(tmp);
-  }
-  pc.mark("user_slots");
-  const uint32_t* af_dev = nullptr;
-  unsigned long long* afp_dev = nullptr;
-  uint32_t* anc_dev = nullptr;
-  if (!af_lab.empty()) {
-    uint32_t* q = lalloc(af_lab.size() * 4);
-    HIP_OK(hipMemcpy(q, af_lab.data(), af_lab.size() * 4, hipMemcpyHostToDevice));
-    af_dev = q;
-    // the parent edges for the chain walk (tupleset CSR << 32 | parent), with the forest
-    std::vector<unsigned long long> afp(par.size());
-    for (size_t v = 0; v < par.size(); ++v) afp[v] = ((unsigned long long)via[v] << 32) | par[v];
-    afp_dev = reinterpret_cast<unsigned long long*>(lalloc(std::max<size_t>(afp.size(), 1) * 8));
-    if (!afp.empty()) HIP_OK(hipMemcpy(afp_dev, afp.data(), afp.size() * 8, hipMemcpyHostToDevice));
-    // each vertex's ancestors in one line (lj_chain_wave): its whole chain in one round
-    std::vector<uint32_t> anc(par.size() * kAncWords, 0u);
-    host_parallel(par.size(), 1 << 14, [&](size_t lo, size_t hi) {
-      for (size_t v = lo; v < hi; ++v) {
-        uint32_t* L = &anc[v * kAncWords];
-        uint32_t n = 0, x = (uint32_t)v;
-        while (par[x] != kNone) {
-          if (n + 1 == kAncWords) {
-            n |= kAncOver;
-            break;
-          }
-          x = par[x];
-          L[++n] = x;
-        }
-        L[0] = n;
-      }
-    });
-    anc_dev = lalloc(std::max<size_t>(anc.size(), 1) * 4);
-    if (!anc.empty()) HIP_OK(hipMemcpy(anc_dev, anc.data(), anc.size() * 4, hipMemcpyHostToDevice));
-  }
-  // 5b. chain programs (LjChain, lj_chain_walk): per term the sets of schema nodes its flattening
-  // holds at each depth of the resource's forest chain — the nodes reached through computed
-  // usersets on one object, then through the level's arrow on the parent — and the direct-user
-  // classes those nodes read. Exact only where the walk can follow the flattening: every arrow of
-  // a level over one tupleset CSR (the forest edge the walk checks), no userset to a node that is
-  // not a hub (its objects would be other chains), unions and stored relations only. Otherwise the
-  // root has no program and its overlay hits defer, as before.
-  auto lj_chain_of = [&](const LabelPlan& pl, LjChain& ch) -> bool {
-    std::memset(&ch, 0, sizeof(ch));
-    std::memset(ch.first, kLjChainEnd, sizeof(ch.first));
-    std::vector<std::vector<uint32_t>> sets;
-    auto closure = [&](std::vector<uint32_t> st) {
-      std::vector<char> seen(nf, 0);
-      std::vector<uint32_t> out;
-      while (!st.empty()) {
-        const uint32_t n = st.back();
-        st.pop_back();
-        if (n >= nf || seen[n] || hub[n]) continue;
-        seen[n] = 1;
-        out.push_back(n);
-        const DevNode& nd = nodes[n];
-        if (nd.kind != NK_UNION) continue;
-        for (uint32_t k = 0; k < nd.count; ++k)
-          if (items[nd.first + k].kind == IT_COMPUTED) st.push_back(items[nd.first + k].target);
-      }
-      std::sort(out.begin(), out.end());
-      return out;
-    };
-    for (size_t t = 0; t < pl.terms.size(); ++t) {
-      std::vector<uint32_t> N = closure({pl.terms[t]});
-      uint8_t* link = &ch.first[t];
-      for (;;) {
-        const auto f = std::find(sets.begin(), sets.end(), N);
-        if (f != sets.end()) {
-          *link = (uint8_t)(f - sets.begin());
-          break;
-        }
-        if (sets.size() == kLjChainLvls) return false;
-        LjChainLvl L{};
-        L.arrow = 0xFFFFu;
-        L.next = kLjChainEnd;
-        uint32_t type = kNone, arrow = kNone;
-        std::vector<uint32_t> targets;
-        for (uint32_t n : N) {
-          const DevNode& nd = nodes[n];
-          if (type != kNone && nd.type != type) return false;
-          type = nd.type;
-          if (nd.kind == NK_NIL) continue;
-          if (nd.kind != NK_RELATION && nd.kind != NK_UNION) return false;
-          for (uint32_t k = 0; k < nd.count; ++k) {
-            const DevItem& it = items[nd.first + k];
-            if (nd.kind == NK_RELATION) {
-              if (it.kind != IT_KIND) return false;
-              if (it.srel != kEllipsis) {
-                if (it.target == kNoNode || it.target >= nf || !hub[it.target]) return false;
-                continue;  // (a hub's members: the slot's intervals)
-              }
-              if (it.stype != U) continue;
-              for (uint32_t c : {it.csr_plain, it.csr_ext})
-                if (has_rows(c)) {
-                  if (L.n == kLjChainCls || c >= 0xFFFFu) return false;
-                  L.csr[L.n++] = (uint16_t)c;
-                }
-            } else if (it.kind == IT_ARROW) {
-              if (it.target == kNoNode || it.target >= nf || hub[it.target] || !has_rows(it.csr_plain)) continue;
-              if (arrow != kNone && arrow != it.csr_plain) return false;
-              arrow = it.csr_plain;
-              targets.push_back(it.target);
-            } else if (it.kind != IT_COMPUTED) {
-              return false;
-            }
-          }
-        }
-        if (type == kNone || type >= af_base.size() || af_base[type] == kNone || (arrow != kNone && arrow >= 0xFFFFu)) return false;
-        L.af_base = af_base[type];
-        const size_t idx = sets.size();
-        sets.push_back(N);
-        ch.lvl[idx] = L;
-        *link = (uint8_t)idx;
-        if (targets.empty()) break;
-        ch.lvl[idx].arrow = (uint16_t)arrow;
-        link = &ch.lvl[idx].next;
-        N = closure(targets);
-      }
-    }
-    for (size_t t = 0; t < pl.terms.size(); ++t)
-      if (ch.first[t] >= sets.size()) return false;
-    for (size_t l = 0; l < sets.size(); ++l)
-      if (ch.lvl[l].next != kLjChainEnd && ch.lvl[l].next >= sets.size()) return false;
-    return true;
-  };
-  // resource slots, every root, in parallel over the resources; records that do not fit inline go
-  // to the extension array (one per root)
-  std::vector<LjMeta> metas;
-  std::vector<uint16_t> root(nf, 0xFFFFu);
-  for (size_t k = 0; k < plans.size(); ++k) {
-    const LabelPlan& pl = plans[k];
-    const uint32_t n_res = count_of(nodes[pl.p].type);
-    if (pl.terms.empty()) {  // hub root: the "slot" is the vertex's interval in the labels
-      LjMeta M{};
-      M.uslot = uslot;
-      M.ulist = ulist;
-      M.rslot = lab_dev + 2 * base[pl.p];
-      M.u_rows = n_users;
-      M.r_rows = n_res;
-      M.rtype = nodes[pl.p].type;
-      M.utype = (uint16_t)U;
-      M.n_terms = 0;
-      root[pl.p] = (uint16_t)metas.size();
-      metas.push_back(M);
-      continue;
-    }
-    // (a partitioned graph: the resources this rank owns, slot li = resource li * P + rank)
-    const uint32_t n_loc = part_local_count(n_res, prank, P);
-    std::vector<uint32_t> slots((size_t)std::max<uint32_t>(n_loc, 1) * sw, 0);
-    std::mutex ext_mu;
-    std::vector<std::pair<uint32_t, std::vector<uint32_t>>> exts;  // (first slot of the chunk, records)
-    std::atomic<uint64_t> n_ext{0}, n_over{0}, n_pairs{0};  // (GCK_DEBUG_PHASES: the slot formats)
-    const std::vector<uint32_t>& hh = hgt_host[k];
-    host_parallel(n_loc, 4096, [&](size_t lo, size_t hi) {
-      std::vector<Flat> fs(pl.terms.size());
-      std::vector<uint64_t> st, seen;
-      std::vector<uint32_t> ext;
-      for (size_t li = lo; li < hi; ++li) {
-        const size_t r = li * P + prank;
-        uint32_t* w = &slots[li * sw];
-        if (!hh.empty() && (r >= hh.size() || hh[r] >= max_depth)) {
-          w[0] = kLjHdrOverflow;
-          continue;
-        }
-        bool over = false;
-        for (size_t t = 0; t < pl.terms.size(); ++t) {
-          flatten((uint32_t)r, pl.terms[t], fs[t], st, seen);
-          over |= fs[t].over;
-        }
-        if (over) {
-          w[0] = kLjHdrOverflow;
-          ++n_over;
-          continue;
-        }
-        for (const Flat& f : fs) n_pairs += f.C.size() / 2;
-        bool ok;
-        const uint32_t words = words_of(fs, ok);
-        if (ok && words <= sw) {
-          uint32_t hdr = 0, pos = 1, fld = 0;
-          // a 24-bit field at bit 32 + 24 j of the slot (the caveated-pair flag and wildcard
-          // re-encoded: LjEnt24)
-          auto put24 = [&](uint32_t v) {
-            const uint32_t b = 32u + 24u * fld++, i = b >> 5, sh = b & 31u;
-            w[i] |= v << sh;
-            if (sh > 8u) w[i + 1] |= v >> (32u - sh);
-          };
-          for (size_t t = 0; t < fs.size(); ++t) {
-            const uint32_t nD = (uint32_t)(fs[t].D.size() + fs[t].C.size());
-            hdr |= (nD | (uint32_t)(fs[t].V.size() / 2) << 5 | (fs[t].wild ? 1u : 0u) << 9) << (10 * t);
-            if (pack) {
-              for (uint32_t v : fs[t].D) put24(v);
-              for (size_t q = 0; q < fs[t].C.size(); q += 2) {
-                const uint32_t a = fs[t].C[q];
-                put24(a == (kLjCav | kLjCavWild) ? 0xFFFFFFu : ((a & ~kLjCav) | LjEnt24::kCav));
-                put24(fs[t].C[q + 1]);
-              }
-              for (uint32_t v : fs[t].V) put24(v);
-            } else {
-              for (uint32_t v : fs[t].D) w[pos++] = v;
-              for (uint32_t v : fs[t].C) w[pos++] = v;
-              for (uint32_t v : fs[t].V) w[pos++] = v;
-            }
-          }
-          w[0] = hdr;
-        } else {
-          ++n_ext;
-          w[0] = kLjHdrExt;
-          w[1] = (uint32_t)ext.size();  // chunk-local; made global below
-          uint32_t h0 = (uint32_t)fs.size();
-          for (size_t t = 0; t < fs.size(); ++t) h0 |= (fs[t].wild ? 1u : 0u) << (8 + t);
-          ext.push_back(h0);
-          for (const Flat& f : fs) ext.push_back((uint32_t)(f.D.size() + f.C.size())), ext.push_back((uint32_t)(f.V.size() / 2));
-          for (const Flat& f : fs) {
-            ext.insert(ext.end(), f.D.begin(), f.D.end());
-            ext.insert(ext.end(), f.C.begin(), f.C.end());
-            ext.insert(ext.end(), f.V.begin(), f.V.end());
-          }
-        }
-      }
-      std::lock_guard<std::mutex> lk(ext_mu);
-      exts.push_back({(uint32_t)lo, std::move(ext)});
-    });
-    if (pc.on)
-      pc.line += " root" + std::to_string(pl.p) + "[n=" + std::to_string(n_loc) + " need=" + std::to_string(pl.sw_need) +
-                 " ext=" + std::to_string(n_ext.load()) +
-                 " deferred=" + std::to_string(n_over.load()) + " pairs=" + std::to_string(n_pairs.load()) + "]";
-    std::sort(exts.begin(), exts.end(), [](auto& a, auto& b) { return a.first < b.first; });
-    std::vector<uint32_t> ext_all;
-    for (size_t c = 0; c < exts.size(); ++c) {
-      const uint32_t lo = exts[c].first, hi = c + 1 < exts.size() ? exts[c + 1].first : n_loc;
-      const uint32_t b = (uint32_t)ext_all.size();
-      if (ext_all.size() + exts[c].second.size() >= (1ull << 31)) return;
-      for (uint32_t r = lo; r < hi; ++r)
-        if (slots[(size_t)r * sw] == kLjHdrExt) slots[(size_t)r * sw + 1] += b;
-      ext_all.insert(ext_all.end(), exts[c].second.begin(), exts[c].second.end());
-    }
-    uint32_t* d_slots = lalloc(slots.size() * 4);
-    HIP_OK(hipMemcpy(d_slots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
-    uint32_t* d_ext = nullptr;
-    if (!ext_all.empty()) {
-      d_ext = lalloc(ext_all.size() * 4);
-      HIP_OK(hipMemcpy(d_ext, ext_all.data(), ext_all.size() * 4, hipMemcpyHostToDevice));
-    }
-    LjMeta M{};
-    M.uslot = uslot;
-    M.ulist = ulist;
-    M.rslot = d_slots;
-    M.rext = d_ext;
-    M.u_rows = n_users;
-    M.r_rows = n_res;
-    M.rtype = nodes[pl.p].type;
-    M.utype = (uint16_t)U;
-    M.n_terms = (uint8_t)pl.terms.size();
-    M.neg = pl.neg;
-    M.cav = pl.cav ? 1 : 0;
-    M.pack = pack ? 1 : 0;
-    M.apre = af_dev && af_base[M.rtype] != kNone ? af_dev + 2 * (size_t)af_base[M.rtype] : nullptr;
-    M.chain = nullptr;
-    if (M.apre && afp_dev) {
-      LjChain ch;
-      if (lj_chain_of(pl, ch)) {
-        LjChain* q = reinterpret_cast<LjChain*>(lalloc(sizeof(LjChain)));
-        HIP_OK(hipMemcpy(q, &ch, sizeof(LjChain), hipMemcpyHostToDevice));
-        M.chain = q;
-      }
-      if (pc.on) {
-        pc.line += std::string(" chain") + std::to_string(pl.p) + "=";
-        if (!M.chain) pc.line += "no";
-        for (size_t t = 0; M.chain && t < pl.terms.size(); ++t) pc.line += "t" + std::to_string(ch.first[t]);
-        for (uint32_t l = 0; M.chain && l < kLjChainLvls && (ch.lvl[l].n || ch.lvl[l].arrow); ++l)
-          pc.line += "[" + std::to_string(ch.lvl[l].af_base) + "," + std::to_string(ch.lvl[l].n) + "," +
-                     std::to_string(ch.lvl[l].arrow) + "," + std::to_string(ch.lvl[l].next) + "]";
-      }
-    }
-    root[pl.p] = (uint16_t)metas.size();
-    metas.push_back(M);
-  }
-  std::vector<unsigned char> blob;
-  auto put = [&](const void* src, size_t bytes) {
-    const size_t o = (blob.size() + 15) & ~(size_t)15;
-    blob.resize(o + bytes);
-    std::memcpy(blob.data() + o, src, bytes);
-    return (uint32_t)o;
-  };
-  pc.mark("res_slots");
-  put(root.data(), root.size() * 2);
-  const uint32_t o_meta = put(metas.data(), metas.size() * sizeof(LjMeta));
-  if (blob.size() > kLjLdsBytes) return;  // (the slots stay allocated with the snapshot)
-  // the closure join keeps the stage when it answers every root the labels answer (config 4's
-  // tuned path); the labels take it when they cover every closure-join root and more
-  bool covers = true, more = false;
-  for (uint32_t p = 0; p < nf; ++p) {
-    const bool in_cj = !ds.cj_host.empty() && p * 2 + 1 < ds.cj_host.size() &&
-                       reinterpret_cast<const uint16_t*>(ds.cj_host.data())[p] != 0xFFFFu;
-    const bool in_lj = root[p] != 0xFFFFu;
-    covers &= !in_cj || in_lj;
-    more |= in_lj && !in_cj;
-  }
-  ds.lj_preferred = covers && more;
-  ds.lj_dkey = std::move(dkey);
-  ds.lj_hgt = std::move(hkey);
-  ds.lj_users = n_users;
-  ds.lj_af = const_cast<uint32_t*>(af_dev);
-  ds.lj_afp = afp_dev;
-  ds.lj_afp_n = afp_dev ? (uint32_t)par.size() : 0u;
-  ds.lj_anc = anc_dev;
-  ds.lj_af_base = std::move(af_base);
-  ds.lj_af_rows = std::move(af_rows);
-  std::sort(dfeed_type.begin(), dfeed_type.end());
-  dfeed_type.erase(std::unique(dfeed_type.begin(), dfeed_type.end()), dfeed_type.end());
-  ds.lj_dtype = std::move(dfeed_type);
-  ds.lj_dov = nullptr;  // (a fresh set of dirty subjects: the tables are new)
-  for (const LabelPlan& pl : plans) ds.lj_cav |= pl.cav;
-  ds.lj_key = std::move(key);
-  ds.lj_host = std::move(blob);
-  ds.lj_o_meta = o_meta;
-  ds.lj_sw = sw;
-  if (pc.on) pc.line += " sw=" + std::to_string(sw) + " bits=" + std::to_string(bits) + " pack=" + (pack ? "24" : "32");
-  ds.lj_bits = bits;
 }
 
 // ---- the label join over a partitioned graph (partition.inc part_join_*) -----------------------

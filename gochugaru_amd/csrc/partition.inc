@@ -6,7 +6,7 @@
 //
 //   * the rows of the objects it owns, complete — what the level loop expands — except of the
 //     hub relations (group#member), whose tuples are kept by subject:
-//   * the schema's hub hierarchy (labels.inc partition_rules: the userset / wildcard tuples of
+//   * the schema's hub hierarchy (labels_build.inc partition_rules: the userset / wildcard tuples of
 //     the hub relations, group#member@group#member), replicated — the hierarchy labels;
 //   * the hub tuples of the subjects it owns (group#member@user:u, owner(u) = r) — their user
 //     slots, at part_local(u). A group's direct members live with the members' owners, not with
@@ -360,7 +360,7 @@ static PartState& part_bufs(Engine& e, Workspace& w, size_t n) {
   return p;
 }
 
-static LjTab lj_tab(const DeviceSnapshot& ds) { return LjTab{ds.d_lj, ds.n_fwd, ds.lj_o_meta}; }
+static LjTab lj_tab(const DeviceSnapshot& ds) { return LjTab{ds.d_lj, ds.n_fwd, ds.lj.o_meta}; }
 
 static void add_join_stats(Engine& e, size_t n, size_t n_left) {
   std::lock_guard<std::mutex> sl(e.stats_mu);
@@ -715,12 +715,12 @@ static void part_run(Engine& e, const Xport& X, const gck_item* d_items, size_t 
       // this rank's own records in place, the received ones after them
       auto decide = [&](const uint32_t* recs, size_t cnt) {
         if (!cnt) return;
-        if (ds.lj_bits == 24)
+        if (ds.lj.bits == 24)
           hipLaunchKernelGGL(k_pj_decide<24>, dim3(grid_for(cnt)), dim3(kBlock), 0, st, lj_tab(ds), d_items, (uint32_t)n,
-                             ds.lj_sw, W, recs, (uint32_t)cnt, nullptr, d_perm, d_err);
+                             ds.lj.sw, W, recs, (uint32_t)cnt, nullptr, d_perm, d_err);
         else
           hipLaunchKernelGGL(k_pj_decide<32>, dim3(grid_for(cnt)), dim3(kBlock), 0, st, lj_tab(ds), d_items, (uint32_t)n,
-                             ds.lj_sw, W, recs, (uint32_t)cnt, nullptr, d_perm, d_err);
+                             ds.lj.sw, W, recs, (uint32_t)cnt, nullptr, d_perm, d_err);
         HIP_OK(hipGetLastError());
       };
       if (prof) HIP_OK(hipEventRecord(w.pev[2], st));

@@ -447,7 +447,7 @@ def hub_arrow(seed, n_users=60, n_orgs=10, n_repos=50):
     """A hub relation (org#member: arrows point at it) whose rows are also read as an arrow's
     tupleset outside the hub (org#member_mgr = member->manager). A partitioned graph keeps a hub's
     direct tuples with their subjects' owners, so such a relation must not be a hub there
-    (labels.inc partition_rules)."""
+    (labels_build.inc partition_rules)."""
     rng = random.Random(seed)
     t = []
     for u in range(n_users):

@@ -1,4 +1,4 @@
-"""The label join (gochugaru_amd/csrc/labels.inc) against the oracle: hub hierarchies (nested
+"""The label join (gochugaru_amd/csrc/labels.inc, labels_build.inc) against the oracle: hub hierarchies (nested
 groups, teams inside organisations), resource-side flattening through arrow chains (folder
 forests), exclusion and intersection terms, wildcards, the extension records of resources whose
 grants do not fit a slot, cover lists of users in many groups, and what it must leave to the wave
@@ -125,7 +125,7 @@ def test_resources_at_the_budget_are_deferred():
 
 
 def test_cyclic_hierarchy_condensed():
-    """Cycles in the group hierarchy are condensed (labels.inc hier_scc); resources that reach a
+    """Cycles in the group hierarchy are condensed (labels_build.inc hier_scc); resources that reach a
     cycle sit at the depth budget and are deferred to the exact-depth path."""
     for seed in (1, 2):
         schema, tuples, checks = gen.cyclic(seed)
@@ -410,4 +410,81 @@ def test_direct_grant_churn_keeps_the_tables():
         bad = [(c, x, w, g) for c, x, w, g in zip(checks, ctxs, want, got) if w != g]
         assert not bad, (rev, bad[:10])
         assert st["label_checks"] >= 0.4 * len(checks), (rev, st["label_checks"])
+    e.close()
+
+
+# ---- builds that refuse: the checks go to the bundles, exactly ---------------------------------
+
+def _flat_docs(n_perms):
+    """One `doc` type with n_perms permissions pN = viewer + owner (each a label root), 20
+    documents, 10 users."""
+    rng = random.Random(21)
+    schema = ("definition user {}\ndefinition doc {\n  relation viewer: user\n  relation owner: user\n" +
+              "".join(f"  permission p{k} = viewer + owner\n" for k in range(n_perms)) + "}")
+    t = [f"doc:d{d}#owner@user:u{rng.randrange(10)}" for d in range(20)]
+    t += [f"doc:d{d}#viewer@user:u{rng.randrange(10)}" for d in range(20) for _ in range(2)]
+    checks = [f"doc:d{d}#p{k}@user:{u}" for k in range(n_perms) for d in range(20) for u in ("u1", "u4", "u7", "nobody")]
+    return schema, sorted(set(t)), checks
+
+
+def test_too_many_roots_for_the_lds_table():
+    """40 label roots: their LjMeta (64 B each) exceed the 2048-B root table the join keeps in
+    LDS, so the build refuses (at its plan stage) and every check is answered by the bundles; with
+    8 roots the tables are built and used."""
+    st, want = _run(*_flat_docs(40))
+    assert st["label_checks"] == 0, st["label_checks"]
+    assert any(w[0] == 2 for w in want) and any(w[0] == 1 for w in want)
+    st, _ = _run(*_flat_docs(8))
+    assert st["label_checks"] > 0, st["label_checks"]
+
+
+WILD_HUB = """
+definition user {}
+definition group { relation member: user | user:* | group#member }
+definition doc {
+  relation owner: user
+  relation viewer: user | group#member
+  permission view = viewer + owner
+}"""
+WILD_MEMBER = "group:g0#member@user:*"
+
+
+def _wild_hub_graph():
+    rng = random.Random(23)
+    t = [f"group:g{g}#member@group:g{rng.randrange(g)}#member" for g in range(1, 6)]
+    t += [f"group:g{g}#member@user:u{rng.randrange(10)}" for g in range(1, 6)]
+    t += [f"doc:d{d}#viewer@group:g{d % 6}#member" for d in range(20)]
+    t += [f"doc:d{d}#owner@user:u{rng.randrange(10)}" for d in range(20)]
+    checks = [f"doc:d{d}#view@user:{u}" for d in range(20) for u in ("u0", "u3", "u8", "nobody")]
+    return sorted(set(t)), checks
+
+
+def test_hub_listing_the_wildcard_is_not_labelled():
+    """group:g0#member@user:* under doc#viewer@group:g0#member: a hub that lists the wildcard holds
+    every subject, so the build refuses and the bundles answer (every user views g0's documents)."""
+    tuples, checks = _wild_hub_graph()
+    st, want = _run(WILD_HUB, sorted(tuples + [WILD_MEMBER]), checks)
+    assert st["label_checks"] == 0, st["label_checks"]
+    assert all(w[0] == 2 for c, w in zip(checks, want) if c.startswith("doc:d0#"))
+
+
+def test_refusal_after_a_snapshot_with_tables():
+    """A snapshot whose labels build, then a Watch batch that adds the wildcard member: the new
+    build refuses and leaves no tables behind (none adopted from the snapshot before it)."""
+    tuples, checks = _wild_hub_graph()
+    e = E.Engine()
+    e.load_schema(WILD_HUB)
+    e.load_snapshot_text(1, "\n".join(tuples))
+    items = e.make_items([parse_check(c) for c in checks])
+    for rev, cur in ((1, tuples), (2, sorted(tuples + [WILD_MEMBER]))):
+        if rev == 2:
+            e.apply_updates_text(rev, "TOUCH " + WILD_MEMBER)
+        ck = oracle_for(WILD_HUB, cur, now=gen.NOW_US / 1e6)
+        want = [ck.check(to_oracle_item(parse_check(c))) for c in checks]
+        e.reset_stats()
+        perm, err = e.check_bulk(items, now_us=gen.NOW_US)
+        got = [(int(p), int(x)) for p, x in zip(perm, err)]
+        assert got == want, rev
+        n = e.stats()["label_checks"]
+        assert (n > 0) if rev == 1 else (n == 0), (rev, n)
     e.close()
