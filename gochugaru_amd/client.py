@@ -28,7 +28,7 @@ from .consistency import Background, Context, Strategy
 from .engine import (CONSISTENCY_AT_LEAST, CONSISTENCY_FULL, CONSISTENCY_MIN_LATENCY,
                      CONSISTENCY_SNAPSHOT, ELLIPSIS, GCK_E_DEVICE, GCK_E_NOT_FOUND, GCK_E_REVISION,
                      ID_ABSENT, ID_WILDCARD, ITEM_ERROR_MESSAGES, PERM_HAS, REL_INVALID, TYPE_INVALID, Engine,
-                     GckError)
+                     GckError, shape_request, unpack_results)
 
 CHECK_ITER_CHUNK = 1000  # client/client.go:166
 
@@ -53,6 +53,16 @@ def WithOverlapRequired():
     """``client/client.go:84-86``."""
     def opt(c: "Client"):
         c.overlapRequired = True
+    return opt
+
+
+def WithCompactRequests():
+    """Check sends every request of at most 64 shapes — (resource type, permission, subject type,
+    subject relation, context slot) — as a shaped request (Engine.check_shaped: a shape table, one
+    index byte and one id pair per check in, 2-bit results out) instead of 20-B items. The
+    ``(results, err)`` it returns are the same."""
+    def opt(c: "Client"):
+        c.compactRequests = True
     return opt
 
 
@@ -112,6 +122,7 @@ class Client:
     def __init__(self, engine: Engine, *opts, chunk: int = 65536):
         self.engine = engine
         self.overlapRequired = False
+        self.compactRequests = False
         self.chunk = chunk
         for o in opts:
             o(self)
@@ -140,8 +151,20 @@ class Client:
                 # interned per attempt, like the server resolving names at evaluation time: an
                 # object a Watch batch created while this request waited is found on the retry
                 items, contexts = self.engine.make_request(rels)
-                return self.engine.check_bulk(items, requirement, revision, contexts=contexts)
+                shaped = shape_request(items) if self.compactRequests and len(items) else None
+                if shaped is None:
+                    return self.engine.check_bulk(items, requirement, revision, contexts=contexts)
+                words, errs, _ = self.engine.check_shaped(*shaped, requirement, revision, contexts=contexts)
+                return unpack_results(words, len(items)), errs
             perm, err = retryRetriableErrors(ctx or Background, attempt)
+            if err.dtype.names:  # a shaped request's error list: ascending (index, code) records
+                first = err[0] if len(err) else None
+                n_ok = int(first["index"]) if first is not None else len(perm)
+                results = [p == PERM_HAS for p in perm[:n_ok].tolist()]
+                if first is None:
+                    return results, None
+                e = int(first["code"])
+                return results, CheckItemError(ITEM_ERROR_MESSAGES.get(e, f"item error {e}"))
         except Exception as e:  # noqa: BLE001 — Go returns (nil, err)
             return None, e
         results: List[bool] = []

@@ -323,13 +323,33 @@ static void aql_put_extra(const AqlState& st, Workspace& w, const void* extra, s
   aql_hdp_flush(st);
 }
 
+// A shaped batch's table (closure.inc CjArgs::shapes) in the workspace's own block behind the
+// kernarg block — the same memory, written the same way: only the 16-B entries that differ from
+// what it holds (a caller's requests mostly repeat one table), then the HDP flush. The workspace
+// runs one batch at a time, so no kernel still reads the previous table.
+constexpr size_t kAqlShapesBytes = GCK_MAX_SHAPES * sizeof(gck_uniform);
+static_assert(sizeof(gck_uniform) == 16, "a shape is one 16-B entry");
+static void aql_put_shapes(const AqlState& st, Workspace& w, const gck_uniform* shapes, uint32_t n_shapes) {
+  static_assert(sizeof(w.shapes_shadow) == kAqlShapesBytes, "shape table shadow size");
+  auto* dst = static_cast<unsigned char*>(w.aql_shapes);
+  const auto* src = reinterpret_cast<const unsigned char*>(shapes);
+  bool wrote = false;
+  for (size_t o = 0; o < (size_t)n_shapes * 16; o += 16) {
+    if (std::memcmp(src + o, w.shapes_shadow + o, 16) == 0) continue;
+    std::memcpy(dst + o, src + o, 16);
+    std::memcpy(w.shapes_shadow + o, src + o, 16);
+    wrote = true;
+  }
+  if (wrote && w.aql_devargs) aql_hdp_flush(st);
+}
+
 static bool aql_workspace(AqlState& st, Workspace& w) {
   if (w.aql_kernarg) return true;
   void* p = nullptr;
   if (st.devargs) {  // a VRAM block the host may write (zeroed: a kernel reading it does nothing)
-    if (hsa_amd_memory_pool_allocate(st.pool, kAqlKernargBytes, 0, &p) == HSA_STATUS_SUCCESS) {
+    if (hsa_amd_memory_pool_allocate(st.pool, kAqlKernargBytes + kAqlShapesBytes, 0, &p) == HSA_STATUS_SUCCESS) {
       if (hsa_amd_agents_allow_access(1, &st.cpu, nullptr, p) == HSA_STATUS_SUCCESS) {
-        std::memset(p, 0, kAqlKernargBytes);
+        std::memset(p, 0, kAqlKernargBytes + kAqlShapesBytes);
         aql_hdp_flush(st);
         w.aql_devargs = true;
       } else {
@@ -339,8 +359,9 @@ static bool aql_workspace(AqlState& st, Workspace& w) {
     }
   }
   if (!p) {  // (no HDP flush register: pinned host memory, zeroed as the VRAM block is)
-    if (hipHostMalloc(&p, kAqlKernargBytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) return false;
-    std::memset(p, 0, kAqlKernargBytes);
+    if (hipHostMalloc(&p, kAqlKernargBytes + kAqlShapesBytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
+      return false;
+    std::memset(p, 0, kAqlKernargBytes + kAqlShapesBytes);
   }
   hsa_signal_t s;
   // (GCK_DEBUG_AQL_SIGNAL: a signal without the completion interrupt — the host only spins on it —
@@ -355,6 +376,8 @@ static bool aql_workspace(AqlState& st, Workspace& w) {
     return false;
   }
   w.aql_kernarg = p;
+  w.aql_shapes = static_cast<unsigned char*>(p) + kAqlKernargBytes;
+  std::memset(w.shapes_shadow, 0, sizeof(w.shapes_shadow));
   w.aql_signal = s.handle;
   return true;
 }
@@ -368,6 +391,7 @@ static void aql_workspace_free(Workspace& w) {
   if (w.aql_kernarg && w.aql_devargs) (void)hsa_amd_memory_pool_free(w.aql_kernarg);
   else if (w.aql_kernarg) (void)hipHostFree(w.aql_kernarg);
   w.aql_kernarg = nullptr;
+  w.aql_shapes = nullptr;
   w.aql_devargs = false;
   w.aql_queue = nullptr;
 }

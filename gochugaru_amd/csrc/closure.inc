@@ -119,15 +119,30 @@ struct CjArgs {
   gck_item* items_out;
   uint32_t pub_words, seq;
   uint32_t slot_limit;
-  uint32_t u_rp, u_ss, u_ctx;
   uint32_t n_desc;
-  uint32_t cold_pad[3];
+  // a shaped batch (gck_check_bulk_shaped; kCjShaped, with `pairs`): check k's header is
+  // shapes[shape_of[k]] — a table of n_shapes <= GCK_MAX_SHAPES 16-B entries in device-visible
+  // memory of the workspace, and one index byte per check beside the pairs. An index >= n_shapes is
+  // clamped before the lookup and fails the request through *bad_slot (the check's context slot
+  // reads as 0xFFFFFFFF there). The pointers lie over the header words a shaped batch does not use.
+  union {
+    struct {
+      uint32_t u_rp, u_ss, u_ctx;
+    };
+    struct {
+      const uint8_t* shape_of;
+      const gck_uniform* shapes;
+    };
+  };
+  uint32_t n_shapes;  // 0: not shaped
+  uint32_t cold_pad[1];
 };
 // CjArgs::mode beside kPubCoherent | kPubBySignal (engine.hip)
 constexpr uint32_t kCjUniform = 4u;   // pairs != null
 constexpr uint32_t kCjBadSlot = 8u;   // bad_slot != null
 constexpr uint32_t kCjSelfPub = 16u;  // h_out != null
 constexpr uint32_t kCjTimed = 32u;    // timing != null
+constexpr uint32_t kCjShaped = 64u;   // n_shapes != 0 (with kCjUniform)
 
 struct CjHot {  // the hot line as the kernel holds it (scalar registers)
   const gck_item* items;
@@ -157,7 +172,7 @@ static_assert((sizeof(Ctx) + kCjHotOff) % 64 == 0, "the hot line is one 64-B lin
 // the launch, the dispatch or the post).
 inline void cj_seal(CjArgs& j) {
   j.mode = (j.mode & (kPubCoherent | kPubBySignal)) | (j.pairs ? kCjUniform : 0u) | (j.bad_slot ? kCjBadSlot : 0u) |
-           (j.h_out ? kCjSelfPub : 0u) | (j.timing ? kCjTimed : 0u);
+           (j.h_out ? kCjSelfPub : 0u) | (j.timing ? kCjTimed : 0u) | (j.pairs && j.n_shapes ? kCjShaped : 0u);
 }
 // The staged bytes of a table of `bytes` bytes (its device buffer is allocated to this size).
 constexpr uint32_t cj_table_bytes(size_t bytes) { return (uint32_t)((bytes + 15) & ~(size_t)15); }
@@ -596,6 +611,21 @@ __device__ __forceinline__ uint32_t slot_decide_wave(const uint32_t (&w)[kUSlotW
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
+// A shaped batch's check (CjArgs::shapes): its table entry e (16 B: gck_uniform) and its id pair. `bad`:
+// its index byte was beyond the table (the entry is the clamped one) — the item then carries a
+// context slot no call has, which check_slots reports as the request's error.
+__device__ __forceinline__ gck_item shaped_item(const u32x4 e, bool bad, uint32_t res, uint32_t sub) {
+  return uniform_item(e.x, e.y, bad ? 0xFFFFFFFFu : e.z, res, sub);
+}
+// ... read again from global memory, by the rare check the join leaves to the bundle stages (the
+// index clamped as in the join; the request has failed already when it was out of range)
+__device__ __forceinline__ gck_item shaped_item_again(const uint8_t* shape_of, const gck_uniform* shapes, uint32_t n_shapes,
+                                                      uint32_t i, uint32_t res, uint32_t sub) {
+  const uint32_t sb = *(const GCK_GLOBAL uint8_t*)(shape_of + i);
+  const u32x4 e = *(const GCK_GLOBAL u32x4*)(shapes + min(sb, n_shapes - 1u));
+  return shaped_item(e, false, res, sub);
+}
+
 // slot lines are read once per check and never again by the batch: nontemporal loads
 // (tools/slot_probe: 8 % more random lines/s at three batches' worth of waves)
 __device__ __forceinline__ u32x4 slot_load(const GCK_GLOBAL u32x4* p) {
@@ -673,6 +703,22 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
       item_chunk.y = (uint32_t)(pr >> 32);
     }
   }
+  // a shaped batch: in the same round each check lane its index byte (32 consecutive bytes per
+  // wave: one request) and lane l < n_shapes entry l of the shape table (<= 1 KB, the same for
+  // every wave: L2-hot after the first). The entries go to the wave's own stage region, idle in
+  // this mode until the slot addresses: each lane then reads its entry by index from LDS — no
+  // dependent global round, no block barrier beyond the table's.
+  const bool shaped = (a.mode & kCjShaped) != 0u;
+  uint32_t n_shapes = 0;
+  u32x4 shape_ent{0u, 0u, 0u, 0u};
+  if (__builtin_expect(shaped, 0)) {
+    const auto cold = ax.cold();
+    const uint8_t* shape_of = cold->shape_of;
+    const gck_uniform* shapes = cold->shapes;
+    n_shapes = min(cold->n_shapes, (uint32_t)GCK_MAX_SHAPES);
+    if ((uint32_t)lane < CPW && w0 + (uint32_t)lane < a.n) item_chunk.z = *(const GCK_GLOBAL uint8_t*)(shape_of + w0 + (uint32_t)lane);
+    if ((uint32_t)lane < n_shapes) shape_ent = *(const GCK_GLOBAL u32x4*)(shapes + lane);
+  }
   // the table in 16-B chunks (table_bytes is a multiple of 16, and at most TAB: the launch picks
   // the variant), every load issued before the first LDS write: one L2 round trip for the whole
   // table instead of one per pass of a word-by-word loop
@@ -690,6 +736,8 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
       if (at < a.table_bytes && at < TAB) *reinterpret_cast<u32x4*>(&s_tab[at]) = tc[r];
     }
   }
+  // (after the table's loads were issued: the entries' wait is the table's)
+  if (__builtin_expect(shaped, 0) && (uint32_t)lane < n_shapes) *reinterpret_cast<u32x4*>(&s_item_w[lane * 4u]) = shape_ent;
   __syncthreads();
   const uint16_t* root = reinterpret_cast<const uint16_t*>(s_tab);
   const CjMeta* meta = reinterpret_cast<const CjMeta*>(s_tab + a.o_meta);
@@ -740,7 +788,13 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
   if (uni) {
     const auto cold = ax.cold();
     const uint32_t u_rp = cold->u_rp, u_ss = cold->u_ss, u_ctx = cold->u_ctx;
-    if (active) it = uniform_item(u_rp, u_ss, u_ctx, item_chunk.x, item_chunk.y);
+    if (__builtin_expect(shaped, 0)) {
+      // (the wave's own LDS writes above are visible: the table's barrier lies between)
+      const uint32_t sb = min(item_chunk.z, n_shapes - 1u);  // clamped before the lookup
+      if (active) it = shaped_item(*reinterpret_cast<const u32x4*>(&s_item_w[sb * 4u]), item_chunk.z >= n_shapes, item_chunk.x, item_chunk.y);
+    } else if (active) {
+      it = uniform_item(u_rp, u_ss, u_ctx, item_chunk.x, item_chunk.y);
+    }
   } else if (active) {
     uint32_t iw[5];
     for (uint32_t q = 0; q < 5u; ++q) iw[q] = s_item_w[lane * 5u + q];
@@ -1116,7 +1170,10 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
       if (left) cold->deferred[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
       if (left && uni) {  // the check's item where the bundle stages read it (its pair read again: rare)
         const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(cold->pairs + 2ull * i);
-        cold->items_out[i] = uniform_item(cold->u_rp, cold->u_ss, cold->u_ctx, (uint32_t)pr, (uint32_t)(pr >> 32));
+        if (shaped)
+          cold->items_out[i] = shaped_item_again(cold->shape_of, cold->shapes, n_shapes, i, (uint32_t)pr, (uint32_t)(pr >> 32));
+        else
+          cold->items_out[i] = uniform_item(cold->u_rp, cold->u_ss, cold->u_ctx, (uint32_t)pr, (uint32_t)(pr >> 32));
       }
     }
   }

@@ -248,6 +248,13 @@ struct Workspace {
   gck_item_error* u_errs = nullptr;             // submit_uniform: the caller's error list
   size_t u_err_cap = 0;
   size_t* u_n_errs = nullptr;
+  // ---- ... or shaped (gck_check_bulk_shaped / gck_check_submit_shaped): u_on as above, and -----
+  bool s_join = false;                          // the join reads the index bytes and the shape table too (with u_join)
+  uint32_t s_n_shapes = 0;
+  const uint8_t* s_shape_of = nullptr;          // the index bytes the join reads (caller's pinned buffer or staging)
+  size_t s_pos = 0;                             // the chunk's offset in its request (a bad index is reported request-global)
+  void* aql_shapes = nullptr;   // aql.inc: the shape table the join reads (GCK_MAX_SHAPES entries, memory as aql_kernarg)
+  alignas(16) unsigned char shapes_shadow[GCK_MAX_SHAPES * sizeof(gck_uniform)] = {};  // ... what it holds now
   void* aql_kernarg = nullptr;  // aql.inc: kernarg block of the dispatched join (pinned host memory, or VRAM)
   bool aql_devargs = false;     // ... in VRAM (aql.inc AqlState::devargs)
   uint64_t aql_signal = 0;      // aql.inc: its completion signal (hsa_signal_t handle)
@@ -2510,6 +2517,12 @@ static void slot_error(uint32_t i, uint32_t slot, uint32_t limit) {
                                           " beyond the " + std::to_string(limit) + " contexts given");
 }
 
+// ... and of a shaped request's index bytes (k: the check's position in the whole request)
+static void shape_index_error(size_t k, uint32_t index, uint32_t n_shapes) {
+  throw Error(GCK_E_INVALID_ARGUMENT, "shaped request: shape_of[" + std::to_string(k) + "] = " + std::to_string(index) +
+                                          " beyond the " + std::to_string(n_shapes) + " shapes given");
+}
+
 static void validate_slots(const gck_item* items, uint32_t n, uint32_t limit) {
   for (uint32_t i = 0; i < n; ++i)
     if (items[i].context_slot > limit) slot_error(i, items[i].context_slot, limit);
@@ -2579,6 +2592,11 @@ static void uniform_args(const Workspace& w, Args& j) {
   j.u_rp = w.u_rp;
   j.u_ss = w.u_ss;
   j.u_ctx = w.u_ctx;
+  if (w.s_join) {  // (a shaped batch: the index bytes and the table lie over the header words)
+    j.shape_of = w.s_shape_of;
+    j.shapes = static_cast<const gck_uniform*>(w.aql_shapes);
+    j.n_shapes = w.s_n_shapes;
+  }
   j.items = nullptr;
 }
 
@@ -2797,7 +2815,9 @@ static void closure_join_start(Engine& e, Workspace& w, const Route& r, const Ct
   if (ak && j.h_out)
     aql_summaries(w, cj_args.j.mode, cj_args.j.h_out, cj_args.j.done, cj_args.j.n_deferred, grid.x);
   // the resident join (resident.inc) takes the request without a dispatch of its own
-  const bool res_ok = ak && e.res && !r.timed && w.b_sum_blocks == grid.x && (cj_args.j.mode & kPubBySignal);
+  // (a shaped batch is dispatched: the running launch would read the workspace's shape table, which
+  // the host rewrites between requests, without a dispatch's acquire in between)
+  const bool res_ok = ak && e.res && !r.timed && w.b_sum_blocks == grid.x && (cj_args.j.mode & kPubBySignal) && !w.s_join;
   if (res_ok) {
     aql_after_build(e);
     res_post(e, w, cj_args.j, grid.x);
@@ -2897,6 +2917,8 @@ static float bundles_finish(Engine& e, Workspace& w) {
   w.ctr_clean = true;  // k_publish zeroed the device counters
   if (w.h_ctr->bad_slot) {  // (a zero-copy batch's join found a context slot out of range)
     const uint32_t i = 0xFFFFFFFFu - w.h_ctr->bad_slot;
+    // (a shaped batch's table was checked by the host: the join reports an index byte beyond it)
+    if (w.s_join) shape_index_error(w.s_pos + i, i < n ? w.s_shape_of[i] : 0u, w.s_n_shapes);
     slot_error(i, i < n ? d_items[i].context_slot : 0u, w.cav.n_given);
   }
   const bool profile = w.b_timed;
@@ -3254,8 +3276,10 @@ void host_free_all(Engine& e) {
 }
 
 static void submit_batch(Engine& e, Workspace& w, const gck_item* items, uint32_t n, int64_t now_us, uint8_t* perm,
-                         int32_t* err, hipStream_t st, bool host, bool own_stream = false, bool uniform_join = false) {
+                         int32_t* err, hipStream_t st, bool host, bool own_stream = false, bool uniform_join = false,
+                         bool shaped_join = false) {
   w.u_join = uniform_join;  // (the join's arguments: bundles_launch)
+  w.s_join = shaped_join;   // (with uniform_join)
   w.u_on = false;           // (submit_uniform sets it after this)
   w.b_own_stream = own_stream;
   w.b_n = n;
@@ -3277,7 +3301,7 @@ static void submit_batch(Engine& e, Workspace& w, const gck_item* items, uint32_
   // (GCK_AQL=0, a profiled batch): the DMA path below.
   w.b_copy_perm = nullptr;
   w.b_copy_err = nullptr;
-  w.b_validate = false;
+  w.b_validate = shaped_join;  // (its join reads the index bytes in place: a bad one lands in bad_slot)
   if (host && zero_copy_ok(e, w)) {
     // the join reads every item once, in place: it also checks the context slots (no host pass
     // over the items on the submitting thread)
@@ -3621,6 +3645,94 @@ static void uniform_errors(std::vector<gck_item_error>& errs, gck_item_error* ou
   const size_t m = std::min(cap, errs.size());
   if (m && out) std::memcpy(out, errs.data(), m * sizeof(gck_item_error));
   if (n_errs) *n_errs = errs.size();
+}
+
+// ---- shaped batches (include/gck.h gck_check_bulk_shaped, gck_check_submit_shaped) ------------
+// A table of shapes, one index byte per check and the id pairs in; the uniform request's words and
+// error list out (uniform_collect). Zero-copy under the uniform request's condition: the join reads
+// the pairs and the index bytes in place (or from the pinned staging after one host copy), the
+// table from the workspace's own block (aql.inc aql_put_shapes), and reports an index beyond the
+// table through the context-slot check's counter. Otherwise each check is expanded to its own item.
+// pos: the chunk's offset in the request.
+static void submit_shaped(Engine& e, Workspace& w, const gck_uniform* shapes, uint32_t n_shapes, const uint8_t* shape_of,
+                          const uint32_t* pairs, uint32_t n, int64_t now_us, unsigned long long* packed, size_t pos) {
+  w.s_pos = pos;
+  w.s_n_shapes = n_shapes;
+  if (zero_copy_ok(e, w) && w.aql_shapes) {
+    const size_t words = ((size_t)n + 31u) / 32u;
+    const bool pin_pairs = host_pinned(e, pairs, (size_t)n * 8u), pin_idx = host_pinned(e, shape_of, n);
+    const bool pin_out = host_pinned(e, packed, words * 8u);
+    // (the staging's item region holds 20 B per check: the pairs, then the index bytes)
+    unsigned char* stage = reinterpret_cast<unsigned char*>(w.h_items);
+    if (!pin_pairs) std::memcpy(stage, pairs, (size_t)n * 8u);
+    if (!pin_idx) std::memcpy(stage + (size_t)n * 8u, shape_of, n);
+    aql_put_shapes(*e.aql, w, shapes, n_shapes);
+    w.u_rp = w.u_ss = w.u_ctx = 0;
+    w.u_pairs = pin_pairs ? pairs : reinterpret_cast<const uint32_t*>(stage);
+    w.s_shape_of = pin_idx ? shape_of : stage + (size_t)n * 8u;
+    w.u_packed = pin_out ? packed : reinterpret_cast<unsigned long long*>(w.h_err);
+    submit_batch(e, w, w.d_items, n, now_us, w.d_perm, w.d_err, w.stream, false, true, true, true);
+    e.shaped_in_place.fetch_add(1, std::memory_order_relaxed);
+  } else {
+    w.u_items.resize(n);
+    for (uint32_t k = 0; k < n; ++k) {
+      if (shape_of[k] >= n_shapes) shape_index_error(pos + k, shape_of[k], n_shapes);
+      const gck_uniform& h = shapes[shape_of[k]];
+      gck_item& it = w.u_items[k];
+      it.resource_type = h.resource_type;
+      it.permission = h.permission;
+      it.resource_id = pairs[2 * (size_t)k];
+      it.subject_type = h.subject_type;
+      it.subject_relation = h.subject_relation;
+      it.subject_id = pairs[2 * (size_t)k + 1];
+      it.context_slot = h.context_slot;
+    }
+    w.u_perm.resize(n);
+    w.u_err.resize(n);
+    w.u_packed = nullptr;
+    submit_batch(e, w, w.u_items.data(), n, now_us, w.u_perm.data(), w.u_err.data(), nullptr, true);
+    e.shaped_expanded.fetch_add(1, std::memory_order_relaxed);
+  }
+  w.u_on = true;
+  w.u_out = packed;
+  w.u_ncj = 0;
+}
+
+void device_submit_shaped(Engine& e, Workspace* w, const gck_uniform* shapes, uint32_t n_shapes, const uint8_t* shape_of,
+                          const uint32_t* pairs, size_t n, int64_t now_us, uint64_t* packed, gck_item_error* errs,
+                          size_t cap, size_t* n_errs, CavCall cav) {
+  HIP_OK(hipSetDevice(e.device));
+  std::lock_guard<std::mutex> lk(w->m);
+  if (n > w->max_batch) throw Error(GCK_E_INVALID_ARGUMENT, "submitted batch above max_batch");
+  stage_caveats(*w, std::move(cav), w->stream);
+  if (now_us == 0) now_us = wall_now_us();
+  submit_shaped(e, *w, shapes, n_shapes, shape_of, pairs, (uint32_t)n, now_us,
+                reinterpret_cast<unsigned long long*>(packed), 0);
+  w->u_errs = errs;
+  w->u_err_cap = cap;
+  w->u_n_errs = n_errs;
+}
+
+// Synchronous: chunks as device_check_uniform's (multiples of 32 checks); chunk inputs are
+// shape_of + pos and pairs + 2 pos.
+void device_check_shaped(Engine& e, Workspace* w0, Workspace* w1, const gck_uniform* shapes, uint32_t n_shapes,
+                         const uint8_t* shape_of, const uint32_t* pairs, size_t n, int64_t now_us, uint64_t* packed,
+                         gck_item_error* out_errs, size_t cap, size_t* n_errs, const CavCall& cav) {
+  HIP_OK(hipSetDevice(e.device));
+  if (now_us == 0) now_us = wall_now_us();
+  const size_t mb = w0->max_batch >= 32 ? (w0->max_batch & ~(size_t)31) : w0->max_batch;
+  if (n > mb && mb % 32 != 0) throw Error(GCK_E_CAPACITY, "a shaped request above max_batch needs max_batch >= 32");
+  std::vector<gck_item_error> errs;
+  size_t pos_of[2] = {0, 0};
+  run_chunks(
+      e, w0, w1, n, mb, cav,
+      [&](Workspace& w, size_t pos, uint32_t len) {
+        pos_of[&w == w0 ? 0 : 1] = pos;
+        submit_shaped(e, w, shapes, n_shapes, shape_of + pos, pairs + 2 * pos, len, now_us,
+                      reinterpret_cast<unsigned long long*>(packed + pos / 32), pos);
+      },
+      [&](Workspace& w) { uniform_collect(w, (uint32_t)pos_of[&w == w0 ? 0 : 1], errs); });
+  uniform_errors(errs, out_errs, cap, n_errs);
 }
 
 void device_submit_uniform(Engine& e, Workspace* w, const gck_uniform& h, const uint32_t* pairs, size_t n,

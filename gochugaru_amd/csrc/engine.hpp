@@ -275,6 +275,8 @@ struct Engine {
   std::unordered_map<void*, size_t> recyclable;
   size_t recycle_bytes = 0;
   gck_stats stats{};
+  // gck_shaped_stats: shaped requests (chunks) whose join read them in place / expanded to items
+  std::atomic<uint64_t> shaped_in_place{0}, shaped_expanded{0};
   // batches to come that chain the wave bundles behind the join in stage A (engine.hip
   // bundles_launch): reset to 16 by a batch whose join left kChainLeftovers or more, counted down by
   // one that left fewer
@@ -397,6 +399,15 @@ void device_check_uniform(Engine& e, Workspace* w0, Workspace* w1, const gck_uni
 void device_submit_uniform(Engine& e, Workspace* w, const gck_uniform& h, const uint32_t* pairs, size_t n,
                            int64_t now_us, uint64_t* packed, gck_item_error* errs, size_t cap, size_t* n_errs,
                            CavCall cav);
+// Shaped requests (gck_check_bulk_shaped / gck_check_submit_shaped): a table of n_shapes headers
+// (copied into the workspace by the submit), an index byte per check and the id pairs in; the
+// outputs are the uniform request's.
+void device_check_shaped(Engine& e, Workspace* w0, Workspace* w1, const gck_uniform* shapes, uint32_t n_shapes,
+                         const uint8_t* shape_of, const uint32_t* pairs, size_t n, int64_t now_us, uint64_t* packed,
+                         gck_item_error* errs, size_t cap, size_t* n_errs, const CavCall& cav);
+void device_submit_shaped(Engine& e, Workspace* w, const gck_uniform* shapes, uint32_t n_shapes, const uint8_t* shape_of,
+                          const uint32_t* pairs, size_t n, int64_t now_us, uint64_t* packed, gck_item_error* errs,
+                          size_t cap, size_t* n_errs, CavCall cav);
 // Pinned host buffers (gck_host_alloc): a host batch whose items / results live in one is
 // copied by DMA directly, without the workspace's staging copy.
 void* host_alloc(Engine& e, size_t bytes);

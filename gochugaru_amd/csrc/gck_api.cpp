@@ -1143,6 +1143,110 @@ int gck_check_submit_uniform(gck_engine* ge, const gck_consistency* cs, const gc
   });
 }
 
+// A shaped request's table against the call (include/gck.h gck_check_bulk_shaped): every entry is
+// checked here, once; the index bytes by whoever reads them (the join in place, or the expansion).
+static void check_shapes(const gck_uniform* shapes, size_t n_shapes, size_t n_contexts) {
+  REQUIRE(n_shapes >= 1 && n_shapes <= GCK_MAX_SHAPES, GCK_E_INVALID_ARGUMENT,
+          "shaped request: n_shapes " + std::to_string(n_shapes) + " outside 1.." + std::to_string(GCK_MAX_SHAPES));
+  REQUIRE(shapes, GCK_E_INVALID_ARGUMENT, "null shape table");
+  for (size_t s = 0; s < n_shapes; ++s) {
+    REQUIRE(shapes[s].context_slot <= n_contexts, GCK_E_INVALID_ARGUMENT,
+            "shape " + std::to_string(s) + ": context_slot " + std::to_string(shapes[s].context_slot) + " beyond the " +
+                std::to_string(n_contexts) + " contexts given");
+    REQUIRE(shapes[s].reserved == 0, GCK_E_INVALID_ARGUMENT, "shape " + std::to_string(s) + ": reserved must be 0");
+  }
+}
+
+int gck_check_bulk_shaped(gck_engine* ge, const gck_consistency* cs, const gck_uniform* shapes, size_t n_shapes,
+                          const uint8_t* shape_of, const uint32_t* pairs, size_t n, const char* const* contexts,
+                          const size_t* context_lens, size_t n_contexts, int64_t now_us, uint64_t* out_packed,
+                          gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs, uint64_t* out_revision) {
+  return guard([&] {
+    Engine& e = need(ge);
+    check_shapes(shapes, n_shapes, n_contexts);
+    REQUIRE(n == 0 || (shape_of && pairs && out_packed), GCK_E_INVALID_ARGUMENT, "null buffers");
+    REQUIRE(err_cap == 0 || out_errs, GCK_E_INVALID_ARGUMENT, "null error list");
+    if (out_n_errs) *out_n_errs = 0;
+    if (n == 0) {
+      std::shared_lock<std::shared_mutex> lk(e.mu);
+      check_request(e, cs, nullptr, 0, true, contexts, context_lens, n_contexts);
+      if (out_revision) *out_revision = e.revision;
+      return;
+    }
+    precheck(e);
+    const size_t mb = e.cfg.max_batch ? e.cfg.max_batch : 65536;
+    Workspace* ws[2] = {nullptr, nullptr};
+    acquire_ws_n(e, n > (mb & ~(size_t)31) ? 2 : 1, ws);
+    struct Release {
+      Engine& e;
+      Workspace** ws;
+      ~Release() {
+        release_ws(e, ws[0]);
+        if (ws[1] && ws[1] != ws[0]) release_ws(e, ws[1]);
+      }
+    } rel{e, ws};
+    std::shared_lock<std::shared_mutex> lk(e.mu);
+    check_request(e, cs, nullptr, n, true, contexts, context_lens, n_contexts);
+    const CavCall cav = caveat_call(e, contexts, context_lens, n_contexts);
+    const uint64_t rev = e.revision;
+    device_check_shaped(e, ws[0], ws[1], shapes, (uint32_t)n_shapes, shape_of, pairs, n, now_us, out_packed, out_errs,
+                        err_cap, out_n_errs, cav);
+    if (out_revision) *out_revision = rev;
+  });
+}
+
+int gck_check_submit_shaped(gck_engine* ge, const gck_consistency* cs, const gck_uniform* shapes, size_t n_shapes,
+                            const uint8_t* shape_of, const uint32_t* pairs, size_t n, const char* const* contexts,
+                            const size_t* context_lens, size_t n_contexts, int64_t now_us, uint64_t* out_packed,
+                            gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs, gck_batch** out) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    check_shapes(shapes, n_shapes, n_contexts);
+    REQUIRE(n == 0 || (shape_of && pairs && out_packed), GCK_E_INVALID_ARGUMENT, "null buffers");
+    REQUIRE(err_cap == 0 || out_errs, GCK_E_INVALID_ARGUMENT, "null error list");
+    if (out_n_errs) *out_n_errs = 0;
+    auto* b = new gck_batch();
+    if (n == 0) {
+      std::shared_lock<std::shared_mutex> lk(e.mu);
+      try {
+        check_request(e, cs, nullptr, 0, true, contexts, context_lens, n_contexts);
+        b->revision = e.revision;
+      } catch (...) {
+        delete b;
+        throw;
+      }
+      *out = b;
+      return;
+    }
+    precheck(e);
+    Workspace* w = acquire_ws(e);
+    try {
+      std::shared_lock<std::shared_mutex> lk(e.mu);
+      check_request(e, cs, nullptr, n, true, contexts, context_lens, n_contexts);
+      b->revision = e.revision;
+      device_submit_shaped(e, w, shapes, (uint32_t)n_shapes, shape_of, pairs, n, now_us, out_packed, out_errs, err_cap,
+                           out_n_errs, caveat_call(e, contexts, context_lens, n_contexts));
+    } catch (...) {
+      release_ws(e, w);
+      delete b;
+      throw;
+    }
+    b->w = w;
+    *out = b;
+  });
+}
+
+int gck_shaped_stats(gck_engine* ge, uint64_t out[2]) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    out[0] = e.shaped_in_place.load(std::memory_order_relaxed);
+    out[1] = e.shaped_expanded.load(std::memory_order_relaxed);
+  });
+}
+
 int gck_host_alloc(gck_engine* ge, size_t bytes, void** out) {
   return guard([&] {
     Engine& e = need(ge);

@@ -117,6 +117,7 @@ struct LjArgs {
   // host items read in place: the request check of their context slots (CjArgs::bad_slot)
   unsigned* bad_slot;
   uint32_t slot_limit;
+  uint32_t n_shapes;  // a shaped batch (below): the table's entries; 0: not shaped
   // the dirty subjects' changed objects (kDovWords per subject; null: a dirty subject defers)
   const uint32_t* dov;
   unsigned long long* timing;  // GCK_DEBUG_TIMING (TIMING=1 builds): kLjTimingWords per wave
@@ -124,7 +125,17 @@ struct LjArgs {
   const uint32_t* pairs;
   unsigned long long* out_packed;
   gck_item* items_out;
-  uint32_t u_rp, u_ss, u_ctx;
+  // ... or a shaped batch (closure.inc CjArgs::shapes; n_shapes != 0, with `pairs`): the index bytes
+  // and the table lie over the header words, which it does not use
+  union {
+    struct {
+      uint32_t u_rp, u_ss, u_ctx;
+    };
+    struct {
+      const uint8_t* shape_of;
+      const gck_uniform* shapes;
+    };
+  };
   // the chain walk of a dirty subject's overlay hit (LjMeta::chain): the current revision's CSRs
   // and the forest's parent edges (LjTables::afp: tupleset CSR << 32 | parent's index)
   const DevCSR* csrs;
@@ -717,8 +728,22 @@ __global__ void __launch_bounds__(kBlock) k_label_join(LjArgs a) {
     item_chunk.x = (uint32_t)pr;
     item_chunk.y = (uint32_t)(pr >> 32);
   }
+  // a shaped batch (closure.inc cj_block): the lane's index byte, and entry l of the shape table by
+  // lane l < n_shapes, in the same round; the entries are staged in the wave's own stage region
+  // (idle in this mode until the slots) and read by index after the table's barrier
+  const bool shaped = uni && a.n_shapes != 0u;
+  const uint32_t n_shapes = min(a.n_shapes, (uint32_t)GCK_MAX_SHAPES);
+  static_assert(CPW * kStride >= GCK_MAX_SHAPES * 4u, "the stage region holds the shape table");
+  u32x4 shape_ent{0u, 0u, 0u, 0u};
+  if (__builtin_expect(shaped, 0)) {
+    if ((threadIdx.x & 63u) < CPW && w0 + (threadIdx.x & 63u) < a.n)
+      item_chunk.z = *(const GCK_GLOBAL uint8_t*)(a.shape_of + w0 + (threadIdx.x & 63u));
+    if ((threadIdx.x & 63u) < n_shapes) shape_ent = *(const GCK_GLOBAL u32x4*)(a.shapes + (threadIdx.x & 63u));
+  }
   for (uint32_t k = threadIdx.x; k < a.table_bytes / 4; k += kBlock)
     reinterpret_cast<uint32_t*>(s_tab)[k] = gptr(reinterpret_cast<const uint32_t*>(a.table))[k];
+  if (__builtin_expect(shaped, 0) && (threadIdx.x & 63u) < n_shapes)
+    *reinterpret_cast<u32x4*>(&s_stage[threadIdx.x >> 6][(threadIdx.x & 63u) * 4u]) = shape_ent;
   uint32_t cl_nctx = 0, cl_ndist = 0;
   if constexpr (CL) {  // (the launcher checked the sizes against kLjCav*)
     const Ctx& c = *a.cx;
@@ -752,7 +777,12 @@ __global__ void __launch_bounds__(kBlock) k_label_join(LjArgs a) {
   lds_wave_fence();
   gck_item it{};
   if (active && uni) {
-    it = uniform_item(a.u_rp, a.u_ss, a.u_ctx, item_chunk.x, item_chunk.y);
+    if (__builtin_expect(shaped, 0)) {
+      const uint32_t sb = min(item_chunk.z, n_shapes - 1u);  // clamped before the lookup
+      it = shaped_item(*reinterpret_cast<const u32x4*>(&stage[sb * 4u]), item_chunk.z >= n_shapes, item_chunk.x, item_chunk.y);
+    } else {
+      it = uniform_item(a.u_rp, a.u_ss, a.u_ctx, item_chunk.x, item_chunk.y);
+    }
     if (a.cx) gptr_w(a.cx->cav_flag)[i] = 0;
   } else if (active) {
     uint32_t iw[5];
@@ -1028,7 +1058,8 @@ __global__ void __launch_bounds__(kBlock) k_label_join(LjArgs a) {
   if (active && !res) a.deferred[at] = i;
   if (active && !res && uni) {  // the check's item where the bundle stages read it (its pair read again)
     const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(a.pairs + 2ull * i);
-    a.items_out[i] = uniform_item(a.u_rp, a.u_ss, a.u_ctx, (uint32_t)pr, (uint32_t)(pr >> 32));
+    if (shaped) a.items_out[i] = shaped_item_again(a.shape_of, a.shapes, n_shapes, i, (uint32_t)pr, (uint32_t)(pr >> 32));
+    else a.items_out[i] = uniform_item(a.u_rp, a.u_ss, a.u_ctx, (uint32_t)pr, (uint32_t)(pr >> 32));
   }
   if (a.coherent & kPubBySignal) {  // (closure.inc block_summary)
     const uint32_t nd = (uint32_t)__popcll(__ballot(active && !res));

@@ -150,6 +150,43 @@ def unpack_results(words: np.ndarray, n: int) -> np.ndarray:
     return four[:n].astype(np.uint8)
 
 
+MAX_SHAPES = 64  # GCK_MAX_SHAPES
+_SHAPE_FIELDS = ("resource_type", "permission", "subject_type", "subject_relation", "context_slot")
+
+
+def _shape_table(shapes):
+    """A ctypes array of gck_uniform from (resource_type, permission, subject_type,
+    subject_relation[, context_slot[, reserved]]) tuples (or Uniform structures)."""
+    rows = [h if isinstance(h, Uniform) else
+            Uniform(*[int(x) for x in h[:4]], int(h[4]) if len(h) > 4 else 0, int(h[5]) if len(h) > 5 else 0)
+            for h in shapes]
+    return (Uniform * max(1, len(rows)))(*rows), len(rows)
+
+
+def shape_request(items: np.ndarray):
+    """A request's items as a shaped request (gck_check_bulk_shaped): (shapes, shape_of, pairs) —
+    the distinct (resource type, permission, subject type, subject relation, context slot) tuples
+    in first-seen order, each check's index into them (u8) and its (resource id, subject id) pair
+    ((n, 2) u32). None when the items hold more than MAX_SHAPES shapes."""
+    items = np.ascontiguousarray(items, dtype=ITEM_DTYPE)
+    n = len(items)
+    pairs = np.empty((n, 2), dtype=np.uint32)
+    pairs[:, 0] = items["resource_id"]
+    pairs[:, 1] = items["subject_id"]
+    key = np.zeros(n, dtype=[(f, "<u4") for f in _SHAPE_FIELDS])
+    for f in _SHAPE_FIELDS:
+        key[f] = items[f]
+    uniq, first, inv = np.unique(key, return_index=True, return_inverse=True)
+    if len(uniq) > MAX_SHAPES:
+        return None
+    order = np.argsort(first, kind="stable")      # sorted-unique position -> first-seen rank
+    rank = np.empty(len(uniq), dtype=np.int64)
+    rank[order] = np.arange(len(uniq))
+    shapes = [tuple(int(x) for x in uniq[j]) for j in order]
+    shape_of = rank[inv.reshape(-1)].astype(np.uint8)
+    return shapes, shape_of, pairs
+
+
 # symbol -> (restype, argtypes); the ABI test checks this list against include/gck.h
 _P = C.c_void_p
 
@@ -219,6 +256,13 @@ _SIGS = {
     "gck_check_submit_uniform": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), _P, C.c_size_t,
                                            C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int64, _P,
                                            _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_P)]),
+    "gck_check_bulk_shaped": (C.c_int, [_P, C.POINTER(_Consistency), _P, C.c_size_t, _P, _P, C.c_size_t,
+                                        C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int64, _P, _P,
+                                        C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    "gck_check_submit_shaped": (C.c_int, [_P, C.POINTER(_Consistency), _P, C.c_size_t, _P, _P, C.c_size_t,
+                                          C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int64, _P,
+                                          _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_P)]),
+    "gck_shaped_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "gck_host_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "gck_host_free": (C.c_int, [_P, _P]),
     "gck_last_stats": (C.c_int, [_P, C.POINTER(_Stats)]),
@@ -314,6 +358,10 @@ def _driver():
         d.gckd_run_uniform.argtypes = [C.c_void_p, C.c_void_p, _P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
                                        C.c_int64, C.POINTER(C.c_double)]
+        d.gckd_run_shaped.restype = C.c_int
+        d.gckd_run_shaped.argtypes = [C.c_void_p, C.c_void_p, _P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_void_p, C.c_uint32, C.c_int64, C.POINTER(C.c_double)]
         d.gckd_set_trace.restype = None
         d.gckd_set_trace.argtypes = [C.c_void_p, C.c_size_t]
         _DRIVER = d
@@ -686,6 +734,66 @@ class Engine:
         k = len(pairs)
         return self.prepare_uniform([header] * k, pairs, [n] * k, packed, errs, err_cap, depth, now_us).run()
 
+    def check_shaped(self, shapes, shape_of: np.ndarray, pairs: np.ndarray,
+                     requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                     contexts: Optional[Sequence] = None, out_packed: Optional[np.ndarray] = None,
+                     out_errs: Optional[np.ndarray] = None):
+        """A shaped request (gck_check_bulk_shaped): `shapes` = up to MAX_SHAPES headers as
+        check_uniform takes one, `shape_of` = n u8 indices into them, `pairs` = (n, 2) u32. Returns
+        what check_uniform returns. Pinned arrays (host_array) are read and written in place."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        shape_of = np.ascontiguousarray(shape_of, dtype=np.uint8).reshape(-1)
+        n = len(pairs)
+        if len(shape_of) != n:
+            raise ValueError("shape_of and pairs differ in length")
+        words = out_packed if out_packed is not None else np.zeros((n + 31) // 32, dtype=np.uint64)
+        errs = out_errs if out_errs is not None else np.zeros(n, dtype=ITEM_ERROR_DTYPE)
+        cs = _Consistency(requirement, 0, revision)
+        ctx_arr, ctx_lens, n_ctx = _context_arrays(contexts)
+        table, n_shapes = _shape_table(shapes)
+        n_errs = C.c_size_t(0)
+        rev = C.c_uint64(0)
+        _check(self._lib.gck_check_bulk_shaped(self._h, C.byref(cs), C.addressof(table), n_shapes,
+                                               shape_of.ctypes.data if n else None, pairs.ctypes.data if n else None,
+                                               n, ctx_arr, ctx_lens, n_ctx, now_us, words.ctypes.data if n else None,
+                                               errs.ctypes.data if len(errs) else None, len(errs), C.byref(n_errs),
+                                               C.byref(rev)))
+        return words, errs[:min(n_errs.value, len(errs))].copy(), rev.value
+
+    def submit_shaped(self, shapes, shape_of: np.ndarray, pairs: np.ndarray, out_packed: np.ndarray,
+                      out_errs: np.ndarray, requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0,
+                      now_us: int = 0, contexts: Optional[Sequence] = None) -> "ShapedBatch":
+        """gck_check_submit_shaped: the results land in out_packed / out_errs at wait(). `shape_of`
+        (u8) and `pairs` (u32) are used as they are (contiguous arrays) and kept until the wait."""
+        n = len(pairs)
+        if shape_of.dtype != np.uint8 or pairs.dtype != np.uint32 or len(shape_of) != n:
+            raise ValueError("submit_shaped takes u8 shape_of and u32 pairs of one length")
+        cs = _Consistency(requirement, 0, revision)
+        ctx_arr, ctx_lens, n_ctx = _context_arrays(contexts)
+        table, n_shapes = _shape_table(shapes)
+        b = ShapedBatch(self, (table, shape_of), pairs, out_packed, out_errs)
+        _check(self._lib.gck_check_submit_shaped(self._h, C.byref(cs), C.addressof(table), n_shapes,
+                                                 shape_of.ctypes.data if n else None, pairs.ctypes.data if n else None,
+                                                 n, ctx_arr, ctx_lens, n_ctx, now_us,
+                                                 out_packed.ctypes.data if n else None,
+                                                 out_errs.ctypes.data if len(out_errs) else None, len(out_errs),
+                                                 C.byref(b._n_errs), C.byref(b._h)))
+        return b
+
+    def prepare_shaped(self, shapes, shape_of, pairs, ns, packed, errs, err_cap: int, depth: int,
+                       now_us: int = 0) -> "PreparedShaped":
+        """The compiled submit/wait loop over shaped requests (libgck_driver.so gckd_run_shaped):
+        request k = the table shapes[k] (a list of headers) and host pointers shape_of[k], pairs[k]
+        (ns[k] checks), packed[k], errs[k] (err_cap records), `depth` in flight."""
+        return PreparedShaped(self, shapes, shape_of, pairs, ns, packed, errs, err_cap, depth, now_us)
+
+    def shaped_stats(self) -> Tuple[int, int]:
+        """gck_shaped_stats: shaped requests (chunks) the join read in place, and those expanded to
+        items on the host, since the engine was created."""
+        out = (C.c_uint64 * 2)()
+        _check(self._lib.gck_shaped_stats(self._h, out))
+        return int(out[0]), int(out[1])
+
     def check_bulk_device(self, d_items: int, n: int, d_perm: int, d_err: int,
                           stream: Optional[int] = None, now_us: int = 0,
                           contexts: Optional[Sequence] = None):
@@ -1013,6 +1121,34 @@ class PreparedUniform:
         return self._secs.value
 
 
+class PreparedShaped:
+    """A compiled submit/wait loop over shaped requests with its argument arrays built
+    (Engine.prepare_shaped)."""
+
+    def __init__(self, engine, shapes, shape_of, pairs, ns, packed, errs, err_cap, depth, now_us):
+        arr = lambda xs: (C.c_uint64 * max(1, len(xs)))(*[int(x) for x in xs])
+        self._e, self._k, self._depth, self._now, self._cap = engine, len(pairs), depth, now_us, err_cap
+        self._tables = [_shape_table(t) for t in shapes]
+        self._shapes = arr([C.addressof(t) for t, _ in self._tables])
+        self._n_shapes = arr([m for _, m in self._tables])
+        self._shape_of, self._pairs, self._ns = arr(shape_of), arr(pairs), arr(ns)
+        self._packed, self._errs = arr(packed), arr(errs)
+        self.n_errs = (C.c_size_t * max(1, len(pairs)))()
+        self._cs = _Consistency(CONSISTENCY_MIN_LATENCY, 0, 0)
+        self._drv = _driver()
+        self._submit = C.cast(engine._lib.gck_check_submit_shaped, C.c_void_p)
+        self._wait = C.cast(engine._lib.gck_check_wait, C.c_void_p)
+        self._secs = C.c_double(0.0)
+
+    def run(self) -> float:
+        """Runs the loop; returns its wall time in seconds (first submit to last wait)."""
+        _check(self._drv.gckd_run_shaped(self._submit, self._wait, self._e._h, C.byref(self._cs), self._k,
+                                         self._shapes, self._n_shapes, self._shape_of, self._pairs, self._ns,
+                                         self._packed, self._errs, self._cap, self.n_errs, self._depth, self._now,
+                                         C.byref(self._secs)))
+        return self._secs.value
+
+
 class Batch:
     """A submitted batch (gck_batch): wait() completes it exactly once."""
 
@@ -1062,6 +1198,11 @@ class UniformBatch:
             self.wait()
         except Exception:
             pass
+
+
+class ShapedBatch(UniformBatch):
+    """A submitted shaped request (gck_check_submit_shaped): as UniformBatch; it keeps the shape
+    table and the index bytes alive until the wait."""
 
 
 def _context_json(ctx) -> str:

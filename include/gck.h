@@ -45,6 +45,9 @@
  *       CheckBulkPermissionsRequestItem per relationship, all of one resource type, permission,
  *       subject type and subject relation) as one header and 8-byte (resource id, subject id)
  *       pairs, answered as a packed 2-bit Permissionship plane plus a sparse per-item error list.
+ *   gck_check_bulk_shaped / gck_check_submit_shaped
+ *       any request of that loop that mixes at most GCK_MAX_SHAPES shapes check by check: a table
+ *       of headers, one table index byte and one id pair per check (9 bytes), answered the same way.
  *
  * Ownership: all inputs and outputs are caller-allocated; the engine never retains a caller
  * pointer after a call returns, except that gck_check_submit keeps the output pointers (and, for
@@ -437,6 +440,38 @@ int gck_check_submit_uniform(gck_engine* e, const gck_consistency* cs, const gck
                              size_t n, const char* const* contexts, const size_t* context_lens, size_t n_contexts,
                              int64_t now_us, uint64_t* out_packed, gck_item_error* out_errs, size_t err_cap,
                              size_t* out_n_errs, gck_batch** out);
+
+/* ---- shaped requests (ABI 13, additive) ----------------------------------------------
+ * A request that mixes permissions, resource types, subject kinds or context slots check by check
+ * — what Client.Check sends for arbitrary relationships — travels as a small table of shapes
+ * (gck_uniform headers; 1..GCK_MAX_SHAPES entries, which may repeat), one table index byte per
+ * check and the (resource id, subject id) pairs: 9 bytes per check in and 1/4 byte out, whatever
+ * the order of the checks. Check k is (shapes[shape_of[k]], pairs[2k], pairs[2k + 1]). Results are
+ * the uniform call's: the packed 2-bit words and the ascending (index, GCK_ITEM_*) error records;
+ * semantics, consistency and request errors are gck_check_bulk_at's. GCK_E_INVALID_ARGUMENT for
+ * n_shapes outside 1..GCK_MAX_SHAPES, a shape whose context_slot exceeds n_contexts or whose
+ * `reserved` is not 0, null buffers, and a shape_of[k] >= n_shapes (the message names the smallest
+ * such k of the request; out_packed may then be partly written).
+ * Lifetimes: `shapes` is copied by the call and need not outlive it (the submit call included);
+ * `shape_of`, `pairs` and the outputs follow the uniform rule — valid until the synchronous call
+ * returns, or until the wait of a submitted batch returns. shape_of, pairs and out_packed in
+ * gck_host_alloc memory are read and written in place by the kernels. */
+#define GCK_MAX_SHAPES 64
+int gck_check_bulk_shaped(gck_engine* e, const gck_consistency* cs, const gck_uniform* shapes, size_t n_shapes,
+                          const uint8_t* shape_of, const uint32_t* pairs, size_t n, const char* const* contexts,
+                          const size_t* context_lens, size_t n_contexts, int64_t now_us, uint64_t* out_packed,
+                          gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs, uint64_t* out_revision);
+/* The same as an asynchronous batch (n <= max_batch): completed by gck_check_wait or
+ * gck_check_wait_at, which write out_packed, out_errs and *out_n_errs (and report a bad shape
+ * index found by the kernel). */
+int gck_check_submit_shaped(gck_engine* e, const gck_consistency* cs, const gck_uniform* shapes, size_t n_shapes,
+                            const uint8_t* shape_of, const uint32_t* pairs, size_t n, const char* const* contexts,
+                            const size_t* context_lens, size_t n_contexts, int64_t now_us, uint64_t* out_packed,
+                            gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs, gck_batch** out);
+/* Since the engine was created: out[0] = shaped requests (chunks of max_batch) whose join read the
+ * request in place, out[1] = those expanded to items on the host (check contexts, profiling, no
+ * one-round join). */
+int gck_shaped_stats(gck_engine* e, uint64_t out[2]);
 
 /* ---- lookups (Client.LookupResources / LookupSubjects, client/client.go:508-599) -------- */
 /* Ids of the `resource_type` objects on which the subject has `permission` — HAS or CONDITIONAL,
