@@ -195,6 +195,36 @@ struct DeltaHint {
   std::vector<Users> users;
 };
 
+// The batch in flight as one chunk of a compact request (engine.hpp CompactReq; submit_compact):
+// what its join reads and writes when it runs in place, what the wait packs, patches and lists
+// (uniform_collect). CompactRun is a batch's own part: submit_batch takes it whole and end_batch
+// clears it; the scratch vectors of the expanded form keep their capacity across batches.
+struct CompactRun {
+  // not a compact request's batch / expanded to items, run as a host batch / read in place: the
+  // join reads the pairs and writes the packed words itself
+  enum Mode : uint8_t { kOff, kExpanded, kInPlace } mode = kOff;
+  bool indexed = false;                      // the request has index bytes (shaped; else uniform)
+  uint32_t rp = 0, ss = 0, ctx = 0;          // in place, uniform: the header (closure.inc CjArgs::u_rp ...)
+  uint32_t n_shapes = 0;                     // in place, shaped: the table's entries (the table: Workspace::aql_shapes)
+  const uint8_t* shape_of = nullptr;         // ... and the index bytes the join reads (caller's pinned buffer or staging)
+  size_t pos = 0;                            // the chunk's offset in its request (a bad index is reported request-global)
+  const uint32_t* pairs = nullptr;           // in place: the pairs the join reads (caller's pinned buffer or staging)
+  unsigned long long* packed = nullptr;      // in place: the words the join writes (caller's pinned buffer or staging)
+  unsigned long long* out = nullptr;         // the caller's words
+  uint32_t ncj = 0;                          // in place: checks the join left (answered into d_perm / d_err)
+  gck_item_error* errs = nullptr;            // a submitted batch: the caller's error list (device_wait)
+  size_t err_cap = 0;
+  size_t* n_errs = nullptr;
+  bool in_place() const { return mode == kInPlace; }
+  bool table_join() const { return mode == kInPlace && indexed; }  // the join reads index bytes and a shape table
+};
+struct CompactBatch : CompactRun {
+  std::vector<gck_item> items;  // expanded: the chunk as items ...
+  std::vector<uint8_t> perm;    // ... and its results (in place: of the checks the join left)
+  std::vector<int32_t> err;
+  void set(const CompactRun& r) { static_cast<CompactRun&>(*this) = r; }
+};
+
 // One check workspace: the scratch of one batch in flight, on its own HIP stream. An engine
 // keeps a pool of them (acquire_ws / release_ws), so concurrent callers — and the batches a
 // caller submits without waiting (gck_check_submit) — run side by side on the device: the
@@ -234,25 +264,7 @@ struct Workspace {
   bool b_res = false;         // ... posted to the resident join (resident.inc) instead
   uint32_t ws_index = 0;      // the workspace's place in the pool (its resident-join slot)
   uint32_t res_seq = 0;       // resident-join requests posted from it
-  // ---- a uniform batch (gck_check_bulk_uniform / gck_check_submit_uniform) -----------------
-  bool u_on = false;          // this batch is uniform: its wait packs the results (uniform_collect)
-  bool u_join = false;        // ... and its join reads the pairs and writes the packed words in place
-  uint32_t u_rp = 0, u_ss = 0, u_ctx = 0;       // the header (closure.inc CjArgs::u_rp ...)
-  const uint32_t* u_pairs = nullptr;            // the pairs the join reads (caller's pinned buffer or staging)
-  unsigned long long* u_packed = nullptr;       // the words the join writes (caller's pinned buffer or staging)
-  unsigned long long* u_out = nullptr;          // the caller's words
-  uint32_t u_ncj = 0;                           // checks the join left (answered into d_perm / d_err)
-  std::vector<gck_item> u_items;                // otherwise: the request expanded to items ...
-  std::vector<uint8_t> u_perm;                  // ... and its results
-  std::vector<int32_t> u_err;
-  gck_item_error* u_errs = nullptr;             // submit_uniform: the caller's error list
-  size_t u_err_cap = 0;
-  size_t* u_n_errs = nullptr;
-  // ---- ... or shaped (gck_check_bulk_shaped / gck_check_submit_shaped): u_on as above, and -----
-  bool s_join = false;                          // the join reads the index bytes and the shape table too (with u_join)
-  uint32_t s_n_shapes = 0;
-  const uint8_t* s_shape_of = nullptr;          // the index bytes the join reads (caller's pinned buffer or staging)
-  size_t s_pos = 0;                             // the chunk's offset in its request (a bad index is reported request-global)
+  CompactBatch cb;            // the batch is a compact request's chunk (submit_compact)
   void* aql_shapes = nullptr;   // aql.inc: the shape table the join reads (GCK_MAX_SHAPES entries, memory as aql_kernarg)
   alignas(16) unsigned char shapes_shadow[GCK_MAX_SHAPES * sizeof(gck_uniform)] = {};  // ... what it holds now
   void* aql_kernarg = nullptr;  // aql.inc: kernarg block of the dispatched join (pinned host memory, or VRAM)
@@ -2540,7 +2552,7 @@ static bool join_on(const Engine& e) {
 }
 
 // A batch over host memory can run zero-copy: its join, dispatched into the engine's queues, reads
-// the request from and writes the results into pinned host memory (submit_batch, submit_uniform).
+// the request from and writes the results into pinned host memory (submit_batch, submit_compact).
 // Not with check contexts, nor profiled (GCK_AQL=0 or a profiled batch take the DMA path).
 static bool zero_copy_ok(const Engine& e, const Workspace& w) {
   return e.aql && w.aql_kernarg && !w.cav_on && !(e.cfg.flags & (GCK_FLAG_PROFILE | GCK_FLAG_NO_BUNDLE)) && join_on(e);
@@ -2586,16 +2598,19 @@ static void aql_collect(Workspace& w) {
 // written where those read them (the workspace's item array, which the batch runs on).
 template <typename Args>
 static void uniform_args(const Workspace& w, Args& j) {
-  j.pairs = w.u_pairs;
-  j.out_packed = w.u_packed;
+  const CompactRun& c = w.cb;
+  j.pairs = c.pairs;
+  j.out_packed = c.packed;
   j.items_out = const_cast<gck_item*>(w.b_items);
-  j.u_rp = w.u_rp;
-  j.u_ss = w.u_ss;
-  j.u_ctx = w.u_ctx;
-  if (w.s_join) {  // (a shaped batch: the index bytes and the table lie over the header words)
-    j.shape_of = w.s_shape_of;
+  // kernel input mode: a uniform batch's header travels in the kernarg words; it is never sent as a
+  // table of one entry (the table mode measured 0.86x the header mode's rate)
+  j.u_rp = c.rp;
+  j.u_ss = c.ss;
+  j.u_ctx = c.ctx;
+  if (c.table_join()) {  // (a shaped batch: the index bytes and the table lie over the header words)
+    j.shape_of = c.shape_of;
     j.shapes = static_cast<const gck_uniform*>(w.aql_shapes);
-    j.n_shapes = w.s_n_shapes;
+    j.n_shapes = c.n_shapes;
   }
   j.items = nullptr;
 }
@@ -2703,7 +2718,7 @@ static void join_args(const Route& r, Workspace& w, const BundleArgs& a, Args& j
     j.bad_slot = &w.ctr->bad_slot;
     j.slot_limit = w.cav.n_given;
   }
-  if (w.u_join) uniform_args(w, j);
+  if (w.cb.in_place()) uniform_args(w, j);
   // self-published (a host-side stream query or synchronisation per batch instead costs ~10 us,
   // 11 G -> 3-5 G checks/s)
   if (r.self_pub) {
@@ -2817,7 +2832,8 @@ static void closure_join_start(Engine& e, Workspace& w, const Route& r, const Ct
   // the resident join (resident.inc) takes the request without a dispatch of its own
   // (a shaped batch is dispatched: the running launch would read the workspace's shape table, which
   // the host rewrites between requests, without a dispatch's acquire in between)
-  const bool res_ok = ak && e.res && !r.timed && w.b_sum_blocks == grid.x && (cj_args.j.mode & kPubBySignal) && !w.s_join;
+  const bool res_ok = ak && e.res && !r.timed && w.b_sum_blocks == grid.x && (cj_args.j.mode & kPubBySignal) &&
+                      !w.cb.table_join();
   if (res_ok) {
     aql_after_build(e);
     res_post(e, w, cj_args.j, grid.x);
@@ -2918,7 +2934,7 @@ static float bundles_finish(Engine& e, Workspace& w) {
   if (w.h_ctr->bad_slot) {  // (a zero-copy batch's join found a context slot out of range)
     const uint32_t i = 0xFFFFFFFFu - w.h_ctr->bad_slot;
     // (a shaped batch's table was checked by the host: the join reports an index byte beyond it)
-    if (w.s_join) shape_index_error(w.s_pos + i, i < n ? w.s_shape_of[i] : 0u, w.s_n_shapes);
+    if (w.cb.table_join()) shape_index_error(w.cb.pos + i, i < n ? w.cb.shape_of[i] : 0u, w.cb.n_shapes);
     slot_error(i, i < n ? d_items[i].context_slot : 0u, w.cav.n_given);
   }
   const bool profile = w.b_timed;
@@ -2928,7 +2944,7 @@ static float bundles_finish(Engine& e, Workspace& w) {
   bm = ms;
   const uint32_t n_cj = w.b_closure ? w.h_bctrs[4] : 0u;
   if (n_cj > n) throw Error(GCK_E_DEVICE, "engine invariant violated: closure-join deferred count");
-  w.u_ncj = n_cj;
+  w.cb.ncj = n_cj;
   if (w.b_closure) {
     // the join counts only its task-round checks (DevCounters::closure; usually none, so usually
     // no atomic): the rest of what it answered came from the slots
@@ -3275,13 +3291,23 @@ void host_free_all(Engine& e) {
   e.host_bufs.clear();
 }
 
+// Where a batch's items and result buffers live: device memory ordered on the caller's stream, device
+// memory on the workspace's own stream (GCK_SUBMIT_ENGINE_STREAM), or host memory.
+enum class BatchMem { kCallerStream, kEngineStream, kHost };
+
+// The one end of a batch: the workspace is idle again and holds no compact request's state.
+static void end_batch(Workspace& w) {
+  w.state = 0;
+  w.cb.set(CompactRun{});
+}
+
+// Starts the batch (stage A) on w. `compact`: the batch as a compact request's chunk, set up by
+// submit_compact; the default is a batch of items.
 static void submit_batch(Engine& e, Workspace& w, const gck_item* items, uint32_t n, int64_t now_us, uint8_t* perm,
-                         int32_t* err, hipStream_t st, bool host, bool own_stream = false, bool uniform_join = false,
-                         bool shaped_join = false) {
-  w.u_join = uniform_join;  // (the join's arguments: bundles_launch)
-  w.s_join = shaped_join;   // (with uniform_join)
-  w.u_on = false;           // (submit_uniform sets it after this)
-  w.b_own_stream = own_stream;
+                         int32_t* err, hipStream_t st, BatchMem mem, const CompactRun& compact = CompactRun{}) {
+  bool host = mem == BatchMem::kHost;
+  w.cb.set(compact);  // (whatever an earlier batch left; the join's arguments read it: bundles_launch)
+  w.b_own_stream = mem == BatchMem::kEngineStream;
   w.b_n = n;
   w.b_now = now_us;
   w.b_st = host ? w.stream : st;
@@ -3301,7 +3327,9 @@ static void submit_batch(Engine& e, Workspace& w, const gck_item* items, uint32_
   // (GCK_AQL=0, a profiled batch): the DMA path below.
   w.b_copy_perm = nullptr;
   w.b_copy_err = nullptr;
-  w.b_validate = shaped_join;  // (its join reads the index bytes in place: a bad one lands in bad_slot)
+  // an in-place shaped batch: its join reads the index bytes, and a bad one lands in bad_slot (an
+  // in-place uniform batch needs no check by the join: its one header was checked on the host)
+  w.b_validate = w.cb.table_join();
   if (host && zero_copy_ok(e, w)) {
     // the join reads every item once, in place: it also checks the context slots (no host pass
     // over the items on the submitting thread)
@@ -3452,7 +3480,7 @@ static void check_range(Engine& e, Workspace& w, const gck_item* d_items, size_t
                         int32_t* d_err, hipStream_t st, float* ms) {
   for (size_t pos = 0; pos < n; pos += w.max_batch) {
     const uint32_t len = (uint32_t)std::min(n - pos, w.max_batch);
-    submit_batch(e, w, d_items + pos, len, now_us, d_perm + pos, d_err + pos, st, false);
+    submit_batch(e, w, d_items + pos, len, now_us, d_perm + pos, d_err + pos, st, BatchMem::kCallerStream);
     finish_batch(e, w);
     w.state = 0;
     *ms += w.b_ms;
@@ -3495,8 +3523,7 @@ static void run_chunks(Engine& e, Workspace* w0, Workspace* w1, size_t n, size_t
     finish_batch(e, w);
     copy_out(w);
     complete(w);
-    w.state = 0;
-    w.u_on = false;
+    end_batch(w);
     ms += w.b_ms;
   };
   try {
@@ -3522,8 +3549,7 @@ static void run_chunks(Engine& e, Workspace* w0, Workspace* w1, size_t n, size_t
         } catch (...) {
         }
       }
-      x->state = 0;
-      x->u_on = false;
+      end_batch(*x);
     }
     throw;
   }
@@ -3544,7 +3570,7 @@ void device_check_host(Engine& e, Workspace* w0, Workspace* w1, const gck_item* 
         // fails the call with its request index and no chunk is left writing the caller's buffers (a
         // single chunk's zero-copy join checks its own items in place)
         if (pos == 0 && n > mb) validate_slots(items, (uint32_t)n, w.cav.n_given);
-        submit_batch(e, w, items + pos, len, now_us, perm + pos, err + pos, nullptr, true);
+        submit_batch(e, w, items + pos, len, now_us, perm + pos, err + pos, nullptr, BatchMem::kHost);
       },
       [](Workspace&) {});
 }
@@ -3557,84 +3583,127 @@ void device_submit(Engine& e, Workspace* w, const gck_item* items, size_t n, int
   hipStream_t st = (host || engine_stream) ? w->stream : (hipStream_t)stream;
   stage_caveats(*w, std::move(cav), st);
   if (now_us == 0) now_us = wall_now_us();
-  submit_batch(e, *w, items, (uint32_t)n, now_us, perm, err, st, host, !host && engine_stream);
+  submit_batch(e, *w, items, (uint32_t)n, now_us, perm, err, st,
+               host ? BatchMem::kHost : engine_stream ? BatchMem::kEngineStream : BatchMem::kCallerStream);
 }
 
-// ---- uniform batches (include/gck.h gck_check_bulk_uniform, gck_check_submit_uniform) ----------
-// One header and (resource id, subject id) pairs in, 2-bit results out. With a one-round join on
-// the engine's queues the join reads the pairs and writes the packed words in place (zero-copy:
-// 8 B per check in, 1/4 B out across PCIe) and writes the item of each check it leaves into the
-// workspace's item array, where the bundle stages answer it; the wait patches those into the words
-// and lists the errors. Otherwise the request is expanded to items and runs as a host batch.
-static void submit_uniform(Engine& e, Workspace& w, const gck_uniform& h, const uint32_t* pairs, uint32_t n,
-                           int64_t now_us, unsigned long long* packed) {
-  const uint32_t rp = (uint32_t)h.resource_type | (uint32_t)h.permission << 16;
-  const uint32_t ss = (uint32_t)h.subject_type | (uint32_t)h.subject_relation << 16;
-  if (zero_copy_ok(e, w)) {
-    const size_t words = ((size_t)n + 31u) / 32u;
-    const bool pin_in = host_pinned(e, pairs, (size_t)n * 8u), pin_out = host_pinned(e, packed, words * 8u);
-    if (!pin_in) std::memcpy(w.h_items, pairs, (size_t)n * 8u);
-    w.u_rp = rp;
-    w.u_ss = ss;
-    w.u_ctx = h.context_slot;
-    w.u_pairs = pin_in ? pairs : reinterpret_cast<const uint32_t*>(w.h_items);
-    // (the staging's result region holds 4 B per check: room for the words)
-    w.u_packed = pin_out ? packed : reinterpret_cast<unsigned long long*>(w.h_err);
-    submit_batch(e, w, w.d_items, n, now_us, w.d_perm, w.d_err, w.stream, false, true, true);
-  } else {
-    w.u_items.resize(n);
-    for (uint32_t k = 0; k < n; ++k) {
-      gck_item& it = w.u_items[k];
-      it.resource_type = h.resource_type;
-      it.permission = h.permission;
-      it.resource_id = pairs[2 * (size_t)k];
-      it.subject_type = h.subject_type;
-      it.subject_relation = h.subject_relation;
-      it.subject_id = pairs[2 * (size_t)k + 1];
-      it.context_slot = h.context_slot;
-    }
-    w.u_perm.resize(n);
-    w.u_err.resize(n);
-    w.u_packed = nullptr;
-    submit_batch(e, w, w.u_items.data(), n, now_us, w.u_perm.data(), w.u_err.data(), nullptr, true);
+// ---- compact batches (include/gck.h gck_check_bulk_uniform / _shaped, gck_check_submit_*) --------
+// A table of shapes, (resource id, subject id) pairs and — unless the request is uniform: one shape
+// for every check — an index byte per check in; 2-bit results and an error list out (engine.hpp
+// CompactReq). With a one-round join on the engine's queues the join reads the pairs and the index
+// bytes and writes the packed words in place (zero-copy: 8 or 9 B per check in, 1/4 B out across
+// PCIe) and writes the item of each check it leaves into the workspace's item array, where the
+// bundle stages answer it; the wait patches those into the words and lists the errors
+// (uniform_collect). Otherwise the chunk is expanded to items and runs as a host batch.
+
+// The chunk [pos, pos + items.size()) of the request as items; an index byte beyond the table fails
+// it with the check's place in the request.
+static void compact_expand(const CompactReq& q, size_t pos, std::vector<gck_item>& items) {
+  for (size_t k = 0; k < items.size(); ++k) {
+    const uint32_t s = q.shape_of ? q.shape_of[pos + k] : 0u;
+    if (s >= q.n_shapes) shape_index_error(pos + k, s, q.n_shapes);
+    const gck_uniform& h = q.shapes[s];
+    gck_item& it = items[k];
+    it.resource_type = h.resource_type;
+    it.permission = h.permission;
+    it.resource_id = q.pairs[2 * (pos + k)];
+    it.subject_type = h.subject_type;
+    it.subject_relation = h.subject_relation;
+    it.subject_id = q.pairs[2 * (pos + k) + 1];
+    it.context_slot = h.context_slot;
   }
-  w.u_on = true;
-  w.u_out = packed;
-  w.u_ncj = 0;
 }
 
-// After a uniform batch has finished (finish_batch, copy_out): its words into the caller's buffer
-// and its errors, at request offset `pos`, appended to `errs`.
-static void uniform_collect(Workspace& w, uint32_t pos, std::vector<gck_item_error>& errs) {
-  const uint32_t n = w.b_n;
+// Where the join of an in-place chunk reads and writes: the caller's buffers when they are pinned
+// (gck_host_alloc), else the workspace's pinned staging after one host copy — its item region
+// holds 20 B per check (the pairs first, then the index bytes if there are any), its result
+// region 4 B per check (room for the words).
+static void compact_stage(Engine& e, Workspace& w, const uint32_t* pairs, const uint8_t* shape_of, uint32_t n,
+                          CompactRun& c) {
+  unsigned char* stage = reinterpret_cast<unsigned char*>(w.h_items);
   const size_t words = ((size_t)n + 31u) / 32u;
-  if (w.u_join) {
-    unsigned long long* out = w.u_packed;
-    if (w.u_ncj) {  // the checks the join left: their results from the bundle stages
-      std::vector<uint32_t> idx(w.u_ncj);
-      w.u_perm.resize(n);
-      w.u_err.resize(n);
+  c.pairs = pairs;
+  if (!host_pinned(e, pairs, (size_t)n * 8u)) {
+    std::memcpy(stage, pairs, (size_t)n * 8u);
+    c.pairs = reinterpret_cast<const uint32_t*>(stage);
+  }
+  c.shape_of = shape_of;
+  if (shape_of && !host_pinned(e, shape_of, n)) {
+    std::memcpy(stage + (size_t)n * 8u, shape_of, n);
+    c.shape_of = stage + (size_t)n * 8u;
+  }
+  c.packed = host_pinned(e, c.out, words * 8u) ? c.out : reinterpret_cast<unsigned long long*>(w.h_err);
+}
+
+// Queues the chunk [pos, pos + len) of the request on w (pos: a multiple of 32).
+static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t pos, uint32_t len, int64_t now_us) {
+  CompactRun c;
+  c.indexed = q.shape_of != nullptr;
+  c.n_shapes = q.n_shapes;
+  c.pos = pos;
+  c.out = reinterpret_cast<unsigned long long*>(q.packed + pos / 32);
+  c.errs = q.errs;  // (read by device_wait only: a synchronous request's chunks are collected by its caller)
+  c.err_cap = q.err_cap;
+  c.n_errs = q.n_errs;
+  // in-place condition: a uniform chunk runs in place when a host batch could run zero-copy; a
+  // shaped chunk also needs the workspace's table block
+  if (zero_copy_ok(e, w) && (!c.indexed || w.aql_shapes)) {
+    c.mode = CompactRun::kInPlace;
+    compact_stage(e, w, q.pairs + 2 * pos, c.indexed ? q.shape_of + pos : nullptr, len, c);
+    if (c.indexed) {
+      aql_put_shapes(*e.aql, w, q.shapes, q.n_shapes);
+    } else {  // kernel input mode: the one header in the kernarg words, not a table of one (uniform_args)
+      const gck_uniform& h = q.shapes[0];
+      c.rp = (uint32_t)h.resource_type | (uint32_t)h.permission << 16;
+      c.ss = (uint32_t)h.subject_type | (uint32_t)h.subject_relation << 16;
+      c.ctx = h.context_slot;
+    }
+    submit_batch(e, w, w.d_items, len, now_us, w.d_perm, w.d_err, w.stream, BatchMem::kEngineStream, c);
+  } else {
+    c.mode = CompactRun::kExpanded;
+    w.cb.items.resize(len);
+    compact_expand(q, pos, w.cb.items);
+    w.cb.perm.resize(len);
+    w.cb.err.resize(len);
+    submit_batch(e, w, w.cb.items.data(), len, now_us, w.cb.perm.data(), w.cb.err.data(), nullptr, BatchMem::kHost, c);
+  }
+  // (gck_shaped_stats counts shaped chunks only, one count per chunk)
+  if (c.indexed) (c.in_place() ? e.shaped_in_place : e.shaped_expanded).fetch_add(1, std::memory_order_relaxed);
+}
+
+// After a compact batch has finished (finish_batch, copy_out): its words into the caller's buffer
+// and its errors, at the chunk's offset in the request, appended to `errs`.
+static void uniform_collect(Workspace& w, std::vector<gck_item_error>& errs) {
+  const uint32_t n = w.b_n, pos = (uint32_t)w.cb.pos;
+  const size_t words = ((size_t)n + 31u) / 32u;
+  CompactBatch& c = w.cb;
+  if (c.in_place()) {
+    unsigned long long* out = c.packed;
+    if (c.ncj) {  // the checks the join left: their results from the bundle stages
+      std::vector<uint32_t> idx(c.ncj);
+      c.perm.resize(n);
+      c.err.resize(n);
       HIP_OK(hipMemcpyAsync(idx.data(), w.c_deferred, idx.size() * 4u, hipMemcpyDeviceToHost, w.stream));
-      HIP_OK(hipMemcpyAsync(w.u_perm.data(), w.d_perm, n, hipMemcpyDeviceToHost, w.stream));
-      HIP_OK(hipMemcpyAsync(w.u_err.data(), w.d_err, (size_t)n * 4u, hipMemcpyDeviceToHost, w.stream));
+      HIP_OK(hipMemcpyAsync(c.perm.data(), w.d_perm, n, hipMemcpyDeviceToHost, w.stream));
+      HIP_OK(hipMemcpyAsync(c.err.data(), w.d_err, (size_t)n * 4u, hipMemcpyDeviceToHost, w.stream));
       HIP_OK(hipStreamSynchronize(w.stream));
       for (uint32_t i : idx) {
         if (i >= n) throw Error(GCK_E_DEVICE, "engine invariant violated: deferred index");
-        if (w.u_err[i]) errs.push_back(gck_item_error{pos + i, w.u_err[i]});
-        else out[i >> 5] |= (unsigned long long)(w.u_perm[i] & 3u) << (2u * (i & 31u));
+        if (c.err[i]) errs.push_back(gck_item_error{pos + i, c.err[i]});
+        else out[i >> 5] |= (unsigned long long)(c.perm[i] & 3u) << (2u * (i & 31u));
       }
     }
-    if (out != w.u_out) std::memcpy(w.u_out, out, words * 8u);
+    if (out != c.out) std::memcpy(c.out, out, words * 8u);
   } else {
     for (size_t k = 0; k < words; ++k) {
       unsigned long long x = 0;
       const uint32_t b = (uint32_t)k * 32u, m = std::min<uint32_t>(32u, n - b);
       for (uint32_t q = 0; q < m; ++q) {
         const uint32_t i = b + q;
-        if (w.u_err[i]) errs.push_back(gck_item_error{pos + i, w.u_err[i]});
-        else x |= (unsigned long long)(w.u_perm[i] & 3u) << (2u * q);
+        if (c.err[i]) errs.push_back(gck_item_error{pos + i, c.err[i]});
+        else x |= (unsigned long long)(c.perm[i] & 3u) << (2u * q);
       }
-      w.u_out[k] = x;
+      c.out[k] = x;
     }
   }
 }
@@ -3647,127 +3716,31 @@ static void uniform_errors(std::vector<gck_item_error>& errs, gck_item_error* ou
   if (n_errs) *n_errs = errs.size();
 }
 
-// ---- shaped batches (include/gck.h gck_check_bulk_shaped, gck_check_submit_shaped) ------------
-// A table of shapes, one index byte per check and the id pairs in; the uniform request's words and
-// error list out (uniform_collect). Zero-copy under the uniform request's condition: the join reads
-// the pairs and the index bytes in place (or from the pinned staging after one host copy), the
-// table from the workspace's own block (aql.inc aql_put_shapes), and reports an index beyond the
-// table through the context-slot check's counter. Otherwise each check is expanded to its own item.
-// pos: the chunk's offset in the request.
-static void submit_shaped(Engine& e, Workspace& w, const gck_uniform* shapes, uint32_t n_shapes, const uint8_t* shape_of,
-                          const uint32_t* pairs, uint32_t n, int64_t now_us, unsigned long long* packed, size_t pos) {
-  w.s_pos = pos;
-  w.s_n_shapes = n_shapes;
-  if (zero_copy_ok(e, w) && w.aql_shapes) {
-    const size_t words = ((size_t)n + 31u) / 32u;
-    const bool pin_pairs = host_pinned(e, pairs, (size_t)n * 8u), pin_idx = host_pinned(e, shape_of, n);
-    const bool pin_out = host_pinned(e, packed, words * 8u);
-    // (the staging's item region holds 20 B per check: the pairs, then the index bytes)
-    unsigned char* stage = reinterpret_cast<unsigned char*>(w.h_items);
-    if (!pin_pairs) std::memcpy(stage, pairs, (size_t)n * 8u);
-    if (!pin_idx) std::memcpy(stage + (size_t)n * 8u, shape_of, n);
-    aql_put_shapes(*e.aql, w, shapes, n_shapes);
-    w.u_rp = w.u_ss = w.u_ctx = 0;
-    w.u_pairs = pin_pairs ? pairs : reinterpret_cast<const uint32_t*>(stage);
-    w.s_shape_of = pin_idx ? shape_of : stage + (size_t)n * 8u;
-    w.u_packed = pin_out ? packed : reinterpret_cast<unsigned long long*>(w.h_err);
-    submit_batch(e, w, w.d_items, n, now_us, w.d_perm, w.d_err, w.stream, false, true, true, true);
-    e.shaped_in_place.fetch_add(1, std::memory_order_relaxed);
-  } else {
-    w.u_items.resize(n);
-    for (uint32_t k = 0; k < n; ++k) {
-      if (shape_of[k] >= n_shapes) shape_index_error(pos + k, shape_of[k], n_shapes);
-      const gck_uniform& h = shapes[shape_of[k]];
-      gck_item& it = w.u_items[k];
-      it.resource_type = h.resource_type;
-      it.permission = h.permission;
-      it.resource_id = pairs[2 * (size_t)k];
-      it.subject_type = h.subject_type;
-      it.subject_relation = h.subject_relation;
-      it.subject_id = pairs[2 * (size_t)k + 1];
-      it.context_slot = h.context_slot;
-    }
-    w.u_perm.resize(n);
-    w.u_err.resize(n);
-    w.u_packed = nullptr;
-    submit_batch(e, w, w.u_items.data(), n, now_us, w.u_perm.data(), w.u_err.data(), nullptr, true);
-    e.shaped_expanded.fetch_add(1, std::memory_order_relaxed);
-  }
-  w.u_on = true;
-  w.u_out = packed;
-  w.u_ncj = 0;
-}
-
-void device_submit_shaped(Engine& e, Workspace* w, const gck_uniform* shapes, uint32_t n_shapes, const uint8_t* shape_of,
-                          const uint32_t* pairs, size_t n, int64_t now_us, uint64_t* packed, gck_item_error* errs,
-                          size_t cap, size_t* n_errs, CavCall cav) {
+void device_submit_compact(Engine& e, Workspace* w, const CompactReq& req, int64_t now_us, CavCall cav) {
   HIP_OK(hipSetDevice(e.device));
   std::lock_guard<std::mutex> lk(w->m);
-  if (n > w->max_batch) throw Error(GCK_E_INVALID_ARGUMENT, "submitted batch above max_batch");
+  if (req.n > w->max_batch) throw Error(GCK_E_INVALID_ARGUMENT, "submitted batch above max_batch");
   stage_caveats(*w, std::move(cav), w->stream);
   if (now_us == 0) now_us = wall_now_us();
-  submit_shaped(e, *w, shapes, n_shapes, shape_of, pairs, (uint32_t)n, now_us,
-                reinterpret_cast<unsigned long long*>(packed), 0);
-  w->u_errs = errs;
-  w->u_err_cap = cap;
-  w->u_n_errs = n_errs;
-}
-
-// Synchronous: chunks as device_check_uniform's (multiples of 32 checks); chunk inputs are
-// shape_of + pos and pairs + 2 pos.
-void device_check_shaped(Engine& e, Workspace* w0, Workspace* w1, const gck_uniform* shapes, uint32_t n_shapes,
-                         const uint8_t* shape_of, const uint32_t* pairs, size_t n, int64_t now_us, uint64_t* packed,
-                         gck_item_error* out_errs, size_t cap, size_t* n_errs, const CavCall& cav) {
-  HIP_OK(hipSetDevice(e.device));
-  if (now_us == 0) now_us = wall_now_us();
-  const size_t mb = w0->max_batch >= 32 ? (w0->max_batch & ~(size_t)31) : w0->max_batch;
-  if (n > mb && mb % 32 != 0) throw Error(GCK_E_CAPACITY, "a shaped request above max_batch needs max_batch >= 32");
-  std::vector<gck_item_error> errs;
-  size_t pos_of[2] = {0, 0};
-  run_chunks(
-      e, w0, w1, n, mb, cav,
-      [&](Workspace& w, size_t pos, uint32_t len) {
-        pos_of[&w == w0 ? 0 : 1] = pos;
-        submit_shaped(e, w, shapes, n_shapes, shape_of + pos, pairs + 2 * pos, len, now_us,
-                      reinterpret_cast<unsigned long long*>(packed + pos / 32), pos);
-      },
-      [&](Workspace& w) { uniform_collect(w, (uint32_t)pos_of[&w == w0 ? 0 : 1], errs); });
-  uniform_errors(errs, out_errs, cap, n_errs);
-}
-
-void device_submit_uniform(Engine& e, Workspace* w, const gck_uniform& h, const uint32_t* pairs, size_t n,
-                           int64_t now_us, uint64_t* packed, gck_item_error* errs, size_t cap, size_t* n_errs,
-                           CavCall cav) {
-  HIP_OK(hipSetDevice(e.device));
-  std::lock_guard<std::mutex> lk(w->m);
-  if (n > w->max_batch) throw Error(GCK_E_INVALID_ARGUMENT, "submitted batch above max_batch");
-  stage_caveats(*w, std::move(cav), w->stream);
-  if (now_us == 0) now_us = wall_now_us();
-  submit_uniform(e, *w, h, pairs, (uint32_t)n, now_us, reinterpret_cast<unsigned long long*>(packed));
-  w->u_errs = errs;
-  w->u_err_cap = cap;
-  w->u_n_errs = n_errs;
+  submit_compact(e, *w, req, 0, (uint32_t)req.n, now_us);
 }
 
 // Synchronous: chunks of max_batch (a multiple of 32 checks, so that each chunk's words start a
 // word) on two workspaces in turn, as device_check_host.
-void device_check_uniform(Engine& e, Workspace* w0, Workspace* w1, const gck_uniform& h, const uint32_t* pairs,
-                          size_t n, int64_t now_us, uint64_t* packed, gck_item_error* out_errs, size_t cap,
-                          size_t* n_errs, const CavCall& cav) {
+void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const CompactReq& req, int64_t now_us,
+                          const CavCall& cav) {
   HIP_OK(hipSetDevice(e.device));
   if (now_us == 0) now_us = wall_now_us();
   const size_t mb = w0->max_batch >= 32 ? (w0->max_batch & ~(size_t)31) : w0->max_batch;
-  if (n > mb && mb % 32 != 0) throw Error(GCK_E_CAPACITY, "a uniform request above max_batch needs max_batch >= 32");
+  if (req.n > mb && mb % 32 != 0)
+    throw Error(GCK_E_CAPACITY, req.shape_of ? "a shaped request above max_batch needs max_batch >= 32"
+                                             : "a uniform request above max_batch needs max_batch >= 32");
   std::vector<gck_item_error> errs;
-  size_t pos_of[2] = {0, 0};  // the request offset of the chunk on w0 / on the other workspace
   run_chunks(
-      e, w0, w1, n, mb, cav,
-      [&](Workspace& w, size_t pos, uint32_t len) {
-        pos_of[&w == w0 ? 0 : 1] = pos;
-        submit_uniform(e, w, h, pairs + 2 * pos, len, now_us, reinterpret_cast<unsigned long long*>(packed + pos / 32));
-      },
-      [&](Workspace& w) { uniform_collect(w, (uint32_t)pos_of[&w == w0 ? 0 : 1], errs); });
-  uniform_errors(errs, out_errs, cap, n_errs);
+      e, w0, w1, req.n, mb, cav,
+      [&](Workspace& w, size_t pos, uint32_t len) { submit_compact(e, w, req, pos, len, now_us); },
+      [&](Workspace& w) { uniform_collect(w, errs); });
+  uniform_errors(errs, req.errs, req.err_cap, req.n_errs);
 }
 
 // Completes a submitted batch. Takes no engine lock: a writer that wants to replace the
@@ -3776,16 +3749,17 @@ void device_check_uniform(Engine& e, Workspace* w0, Workspace* w1, const gck_uni
 void device_wait(Engine& e, Workspace* w) {
   HIP_OK(hipSetDevice(e.device));
   std::lock_guard<std::mutex> lk(w->m);
+  struct End {  // (also when the batch failed: the workspace goes back to the pool)
+    Workspace& w;
+    ~End() { end_batch(w); }
+  } end{*w};
   finish_batch(e, *w);  // no-op when a writer already finished it (drain_batches)
-  w->state = 0;
-  const bool uni = w->u_on;
-  w->u_on = false;
   if (w->fail_code) throw Error(w->fail_code, w->fail_msg);
   copy_out(*w);
-  if (uni) {
+  if (w->cb.mode != CompactRun::kOff) {
     std::vector<gck_item_error> errs;
-    uniform_collect(*w, 0, errs);
-    uniform_errors(errs, w->u_errs, w->u_err_cap, w->u_n_errs);
+    uniform_collect(*w, errs);
+    uniform_errors(errs, w->cb.errs, w->cb.err_cap, w->cb.n_errs);
   }
   std::lock_guard<std::mutex> sl(e.stats_mu);
   e.stats.kernel_ms = w->b_ms;

@@ -378,6 +378,17 @@ struct WsLease {
   WsLease(const WsLease&) = delete;
   WsLease& operator=(const WsLease&) = delete;
 };
+struct WsPair {  // a synchronous host request's: two when it spans several chunks (ws[1] null otherwise)
+  Engine& e;
+  Workspace* ws[2] = {nullptr, nullptr};
+  WsPair(Engine& en, int want) : e(en) { acquire_ws_n(en, want, ws); }
+  ~WsPair() {
+    release_ws(e, ws[0]);
+    if (ws[1] && ws[1] != ws[0]) release_ws(e, ws[1]);
+  }
+  WsPair(const WsPair&) = delete;
+  WsPair& operator=(const WsPair&) = delete;
+};
 void device_check(Engine& e, Workspace& w, const gck_item* d_items, size_t n, int64_t now_us,
                   uint8_t* d_perm, int32_t* d_err, void* stream, CavCall cav);
 // Host buffers, chunks of max_batch alternating over w0 and w1 (w1 may be null or w0).
@@ -390,24 +401,26 @@ void device_check_host(Engine& e, Workspace* w0, Workspace* w1, const gck_item* 
 void device_submit(Engine& e, Workspace* w, const gck_item* items, size_t n, int64_t now_us, uint8_t* perm,
                    int32_t* err, void* stream, bool host, bool engine_stream, CavCall cav);
 void device_wait(Engine& e, Workspace* w);
-// Uniform requests (gck_check_bulk_uniform / gck_check_submit_uniform): one header, id pairs, packed
-// 2-bit results and the errored checks' (index, code) records in ascending order (the first `cap`
-// written, their number in *n_errs). The submitted form's outputs are written by device_wait.
-void device_check_uniform(Engine& e, Workspace* w0, Workspace* w1, const gck_uniform& h, const uint32_t* pairs,
-                          size_t n, int64_t now_us, uint64_t* packed, gck_item_error* errs, size_t cap,
-                          size_t* n_errs, const CavCall& cav);
-void device_submit_uniform(Engine& e, Workspace* w, const gck_uniform& h, const uint32_t* pairs, size_t n,
-                           int64_t now_us, uint64_t* packed, gck_item_error* errs, size_t cap, size_t* n_errs,
-                           CavCall cav);
-// Shaped requests (gck_check_bulk_shaped / gck_check_submit_shaped): a table of n_shapes headers
-// (copied into the workspace by the submit), an index byte per check and the id pairs in; the
-// outputs are the uniform request's.
-void device_check_shaped(Engine& e, Workspace* w0, Workspace* w1, const gck_uniform* shapes, uint32_t n_shapes,
-                         const uint8_t* shape_of, const uint32_t* pairs, size_t n, int64_t now_us, uint64_t* packed,
-                         gck_item_error* errs, size_t cap, size_t* n_errs, const CavCall& cav);
-void device_submit_shaped(Engine& e, Workspace* w, const gck_uniform* shapes, uint32_t n_shapes, const uint8_t* shape_of,
-                          const uint32_t* pairs, size_t n, int64_t now_us, uint64_t* packed, gck_item_error* errs,
-                          size_t cap, size_t* n_errs, CavCall cav);
+// A compact request (gck_check_bulk_uniform / _shaped, gck_check_submit_uniform / _shaped): a table
+// of n_shapes headers (consumed by the submit), an index byte per check and the id pairs in; packed
+// 2-bit results and the errored checks' (index, code) records in ascending order out (the first
+// err_cap written, their number in *n_errs). A uniform request is the table of one header without
+// index bytes. The submitted form's outputs are written by device_wait.
+struct CompactReq {
+  const gck_uniform* shapes;
+  uint32_t n_shapes;
+  const uint8_t* shape_of;  // null: uniform — every check is shapes[0]
+  const uint32_t* pairs;
+  size_t n;
+  uint64_t* packed;
+  gck_item_error* errs;
+  size_t err_cap;
+  size_t* n_errs;
+};
+// Synchronous: chunks of max_batch & ~31 checks over w0 and w1 (as device_check_host).
+void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const CompactReq& req, int64_t now_us,
+                          const CavCall& cav);
+void device_submit_compact(Engine& e, Workspace* w, const CompactReq& req, int64_t now_us, CavCall cav);
 // Pinned host buffers (gck_host_alloc): a host batch whose items / results live in one is
 // copied by DMA directly, without the workspace's staging copy.
 void* host_alloc(Engine& e, size_t bytes);

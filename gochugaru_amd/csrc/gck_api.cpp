@@ -918,20 +918,54 @@ static void precheck(Engine& e) {
 }
 
 // The checks common to every check entry point (under the shared engine lock).
-static void check_request(Engine& e, const gck_consistency* cs, const gck_item* items, size_t n, bool host_items,
-                          const char* const* contexts, const size_t* context_lens, size_t n_contexts) {
+// (A host item's context_slot is validated by its batch: the join of a zero-copy batch checks every
+// item it reads, the others are scanned before they are staged — engine.hip submit_batch; a scan
+// here read every host item once more on the submitting thread, ~27 us per 64K batch.)
+static void check_request(Engine& e, const gck_consistency* cs, const char* const* contexts, const size_t* context_lens,
+                          size_t n_contexts) {
   REQUIRE(e.committed, GCK_E_STATE, "no snapshot committed");
   REQUIRE(n_contexts == 0 || (contexts && context_lens), GCK_E_INVALID_ARGUMENT, "null contexts");
   REQUIRE(n_contexts < 0xFFFFFFFFull, GCK_E_INVALID_ARGUMENT, "too many contexts");
   REQUIRE(e.part_world <= 1, GCK_E_STATE, "partitioned engine: use gck_part_* (every rank together)");
   check_consistency(e, cs);
-  // (a host item's context_slot is validated by its batch: the join of a zero-copy batch checks
-  // every item it reads, the others are scanned before they are staged — engine.hip submit_batch;
-  // a scan here read every host item once more on the submitting thread, ~27 us per 64K batch)
-  (void)items;
-  (void)n;
-  (void)host_items;
 }
+
+// What a check call says beside its request: the consistency it asks for and its caveat contexts.
+struct CallCtx {
+  const gck_consistency* cs;
+  const char* const* contexts;
+  const size_t* context_lens;
+  size_t n_contexts;
+};
+
+// A synchronous call over host buffers, after the entry point's own argument checks: a request of
+// n checks in chunks of `chunk`; run(w0, w1, cav) checks it and writes the results.
+extern "C++" {  // (a template cannot have C linkage)
+template <class Run>
+static void check_sync(Engine& e, const CallCtx& c, size_t n, size_t chunk, uint64_t* out_revision, Run run) {
+  if (n == 0) {  // empty request -> empty response (client/client_test.go:203-207): no workspace
+    std::shared_lock<std::shared_mutex> lk(e.mu);
+    check_request(e, c.cs, c.contexts, c.context_lens, c.n_contexts);
+    if (out_revision) *out_revision = e.revision;
+    return;
+  }
+  // workspaces first, then the engine lock (engine.hpp WsLease)
+  precheck(e);
+  // a request above the chunk size alternates over two workspaces, taken in one step (never one
+  // held while waiting for the other: acquire_ws_n)
+  WsPair p(e, n > chunk ? 2 : 1);
+  // (the shared lock is held until the results are written: no Watch batch publishes meanwhile,
+  // so the revision read here is the one every chunk runs on)
+  std::shared_lock<std::shared_mutex> lk(e.mu);
+  check_request(e, c.cs, c.contexts, c.context_lens, c.n_contexts);
+  const CavCall cav = caveat_call(e, c.contexts, c.context_lens, c.n_contexts);
+  const uint64_t rev = e.revision;
+  run(p.ws[0], p.ws[1], cav);
+  if (out_revision) *out_revision = rev;
+}
+}  // extern "C++"
+
+static size_t max_batch_of(const Engine& e) { return e.cfg.max_batch ? e.cfg.max_batch : 65536; }
 
 int gck_check_bulk_at(gck_engine* ge, const gck_consistency* cs, const gck_item* items, size_t n,
                       const char* const* contexts, const size_t* context_lens, size_t n_contexts,
@@ -939,35 +973,10 @@ int gck_check_bulk_at(gck_engine* ge, const gck_consistency* cs, const gck_item*
   return guard([&] {
     Engine& e = need(ge);
     REQUIRE(n == 0 || (items && out_perm && out_err), GCK_E_INVALID_ARGUMENT, "null buffers");
-    if (n == 0) {  // empty request -> empty response (client/client_test.go:203-207)
-      std::shared_lock<std::shared_mutex> lk(e.mu);
-      check_request(e, cs, items, 0, true, contexts, context_lens, n_contexts);
-      if (out_revision) *out_revision = e.revision;
-      return;
-    }
-    // workspaces first, then the engine lock (engine.hpp WsLease)
-    precheck(e);
-    // a request above max_batch alternates over two workspaces, taken in one step (never one
-    // held while waiting for the other: acquire_ws_n)
-    const size_t mb = e.cfg.max_batch ? e.cfg.max_batch : 65536;
-    Workspace* ws[2] = {nullptr, nullptr};
-    acquire_ws_n(e, n > mb ? 2 : 1, ws);
-    struct Release {
-      Engine& e;
-      Workspace** ws;
-      ~Release() {
-        release_ws(e, ws[0]);
-        if (ws[1] && ws[1] != ws[0]) release_ws(e, ws[1]);
-      }
-    } rel{e, ws};
-    // (the shared lock is held until the results are written: no Watch batch publishes meanwhile,
-    // so the revision read here is the one every chunk runs on)
-    std::shared_lock<std::shared_mutex> lk(e.mu);
-    check_request(e, cs, items, n, true, contexts, context_lens, n_contexts);
-    const CavCall cav = caveat_call(e, contexts, context_lens, n_contexts);
-    const uint64_t rev = e.revision;
-    device_check_host(e, ws[0], ws[1], items, n, now_us, out_perm, out_err, cav);
-    if (out_revision) *out_revision = rev;
+    check_sync(e, {cs, contexts, context_lens, n_contexts}, n, max_batch_of(e), out_revision,
+               [&](Workspace* w0, Workspace* w1, const CavCall& cav) {
+                 device_check_host(e, w0, w1, items, n, now_us, out_perm, out_err, cav);
+               });
   });
 }
 
@@ -980,6 +989,27 @@ int gck_check_bulk_ctx(gck_engine* ge, const gck_consistency* cs, const gck_item
 int gck_check_bulk(gck_engine* ge, const gck_consistency* cs, const gck_item* items, size_t n,
                    int64_t now_us, uint8_t* out_perm, int32_t* out_err) {
   return gck_check_bulk_at(ge, cs, items, n, nullptr, nullptr, 0, now_us, out_perm, out_err, nullptr);
+}
+
+// The argument checks the compact entry points share, after the header's or the table's own
+// (check_uniform / check_shapes) and in the ABI's order: the buffers, the error list, then the count
+// is cleared. indexed: a shaped request (its index bytes are one of the buffers). Returns the
+// request as the engine takes it (engine.hpp CompactReq).
+static CompactReq compact_request(const gck_uniform* shapes, size_t n_shapes, bool indexed, const uint8_t* shape_of,
+                                  const uint32_t* pairs, size_t n, uint64_t* out_packed, gck_item_error* out_errs,
+                                  size_t err_cap, size_t* out_n_errs) {
+  REQUIRE(n == 0 || ((shape_of || !indexed) && pairs && out_packed), GCK_E_INVALID_ARGUMENT, "null buffers");
+  REQUIRE(err_cap == 0 || out_errs, GCK_E_INVALID_ARGUMENT, "null error list");
+  if (out_n_errs) *out_n_errs = 0;
+  return CompactReq{shapes, (uint32_t)n_shapes, indexed ? shape_of : nullptr, pairs, n, out_packed, out_errs, err_cap,
+                    out_n_errs};
+}
+
+// gck_check_bulk_uniform / gck_check_bulk_shaped after their argument checks (chunks: whole words).
+static void check_compact_sync(Engine& e, const CallCtx& c, const CompactReq& req, int64_t now_us,
+                               uint64_t* out_revision) {
+  check_sync(e, c, req.n, max_batch_of(e) & ~(size_t)31, out_revision,
+             [&](Workspace* w0, Workspace* w1, const CavCall& cav) { device_check_compact(e, w0, w1, req, now_us, cav); });
 }
 
 // A uniform request's header against the call (include/gck.h gck_uniform): its context slot is
@@ -998,33 +1028,8 @@ int gck_check_bulk_uniform(gck_engine* ge, const gck_consistency* cs, const gck_
   return guard([&] {
     Engine& e = need(ge);
     check_uniform(hdr, n_contexts);
-    REQUIRE(n == 0 || (pairs && out_packed), GCK_E_INVALID_ARGUMENT, "null buffers");
-    REQUIRE(err_cap == 0 || out_errs, GCK_E_INVALID_ARGUMENT, "null error list");
-    if (out_n_errs) *out_n_errs = 0;
-    if (n == 0) {
-      std::shared_lock<std::shared_mutex> lk(e.mu);
-      check_request(e, cs, nullptr, 0, true, contexts, context_lens, n_contexts);
-      if (out_revision) *out_revision = e.revision;
-      return;
-    }
-    precheck(e);
-    const size_t mb = e.cfg.max_batch ? e.cfg.max_batch : 65536;
-    Workspace* ws[2] = {nullptr, nullptr};
-    acquire_ws_n(e, n > (mb & ~(size_t)31) ? 2 : 1, ws);
-    struct Release {
-      Engine& e;
-      Workspace** ws;
-      ~Release() {
-        release_ws(e, ws[0]);
-        if (ws[1] && ws[1] != ws[0]) release_ws(e, ws[1]);
-      }
-    } rel{e, ws};
-    std::shared_lock<std::shared_mutex> lk(e.mu);
-    check_request(e, cs, nullptr, n, true, contexts, context_lens, n_contexts);
-    const CavCall cav = caveat_call(e, contexts, context_lens, n_contexts);
-    const uint64_t rev = e.revision;
-    device_check_uniform(e, ws[0], ws[1], *hdr, pairs, n, now_us, out_packed, out_errs, err_cap, out_n_errs, cav);
-    if (out_revision) *out_revision = rev;
+    const CompactReq req = compact_request(hdr, 1, false, nullptr, pairs, n, out_packed, out_errs, err_cap, out_n_errs);
+    check_compact_sync(e, {cs, contexts, context_lens, n_contexts}, req, now_us, out_revision);
   });
 }
 
@@ -1036,13 +1041,13 @@ int gck_check_bulk_device_ctx(gck_engine* ge, const gck_item* d_items, size_t n,
     REQUIRE(n == 0 || (d_items && d_out_perm && d_out_err), GCK_E_INVALID_ARGUMENT, "null buffers");
     if (n == 0) {
       std::shared_lock<std::shared_mutex> lk(e.mu);
-      check_request(e, nullptr, nullptr, 0, false, contexts, context_lens, n_contexts);
+      check_request(e, nullptr, contexts, context_lens, n_contexts);
       return;
     }
     precheck(e);
     WsLease l0(e);
     std::shared_lock<std::shared_mutex> lk(e.mu);
-    check_request(e, nullptr, nullptr, 0, false, contexts, context_lens, n_contexts);
+    check_request(e, nullptr, contexts, context_lens, n_contexts);
     device_check(e, *l0.w, d_items, n, now_us, d_out_perm, d_out_err, stream,
                  caveat_call(e, contexts, context_lens, n_contexts));
   });
@@ -1060,6 +1065,35 @@ struct gck_batch {
   uint64_t revision = 0;  // the snapshot's revision at submit: the one the batch runs on
 };
 
+// A submit entry point after its own argument checks: start(w, cav) queues the n checks on the
+// workspace taken for them. Returns the batch; whatever throws, the workspace is back in the pool
+// and the batch deleted.
+extern "C++" {
+template <class Start>
+static gck_batch* submit_with(Engine& e, const CallCtx& c, size_t n, Start start) {
+  std::unique_ptr<gck_batch> b(new gck_batch());
+  if (n == 0) {  // an empty batch holds no workspace
+    std::shared_lock<std::shared_mutex> lk(e.mu);
+    check_request(e, c.cs, c.contexts, c.context_lens, c.n_contexts);
+    b->revision = e.revision;
+    return b.release();
+  }
+  precheck(e);
+  Workspace* w = acquire_ws(e);  // before the engine lock (engine.hpp WsLease)
+  try {
+    std::shared_lock<std::shared_mutex> lk(e.mu);
+    check_request(e, c.cs, c.contexts, c.context_lens, c.n_contexts);
+    b->revision = e.revision;
+    start(w, caveat_call(e, c.contexts, c.context_lens, c.n_contexts));
+  } catch (...) {
+    release_ws(e, w);
+    throw;
+  }
+  b->w = w;
+  return b.release();
+}
+}  // extern "C++"
+
 int gck_check_submit(gck_engine* ge, const gck_consistency* cs, const gck_item* items, size_t n,
                      const char* const* contexts, const size_t* context_lens, size_t n_contexts, int64_t now_us,
                      uint8_t* out_perm, int32_t* out_err, uint32_t flags, void* stream, gck_batch** out) {
@@ -1069,34 +1103,10 @@ int gck_check_submit(gck_engine* ge, const gck_consistency* cs, const gck_item* 
     *out = nullptr;
     REQUIRE(n == 0 || (items && out_perm && out_err), GCK_E_INVALID_ARGUMENT, "null buffers");
     const bool host = !(flags & GCK_SUBMIT_DEVICE);
-    auto* b = new gck_batch();
-    if (n == 0) {
-      std::shared_lock<std::shared_mutex> lk(e.mu);
-      try {
-        check_request(e, cs, items, 0, host, contexts, context_lens, n_contexts);
-        b->revision = e.revision;
-      } catch (...) {
-        delete b;
-        throw;
-      }
-      *out = b;
-      return;
-    }
-    precheck(e);
-    Workspace* w = acquire_ws(e);  // before the engine lock (engine.hpp WsLease)
-    try {
-      std::shared_lock<std::shared_mutex> lk(e.mu);
-      check_request(e, cs, items, n, host, contexts, context_lens, n_contexts);
-      b->revision = e.revision;
+    *out = submit_with(e, {cs, contexts, context_lens, n_contexts}, n, [&](Workspace* w, CavCall cav) {
       device_submit(e, w, items, n, now_us, out_perm, out_err, stream, host, !host && (flags & GCK_SUBMIT_ENGINE_STREAM),
-                    caveat_call(e, contexts, context_lens, n_contexts));
-    } catch (...) {
-      release_ws(e, w);
-      delete b;
-      throw;
-    }
-    b->w = w;
-    *out = b;
+                    std::move(cav));
+    });
   });
 }
 
@@ -1109,37 +1119,10 @@ int gck_check_submit_uniform(gck_engine* ge, const gck_consistency* cs, const gc
     REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
     *out = nullptr;
     check_uniform(hdr, n_contexts);
-    REQUIRE(n == 0 || (pairs && out_packed), GCK_E_INVALID_ARGUMENT, "null buffers");
-    REQUIRE(err_cap == 0 || out_errs, GCK_E_INVALID_ARGUMENT, "null error list");
-    if (out_n_errs) *out_n_errs = 0;
-    auto* b = new gck_batch();
-    if (n == 0) {
-      std::shared_lock<std::shared_mutex> lk(e.mu);
-      try {
-        check_request(e, cs, nullptr, 0, true, contexts, context_lens, n_contexts);
-        b->revision = e.revision;
-      } catch (...) {
-        delete b;
-        throw;
-      }
-      *out = b;
-      return;
-    }
-    precheck(e);
-    Workspace* w = acquire_ws(e);
-    try {
-      std::shared_lock<std::shared_mutex> lk(e.mu);
-      check_request(e, cs, nullptr, n, true, contexts, context_lens, n_contexts);
-      b->revision = e.revision;
-      device_submit_uniform(e, w, *hdr, pairs, n, now_us, out_packed, out_errs, err_cap, out_n_errs,
-                            caveat_call(e, contexts, context_lens, n_contexts));
-    } catch (...) {
-      release_ws(e, w);
-      delete b;
-      throw;
-    }
-    b->w = w;
-    *out = b;
+    const CompactReq req = compact_request(hdr, 1, false, nullptr, pairs, n, out_packed, out_errs, err_cap, out_n_errs);
+    *out = submit_with(e, {cs, contexts, context_lens, n_contexts}, n, [&](Workspace* w, CavCall cav) {
+      device_submit_compact(e, w, req, now_us, std::move(cav));
+    });
   });
 }
 
@@ -1164,34 +1147,9 @@ int gck_check_bulk_shaped(gck_engine* ge, const gck_consistency* cs, const gck_u
   return guard([&] {
     Engine& e = need(ge);
     check_shapes(shapes, n_shapes, n_contexts);
-    REQUIRE(n == 0 || (shape_of && pairs && out_packed), GCK_E_INVALID_ARGUMENT, "null buffers");
-    REQUIRE(err_cap == 0 || out_errs, GCK_E_INVALID_ARGUMENT, "null error list");
-    if (out_n_errs) *out_n_errs = 0;
-    if (n == 0) {
-      std::shared_lock<std::shared_mutex> lk(e.mu);
-      check_request(e, cs, nullptr, 0, true, contexts, context_lens, n_contexts);
-      if (out_revision) *out_revision = e.revision;
-      return;
-    }
-    precheck(e);
-    const size_t mb = e.cfg.max_batch ? e.cfg.max_batch : 65536;
-    Workspace* ws[2] = {nullptr, nullptr};
-    acquire_ws_n(e, n > (mb & ~(size_t)31) ? 2 : 1, ws);
-    struct Release {
-      Engine& e;
-      Workspace** ws;
-      ~Release() {
-        release_ws(e, ws[0]);
-        if (ws[1] && ws[1] != ws[0]) release_ws(e, ws[1]);
-      }
-    } rel{e, ws};
-    std::shared_lock<std::shared_mutex> lk(e.mu);
-    check_request(e, cs, nullptr, n, true, contexts, context_lens, n_contexts);
-    const CavCall cav = caveat_call(e, contexts, context_lens, n_contexts);
-    const uint64_t rev = e.revision;
-    device_check_shaped(e, ws[0], ws[1], shapes, (uint32_t)n_shapes, shape_of, pairs, n, now_us, out_packed, out_errs,
-                        err_cap, out_n_errs, cav);
-    if (out_revision) *out_revision = rev;
+    const CompactReq req =
+        compact_request(shapes, n_shapes, true, shape_of, pairs, n, out_packed, out_errs, err_cap, out_n_errs);
+    check_compact_sync(e, {cs, contexts, context_lens, n_contexts}, req, now_us, out_revision);
   });
 }
 
@@ -1204,37 +1162,11 @@ int gck_check_submit_shaped(gck_engine* ge, const gck_consistency* cs, const gck
     REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
     *out = nullptr;
     check_shapes(shapes, n_shapes, n_contexts);
-    REQUIRE(n == 0 || (shape_of && pairs && out_packed), GCK_E_INVALID_ARGUMENT, "null buffers");
-    REQUIRE(err_cap == 0 || out_errs, GCK_E_INVALID_ARGUMENT, "null error list");
-    if (out_n_errs) *out_n_errs = 0;
-    auto* b = new gck_batch();
-    if (n == 0) {
-      std::shared_lock<std::shared_mutex> lk(e.mu);
-      try {
-        check_request(e, cs, nullptr, 0, true, contexts, context_lens, n_contexts);
-        b->revision = e.revision;
-      } catch (...) {
-        delete b;
-        throw;
-      }
-      *out = b;
-      return;
-    }
-    precheck(e);
-    Workspace* w = acquire_ws(e);
-    try {
-      std::shared_lock<std::shared_mutex> lk(e.mu);
-      check_request(e, cs, nullptr, n, true, contexts, context_lens, n_contexts);
-      b->revision = e.revision;
-      device_submit_shaped(e, w, shapes, (uint32_t)n_shapes, shape_of, pairs, n, now_us, out_packed, out_errs, err_cap,
-                           out_n_errs, caveat_call(e, contexts, context_lens, n_contexts));
-    } catch (...) {
-      release_ws(e, w);
-      delete b;
-      throw;
-    }
-    b->w = w;
-    *out = b;
+    const CompactReq req =
+        compact_request(shapes, n_shapes, true, shape_of, pairs, n, out_packed, out_errs, err_cap, out_n_errs);
+    *out = submit_with(e, {cs, contexts, context_lens, n_contexts}, n, [&](Workspace* w, CavCall cav) {
+      device_submit_compact(e, w, req, now_us, std::move(cav));
+    });
   });
 }
 

@@ -138,6 +138,12 @@ class Uniform(C.Structure):
                 ("subject_relation", C.c_uint16), ("context_slot", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+def _header(h) -> Uniform:
+    """A uniform request's header from (resource_type, permission, subject_type, subject_relation
+    [, context_slot])."""
+    return Uniform(*h[:4], h[4] if len(h) > 4 else 0, 0)
+
+
 # gck_item_error: (index, GCK_ITEM_*) of a uniform request's errored checks
 ITEM_ERROR_DTYPE = np.dtype([("index", "<u4"), ("code", "<i4")])
 
@@ -690,34 +696,43 @@ class Engine:
         unpack_results(words, n) gives the Permissionships. Pinned output arrays (host_array) are
         written in place by the kernels."""
         pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        hdr = _header(header)
+        return self._check_compact(self._lib.gck_check_bulk_uniform, (C.byref(hdr),), pairs, requirement, revision,
+                                   now_us, contexts, out_packed, out_errs)
+
+    def _check_compact(self, fn, head, pairs, requirement, revision, now_us, contexts, out_packed, out_errs):
+        """check_uniform / check_shaped after their own arguments: `head` is what the call names
+        before the pairs (the header; or the table, its length and the index bytes)."""
         n = len(pairs)
         words = out_packed if out_packed is not None else np.zeros((n + 31) // 32, dtype=np.uint64)
         errs = out_errs if out_errs is not None else np.zeros(n, dtype=ITEM_ERROR_DTYPE)
         cs = _Consistency(requirement, 0, revision)
         ctx_arr, ctx_lens, n_ctx = _context_arrays(contexts)
-        hdr = Uniform(*header[:4], header[4] if len(header) > 4 else 0, 0)
         n_errs = C.c_size_t(0)
         rev = C.c_uint64(0)
-        _check(self._lib.gck_check_bulk_uniform(self._h, C.byref(cs), C.byref(hdr), pairs.ctypes.data if n else None,
-                                                n, ctx_arr, ctx_lens, n_ctx, now_us,
-                                                words.ctypes.data if n else None, errs.ctypes.data if len(errs) else None,
-                                                len(errs), C.byref(n_errs), C.byref(rev)))
+        _check(fn(self._h, C.byref(cs), *head, pairs.ctypes.data if n else None, n, ctx_arr, ctx_lens, n_ctx, now_us,
+                  words.ctypes.data if n else None, errs.ctypes.data if len(errs) else None, len(errs),
+                  C.byref(n_errs), C.byref(rev)))
         return words, errs[:min(n_errs.value, len(errs))].copy(), rev.value
 
     def submit_uniform(self, header, pairs: np.ndarray, out_packed: np.ndarray, out_errs: np.ndarray,
                        requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
                        contexts: Optional[Sequence] = None) -> "UniformBatch":
         """gck_check_submit_uniform: the results land in out_packed / out_errs at wait()."""
-        n = len(pairs)
+        hdr = _header(header)
+        return self._submit_compact(self._lib.gck_check_submit_uniform, (C.byref(hdr),),
+                                    UniformBatch(self, hdr, pairs, out_packed, out_errs), requirement, revision,
+                                    now_us, contexts)
+
+    def _submit_compact(self, fn, head, b, requirement, revision, now_us, contexts):
+        """submit_uniform / submit_shaped after their own arguments (`head` as _check_compact's): `b`
+        is the batch to return, holding the arrays the call reads and writes."""
+        n = len(b._pairs)
         cs = _Consistency(requirement, 0, revision)
         ctx_arr, ctx_lens, n_ctx = _context_arrays(contexts)
-        hdr = Uniform(*header[:4], header[4] if len(header) > 4 else 0, 0)
-        b = UniformBatch(self, hdr, pairs, out_packed, out_errs)
-        _check(self._lib.gck_check_submit_uniform(self._h, C.byref(cs), C.byref(hdr), pairs.ctypes.data if n else None,
-                                                  n, ctx_arr, ctx_lens, n_ctx, now_us,
-                                                  out_packed.ctypes.data if n else None,
-                                                  out_errs.ctypes.data if len(out_errs) else None, len(out_errs),
-                                                  C.byref(b._n_errs), C.byref(b._h)))
+        _check(fn(self._h, C.byref(cs), *head, b._pairs.ctypes.data if n else None, n, ctx_arr, ctx_lens, n_ctx,
+                  now_us, b.packed.ctypes.data if n else None, b.errs.ctypes.data if len(b.errs) else None,
+                  len(b.errs), C.byref(b._n_errs), C.byref(b._h)))
         return b
 
     def prepare_uniform(self, headers, pairs, ns, packed, errs, err_cap: int, depth: int,
@@ -746,19 +761,10 @@ class Engine:
         n = len(pairs)
         if len(shape_of) != n:
             raise ValueError("shape_of and pairs differ in length")
-        words = out_packed if out_packed is not None else np.zeros((n + 31) // 32, dtype=np.uint64)
-        errs = out_errs if out_errs is not None else np.zeros(n, dtype=ITEM_ERROR_DTYPE)
-        cs = _Consistency(requirement, 0, revision)
-        ctx_arr, ctx_lens, n_ctx = _context_arrays(contexts)
         table, n_shapes = _shape_table(shapes)
-        n_errs = C.c_size_t(0)
-        rev = C.c_uint64(0)
-        _check(self._lib.gck_check_bulk_shaped(self._h, C.byref(cs), C.addressof(table), n_shapes,
-                                               shape_of.ctypes.data if n else None, pairs.ctypes.data if n else None,
-                                               n, ctx_arr, ctx_lens, n_ctx, now_us, words.ctypes.data if n else None,
-                                               errs.ctypes.data if len(errs) else None, len(errs), C.byref(n_errs),
-                                               C.byref(rev)))
-        return words, errs[:min(n_errs.value, len(errs))].copy(), rev.value
+        head = (C.addressof(table), n_shapes, shape_of.ctypes.data if n else None)
+        return self._check_compact(self._lib.gck_check_bulk_shaped, head, pairs, requirement, revision, now_us,
+                                   contexts, out_packed, out_errs)
 
     def submit_shaped(self, shapes, shape_of: np.ndarray, pairs: np.ndarray, out_packed: np.ndarray,
                       out_errs: np.ndarray, requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0,
@@ -768,17 +774,11 @@ class Engine:
         n = len(pairs)
         if shape_of.dtype != np.uint8 or pairs.dtype != np.uint32 or len(shape_of) != n:
             raise ValueError("submit_shaped takes u8 shape_of and u32 pairs of one length")
-        cs = _Consistency(requirement, 0, revision)
-        ctx_arr, ctx_lens, n_ctx = _context_arrays(contexts)
         table, n_shapes = _shape_table(shapes)
-        b = ShapedBatch(self, (table, shape_of), pairs, out_packed, out_errs)
-        _check(self._lib.gck_check_submit_shaped(self._h, C.byref(cs), C.addressof(table), n_shapes,
-                                                 shape_of.ctypes.data if n else None, pairs.ctypes.data if n else None,
-                                                 n, ctx_arr, ctx_lens, n_ctx, now_us,
-                                                 out_packed.ctypes.data if n else None,
-                                                 out_errs.ctypes.data if len(out_errs) else None, len(out_errs),
-                                                 C.byref(b._n_errs), C.byref(b._h)))
-        return b
+        head = (C.addressof(table), n_shapes, shape_of.ctypes.data if n else None)
+        return self._submit_compact(self._lib.gck_check_submit_shaped, head,
+                                    ShapedBatch(self, (table, shape_of), pairs, out_packed, out_errs), requirement,
+                                    revision, now_us, contexts)
 
     def prepare_shaped(self, shapes, shape_of, pairs, ns, packed, errs, err_cap: int, depth: int,
                        now_us: int = 0) -> "PreparedShaped":
@@ -1068,85 +1068,66 @@ class Engine:
         return items
 
 
-class PreparedRun:
-    """A compiled submit/wait loop with its argument arrays built (Engine.prepare_batches)."""
+class _Prepared:
+    """What the compiled submit/wait loops of libgck_driver.so share: `k` batches through `loop`
+    (a gckd_run* function) and the engine's `submit` entry point, `depth` in flight; the
+    subclass's self._args are the loop's own arguments, marshalled ahead."""
 
-    def __init__(self, engine, items, perms, errs, n, depth, streams, engine_streams, now_us, host):
-        arr = lambda xs: (C.c_uint64 * max(1, len(xs)))(*[int(x) for x in xs])
-        self._e, self._k, self._n, self._depth, self._now, self._host = engine, len(items), n, depth, now_us, host
-        self._items, self._perms, self._errs = arr(items), arr(perms), arr(errs)
-        self._streams = arr(streams or [0])
-        self._flags = SUBMIT_ENGINE_STREAM if engine_streams else 0
+    def __init__(self, engine, loop: str, submit: str, k: int, depth: int):
+        self._e, self._k, self._depth = engine, k, depth
         self._cs = _Consistency(CONSISTENCY_MIN_LATENCY, 0, 0)
         self._drv = _driver()
-        self._submit = C.cast(engine._lib.gck_check_submit, C.c_void_p)
+        self._loop = getattr(self._drv, loop)
+        self._submit = C.cast(getattr(engine._lib, submit), C.c_void_p)
         self._wait = C.cast(engine._lib.gck_check_wait, C.c_void_p)
         self._secs = C.c_double(0.0)
+        self.n_errs = (C.c_size_t * max(1, k))()  # per request (the compact loops)
+        self._args = ()
+
+    @staticmethod
+    def _arr(xs):
+        return (C.c_uint64 * max(1, len(xs)))(*[int(x) for x in xs])
 
     def run(self) -> float:
         """Runs the loop; returns its wall time in seconds (first submit to last wait)."""
-        if self._host:
-            _check(self._drv.gckd_run_host(self._submit, self._wait, self._e._h, C.byref(self._cs), self._k,
-                                           self._items, self._perms, self._errs, self._n, self._depth, self._now,
-                                           C.byref(self._secs)))
-        else:
-            _check(self._drv.gckd_run(self._submit, self._wait, self._e._h, C.byref(self._cs), self._k, self._items,
-                                      self._perms, self._errs, self._n, self._depth, self._streams, self._flags,
-                                      self._now, C.byref(self._secs)))
+        _check(self._loop(self._submit, self._wait, self._e._h, C.byref(self._cs), self._k, *self._args,
+                          C.byref(self._secs)))
         return self._secs.value
 
 
-class PreparedUniform:
+class PreparedRun(_Prepared):
+    """A compiled submit/wait loop with its argument arrays built (Engine.prepare_batches)."""
+
+    def __init__(self, engine, items, perms, errs, n, depth, streams, engine_streams, now_us, host):
+        super().__init__(engine, "gckd_run_host" if host else "gckd_run", "gck_check_submit", len(items), depth)
+        arr = self._arr
+        self._args = (arr(items), arr(perms), arr(errs), n, depth)
+        if not host:
+            self._args += (arr(streams or [0]), SUBMIT_ENGINE_STREAM if engine_streams else 0)
+        self._args += (now_us,)
+
+
+class PreparedUniform(_Prepared):
     """A compiled submit/wait loop over uniform requests with its argument arrays built
     (Engine.prepare_uniform)."""
 
     def __init__(self, engine, headers, pairs, ns, packed, errs, err_cap, depth, now_us):
-        arr = lambda xs: (C.c_uint64 * max(1, len(xs)))(*[int(x) for x in xs])
-        self._e, self._k, self._depth, self._now, self._cap = engine, len(pairs), depth, now_us, err_cap
-        self._hdrs = (Uniform * max(1, len(headers)))(
-            *[Uniform(*h[:4], h[4] if len(h) > 4 else 0, 0) for h in headers])
-        self._pairs, self._ns, self._packed, self._errs = arr(pairs), arr(ns), arr(packed), arr(errs)
-        self.n_errs = (C.c_size_t * max(1, len(pairs)))()
-        self._cs = _Consistency(CONSISTENCY_MIN_LATENCY, 0, 0)
-        self._drv = _driver()
-        self._submit = C.cast(engine._lib.gck_check_submit_uniform, C.c_void_p)
-        self._wait = C.cast(engine._lib.gck_check_wait, C.c_void_p)
-        self._secs = C.c_double(0.0)
-
-    def run(self) -> float:
-        """Runs the loop; returns its wall time in seconds (first submit to last wait)."""
-        _check(self._drv.gckd_run_uniform(self._submit, self._wait, self._e._h, C.byref(self._cs), self._k,
-                                          self._hdrs, self._pairs, self._ns, self._packed, self._errs, self._cap,
-                                          self.n_errs, self._depth, self._now, C.byref(self._secs)))
-        return self._secs.value
+        super().__init__(engine, "gckd_run_uniform", "gck_check_submit_uniform", len(pairs), depth)
+        arr = self._arr
+        hdrs = (Uniform * max(1, len(headers)))(*[_header(h) for h in headers])
+        self._args = (hdrs, arr(pairs), arr(ns), arr(packed), arr(errs), err_cap, self.n_errs, depth, now_us)
 
 
-class PreparedShaped:
+class PreparedShaped(_Prepared):
     """A compiled submit/wait loop over shaped requests with its argument arrays built
     (Engine.prepare_shaped)."""
 
     def __init__(self, engine, shapes, shape_of, pairs, ns, packed, errs, err_cap, depth, now_us):
-        arr = lambda xs: (C.c_uint64 * max(1, len(xs)))(*[int(x) for x in xs])
-        self._e, self._k, self._depth, self._now, self._cap = engine, len(pairs), depth, now_us, err_cap
-        self._tables = [_shape_table(t) for t in shapes]
-        self._shapes = arr([C.addressof(t) for t, _ in self._tables])
-        self._n_shapes = arr([m for _, m in self._tables])
-        self._shape_of, self._pairs, self._ns = arr(shape_of), arr(pairs), arr(ns)
-        self._packed, self._errs = arr(packed), arr(errs)
-        self.n_errs = (C.c_size_t * max(1, len(pairs)))()
-        self._cs = _Consistency(CONSISTENCY_MIN_LATENCY, 0, 0)
-        self._drv = _driver()
-        self._submit = C.cast(engine._lib.gck_check_submit_shaped, C.c_void_p)
-        self._wait = C.cast(engine._lib.gck_check_wait, C.c_void_p)
-        self._secs = C.c_double(0.0)
-
-    def run(self) -> float:
-        """Runs the loop; returns its wall time in seconds (first submit to last wait)."""
-        _check(self._drv.gckd_run_shaped(self._submit, self._wait, self._e._h, C.byref(self._cs), self._k,
-                                         self._shapes, self._n_shapes, self._shape_of, self._pairs, self._ns,
-                                         self._packed, self._errs, self._cap, self.n_errs, self._depth, self._now,
-                                         C.byref(self._secs)))
-        return self._secs.value
+        super().__init__(engine, "gckd_run_shaped", "gck_check_submit_shaped", len(pairs), depth)
+        arr = self._arr
+        self._tables = [_shape_table(t) for t in shapes]  # (kept alive: the loop reads their addresses)
+        self._args = (arr([C.addressof(t) for t, _ in self._tables]), arr([m for _, m in self._tables]),
+                      arr(shape_of), arr(pairs), arr(ns), arr(packed), arr(errs), err_cap, self.n_errs, depth, now_us)
 
 
 class Batch:
