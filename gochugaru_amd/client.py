@@ -28,7 +28,7 @@ from .consistency import Background, Context, Strategy
 from .engine import (CONSISTENCY_AT_LEAST, CONSISTENCY_FULL, CONSISTENCY_MIN_LATENCY,
                      CONSISTENCY_SNAPSHOT, ELLIPSIS, GCK_E_DEVICE, GCK_E_NOT_FOUND, GCK_E_REVISION,
                      ID_ABSENT, ID_WILDCARD, ITEM_ERROR_MESSAGES, PERM_HAS, REL_INVALID, TYPE_INVALID, Engine,
-                     GckError, shape_request, unpack_results)
+                     GckError, shape_request, unpack_cross, unpack_results)
 
 CHECK_ITER_CHUNK = 1000  # client/client.go:166
 
@@ -173,6 +173,53 @@ class Client:
                 return results, CheckItemError(ITEM_ERROR_MESSAGES.get(e, f"item error {e}"))
             results.append(p == PERM_HAS)
         return results, None
+
+    def CheckCross(self, ctx: Optional[Context], cs: Optional[Strategy], permission: str, resources: Iterable[str],
+                   subjects: Iterable[str]) -> Tuple[Optional[List[List[bool]]], Optional[Exception]]:
+        """Every subject against every resource under one permission, as one cross request
+        (Engine.check_cross: the two id lists in, 2-bit results out) — what ``Check`` answers for
+        the len(subjects) x len(resources) relationships ``resource#permission@subject``, without
+        building them. ``resources`` are object strings of one type ("document:readme"), ``subjects``
+        of one kind ("user:jimmy", or all "group:eng#member"); mixed types are InvalidArgument.
+        Returns ``(rows, err)``: rows[s][r] is True iff subject s HAS the permission on resource r
+        (NO and CONDITIONAL are False, an unknown name is a nonexistent object). The first per-item
+        error, in row-major order, returns the rows up to it and a CheckItemError, as ``Check``."""
+        self.checkOverlap(ctx)
+        try:
+            res = [_rel.ParseObjectSet(r) for r in resources]
+            sub = [_rel.ParseObjectSet(s) for s in subjects]
+            if len({t for t, _, _ in res}) > 1 or any(rel for _, _, rel in res):
+                raise InvalidArgument("CheckCross: the resources must be objects of one type")
+            if len({(t, rel if rel not in ("", "...") else "") for t, _, rel in sub}) > 1:
+                raise InvalidArgument("CheckCross: the subjects must be of one type and relation")
+            if not res or not sub:
+                return [[] for _ in sub], None
+            requirement, revision = _requirement(cs)
+            eng = self.engine
+            S, R = len(sub), len(res)
+
+            def attempt():
+                # interned per attempt, as Check does
+                rt, st = eng.type_id(res[0][0]), eng.type_id(sub[0][0])
+                srel = ELLIPSIS if sub[0][2] in ("", "...") else eng.relation_id(st, sub[0][2])
+                rids = eng.intern(rt, [i for _, i, _ in res]) if rt != TYPE_INVALID else [ID_ABSENT] * R
+                if st != TYPE_INVALID:
+                    sids = eng.intern(st, [i for _, i, _ in sub])
+                else:
+                    sids = [ID_WILDCARD if i == "*" else ID_ABSENT for _, i, _ in sub]
+                header = (rt, eng.relation_id(rt, permission), st, srel)
+                words, errs, _ = eng.check_cross(header, sids, rids, requirement, revision)
+                return unpack_cross(words, S, R), errs
+            perm, errs = retryRetriableErrors(ctx or Background, attempt)
+            has = (perm == PERM_HAS)
+            if not len(errs):
+                return has.tolist(), None
+            at, e = int(errs[0]["index"]), int(errs[0]["code"])
+            rows = has[:at // R].tolist()
+            rows.append(has[at // R, :at % R].tolist())
+            return rows, CheckItemError(ITEM_ERROR_MESSAGES.get(e, f"item error {e}"))
+        except Exception as e:  # noqa: BLE001 — Go returns (nil, err)
+            return None, e
 
     def CheckOne(self, ctx, cs, r) -> Tuple[bool, Optional[Exception]]:
         results, err = self.Check(ctx, cs, r)

@@ -343,13 +343,44 @@ static void aql_put_shapes(const AqlState& st, Workspace& w, const gck_uniform* 
   if (wrote && w.aql_devargs) aql_hdp_flush(st);
 }
 
+// A cross batch's id block (closure.inc CjArgs::cols) behind the shape-table block, in the same
+// allocation and written the same way: the tile's resource ids, then its subject ids from word
+// cross_sub_off(cols); only the 16-B lines that differ from what the block holds — a tile that
+// moves along a row band rewrites the resource ids alone, a caller paging through resources for
+// one subject likewise — then one HDP flush. GCK_CROSS_IDS ids and the 12 B the subjects' alignment
+// can take.
+constexpr size_t kAqlIdsBytes = (size_t)GCK_CROSS_IDS * 4 + 16;
+static void aql_put_ids(const AqlState& st, Workspace& w, const uint32_t* resources, uint32_t cols, const uint32_t* subjects,
+                        uint32_t rows) {
+  static_assert(sizeof(w.ids_shadow) == kAqlIdsBytes, "id block shadow size");
+  const size_t sub = (size_t)cross_sub_off(cols) * 4, end = sub + (size_t)rows * 4;
+  if (end > kAqlIdsBytes) throw Error(GCK_E_DEVICE, "engine invariant violated: cross tile beyond the id block");
+  auto* dst = static_cast<unsigned char*>(w.aql_ids);
+  bool wrote = false;
+  // (each list begins a 16-B line; the words between the resource ids' end and `sub` are never read)
+  auto put = [&](size_t at, const uint32_t* ids, size_t len) {
+    const auto* src = reinterpret_cast<const unsigned char*>(ids);
+    for (size_t o = 0; o < len; o += 16) {
+      const size_t n = std::min<size_t>(16, len - o);
+      if (std::memcmp(src + o, w.ids_shadow + at + o, n) == 0) continue;
+      std::memcpy(dst + at + o, src + o, n);
+      std::memcpy(w.ids_shadow + at + o, src + o, n);
+      wrote = true;
+    }
+  };
+  put(0, resources, (size_t)cols * 4);
+  put(sub, subjects, (size_t)rows * 4);
+  if (wrote && w.aql_devargs) aql_hdp_flush(st);
+}
+
+constexpr size_t kAqlBlockBytes = kAqlKernargBytes + kAqlShapesBytes + kAqlIdsBytes;
 static bool aql_workspace(AqlState& st, Workspace& w) {
   if (w.aql_kernarg) return true;
   void* p = nullptr;
   if (st.devargs) {  // a VRAM block the host may write (zeroed: a kernel reading it does nothing)
-    if (hsa_amd_memory_pool_allocate(st.pool, kAqlKernargBytes + kAqlShapesBytes, 0, &p) == HSA_STATUS_SUCCESS) {
+    if (hsa_amd_memory_pool_allocate(st.pool, kAqlBlockBytes, 0, &p) == HSA_STATUS_SUCCESS) {
       if (hsa_amd_agents_allow_access(1, &st.cpu, nullptr, p) == HSA_STATUS_SUCCESS) {
-        std::memset(p, 0, kAqlKernargBytes + kAqlShapesBytes);
+        std::memset(p, 0, kAqlBlockBytes);
         aql_hdp_flush(st);
         w.aql_devargs = true;
       } else {
@@ -359,9 +390,8 @@ static bool aql_workspace(AqlState& st, Workspace& w) {
     }
   }
   if (!p) {  // (no HDP flush register: pinned host memory, zeroed as the VRAM block is)
-    if (hipHostMalloc(&p, kAqlKernargBytes + kAqlShapesBytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess)
-      return false;
-    std::memset(p, 0, kAqlKernargBytes + kAqlShapesBytes);
+    if (hipHostMalloc(&p, kAqlBlockBytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) return false;
+    std::memset(p, 0, kAqlBlockBytes);
   }
   hsa_signal_t s;
   // (GCK_DEBUG_AQL_SIGNAL: a signal without the completion interrupt — the host only spins on it —
@@ -378,6 +408,8 @@ static bool aql_workspace(AqlState& st, Workspace& w) {
   w.aql_kernarg = p;
   w.aql_shapes = static_cast<unsigned char*>(p) + kAqlKernargBytes;
   std::memset(w.shapes_shadow, 0, sizeof(w.shapes_shadow));
+  w.aql_ids = static_cast<unsigned char*>(p) + kAqlKernargBytes + kAqlShapesBytes;
+  std::memset(w.ids_shadow, 0, sizeof(w.ids_shadow));
   w.aql_signal = s.handle;
   return true;
 }
@@ -392,6 +424,7 @@ static void aql_workspace_free(Workspace& w) {
   else if (w.aql_kernarg) (void)hipHostFree(w.aql_kernarg);
   w.aql_kernarg = nullptr;
   w.aql_shapes = nullptr;
+  w.aql_ids = nullptr;
   w.aql_devargs = false;
   w.aql_queue = nullptr;
 }

@@ -135,7 +135,12 @@ struct CjArgs {
     };
   };
   uint32_t n_shapes;  // 0: not shaped
-  uint32_t cold_pad[1];
+  // a cross batch (gck_check_bulk_cross; kCjGrid, with `pairs`): `pairs` is the workspace's id block
+  // — the tile's `cols` resource ids, then its subject ids from word cross_sub_off(cols) — and check
+  // i of the n = rows * wpr * 32 (wpr = ceil(cols / 32)) is row (i / 32) / wpr, column
+  // 32 * ((i / 32) % wpr) + i % 32 (cross_rc); a column >= cols is padding: the lane is idle and its
+  // result bits are 0. The header is u_rp / u_ss / u_ctx. 0: not a cross batch.
+  uint32_t cols;
 };
 // CjArgs::mode beside kPubCoherent | kPubBySignal (engine.hip)
 constexpr uint32_t kCjUniform = 4u;   // pairs != null
@@ -143,6 +148,7 @@ constexpr uint32_t kCjBadSlot = 8u;   // bad_slot != null
 constexpr uint32_t kCjSelfPub = 16u;  // h_out != null
 constexpr uint32_t kCjTimed = 32u;    // timing != null
 constexpr uint32_t kCjShaped = 64u;   // n_shapes != 0 (with kCjUniform)
+constexpr uint32_t kCjGrid = 128u;    // cols != 0 (with kCjUniform, never with kCjShaped)
 
 struct CjHot {  // the hot line as the kernel holds it (scalar registers)
   const gck_item* items;
@@ -172,7 +178,8 @@ static_assert((sizeof(Ctx) + kCjHotOff) % 64 == 0, "the hot line is one 64-B lin
 // the launch, the dispatch or the post).
 inline void cj_seal(CjArgs& j) {
   j.mode = (j.mode & (kPubCoherent | kPubBySignal)) | (j.pairs ? kCjUniform : 0u) | (j.bad_slot ? kCjBadSlot : 0u) |
-           (j.h_out ? kCjSelfPub : 0u) | (j.timing ? kCjTimed : 0u) | (j.pairs && j.n_shapes ? kCjShaped : 0u);
+           (j.h_out ? kCjSelfPub : 0u) | (j.timing ? kCjTimed : 0u) | (j.pairs && j.n_shapes ? kCjShaped : 0u) |
+           (j.pairs && !j.n_shapes && j.cols ? kCjGrid : 0u);
 }
 // The staged bytes of a table of `bytes` bytes (its device buffer is allocated to this size).
 constexpr uint32_t cj_table_bytes(size_t bytes) { return (uint32_t)((bytes + 15) & ~(size_t)15); }
@@ -236,6 +243,24 @@ __device__ __forceinline__ gck_item uniform_item(uint32_t rp, uint32_t ss, uint3
   it.subject_id = sub;
   it.context_slot = ctx;
   return it;
+}
+
+// A cross batch's id block (CjArgs::cols): the word at which the subject ids begin — behind the
+// tile's resource ids, on a 16-B line of its own (the host rewrites the block line by line).
+__host__ __device__ constexpr uint32_t cross_sub_off(uint32_t cols) { return (cols + 3u) & ~3u; }
+// ... and the (row, column) of the check whose result is bit pair `bit` of the tile's word `word`
+// (wpr words per row). The join calls it with a wave-uniform word: a scalar division.
+__host__ __device__ __forceinline__ void cross_rc(uint32_t word, uint32_t bit, uint32_t wpr, uint32_t& row, uint32_t& col) {
+  row = word / wpr;
+  col = (word - row * wpr) * 32u + bit;
+}
+// A cross batch's check, read again by (row, column) by the rare check the join leaves to the
+// bundle stages: its resource id and its subject id from the id block.
+__device__ __forceinline__ void cross_ids_again(const uint32_t* ids, uint32_t cols, uint32_t i, uint32_t& res, uint32_t& sub) {
+  uint32_t row, col;
+  cross_rc(i >> 5, i & 31u, (cols + 31u) >> 5, row, col);
+  res = *(const GCK_GLOBAL uint32_t*)(ids + col);
+  sub = *(const GCK_GLOBAL uint32_t*)(ids + cross_sub_off(cols) + row);
 }
 
 // The packed results of a uniform batch: lane l of a wave whose first check is w0 (a multiple of
@@ -694,13 +719,38 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
   if (items_early && lane < 40)
     item_chunk = *(const GCK_GLOBAL u32x4*)(reinterpret_cast<const unsigned char*>(a.items) + (size_t)w0 * 20u + lane * 16u);
   // a uniform batch: each lane its own check's 8-B pair, requested before the table as the items
-  // are (into the same registers)
+  // are (into the same registers; not a cross batch's lanes: `pairs` is then the id block)
+  const bool grid = (a.mode & kCjGrid) != 0u;
   if (uni) {
     const uint32_t* pairs = ax.cold()->pairs;
-    if ((uint32_t)lane < CPW && w0 + (uint32_t)lane < a.n) {
+    if ((uint32_t)lane < CPW && w0 + (uint32_t)lane < a.n && !grid) {
       const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(pairs + 2ull * (w0 + (uint32_t)lane));
       item_chunk.x = (uint32_t)pr;
       item_chunk.y = (uint32_t)(pr >> 32);
+    }
+  }
+  // a cross batch: in the same round the lane's resource id (32 consecutive words per result word:
+  // one request) and its row's subject id (one address per result word) from the id block, into
+  // the chunk's two spare registers (.z, .w; a shaped batch's index byte uses .z, and a cross batch
+  // is never shaped) until the table's barrier — a branch of its own, shaped like the shaped
+  // batch's below: as the other arm of the pair's load it made the compiler wait for the uniform
+  // mode's pair before it issued the table's loads. A lane whose column is padding loads nothing
+  // and stays idle (grid_on)
+  bool grid_on = true;
+  if (__builtin_expect(grid, 0)) {
+    const auto cold = ax.cold();
+    const uint32_t* ids = cold->pairs;
+    const uint32_t cols = cold->cols, wpr = (cols + 31u) >> 5;
+    uint32_t row, col;  // (the wave's first word: scalar; a wave of 64 checks holds two words)
+    cross_rc((uint32_t)__builtin_amdgcn_readfirstlane((int)(w0 >> 5)), (uint32_t)lane & 31u, wpr, row, col);
+    if (CPW == 64 && lane >= 32) {
+      col += 32u;
+      if (col >= wpr * 32u) col -= wpr * 32u, ++row;
+    }
+    grid_on = col < cols;
+    if ((uint32_t)lane < CPW && w0 + (uint32_t)lane < a.n && grid_on) {
+      item_chunk.z = *(const GCK_GLOBAL uint32_t*)(ids + col);
+      item_chunk.w = *(const GCK_GLOBAL uint32_t*)(ids + cross_sub_off(cols) + row);
     }
   }
   // a shaped batch: in the same round each check lane its index byte (32 consecutive bytes per
@@ -739,11 +789,12 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
   // (after the table's loads were issued: the entries' wait is the table's)
   if (__builtin_expect(shaped, 0) && (uint32_t)lane < n_shapes) *reinterpret_cast<u32x4*>(&s_item_w[lane * 4u]) = shape_ent;
   __syncthreads();
+  if (__builtin_expect(grid, 0)) item_chunk.x = item_chunk.z, item_chunk.y = item_chunk.w;
   const uint16_t* root = reinterpret_cast<const uint16_t*>(s_tab);
   const CjMeta* meta = reinterpret_cast<const CjMeta*>(s_tab + a.o_meta);
   const CjEntry* ent = reinterpret_cast<const CjEntry*>(s_tab + a.o_entries);
   const uint32_t i = (blk * kWaves + wib) * CPW + lane;
-  const bool active = (uint32_t)lane < CPW && i < a.n;
+  const bool active = (uint32_t)lane < CPW && i < a.n && grid_on;
   const unsigned long long t_tab = timed ? wall_clock64() : 0ull;
   // (the task rounds below: row extents of what the slots left, then V(R), G(u), signatures, probes)
   bool take = false, self = false;
@@ -1169,11 +1220,17 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
       base = (uint32_t)__shfl((int)base, leader, 64);
       if (left) cold->deferred[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
       if (left && uni) {  // the check's item where the bundle stages read it (its pair read again: rare)
-        const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(cold->pairs + 2ull * i);
-        if (shaped)
-          cold->items_out[i] = shaped_item_again(cold->shape_of, cold->shapes, n_shapes, i, (uint32_t)pr, (uint32_t)(pr >> 32));
-        else
-          cold->items_out[i] = uniform_item(cold->u_rp, cold->u_ss, cold->u_ctx, (uint32_t)pr, (uint32_t)(pr >> 32));
+        if (a.mode & kCjGrid) {  // (a cross batch: its two ids by (row, column))
+          uint32_t res, sub;
+          cross_ids_again(cold->pairs, cold->cols, i, res, sub);
+          cold->items_out[i] = uniform_item(cold->u_rp, cold->u_ss, cold->u_ctx, res, sub);
+        } else {
+          const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(cold->pairs + 2ull * i);
+          if (shaped)
+            cold->items_out[i] = shaped_item_again(cold->shape_of, cold->shapes, n_shapes, i, (uint32_t)pr, (uint32_t)(pr >> 32));
+          else
+            cold->items_out[i] = uniform_item(cold->u_rp, cold->u_ss, cold->u_ctx, (uint32_t)pr, (uint32_t)(pr >> 32));
+        }
       }
     }
   }

@@ -20,6 +20,9 @@ using submit_uniform_fn = int (*)(gck_engine*, const gck_consistency*, const gck
 using submit_shaped_fn = int (*)(gck_engine*, const gck_consistency*, const gck_uniform*, size_t, const uint8_t*,
                                  const uint32_t*, size_t, const char* const*, const size_t*, size_t, int64_t, uint64_t*,
                                  gck_item_error*, size_t, size_t*, gck_batch**);
+using submit_cross_fn = int (*)(gck_engine*, const gck_consistency*, const gck_uniform*, const uint32_t*, size_t,
+                                const uint32_t*, size_t, const char* const*, const size_t*, size_t, int64_t, uint64_t*,
+                                gck_item_error*, size_t, size_t*, gck_batch**);
 
 // Optional per-batch timeline of the next loops (gckd_set_trace): for batch k, the seconds after
 // the loop's start at which its submit and its wait returned (stamps[2k], stamps[2k + 1]).
@@ -124,6 +127,22 @@ int gckd_run_shaped(submit_shaped_fn submit, wait_fn wait, gck_engine* e, const 
                   reinterpret_cast<const uint8_t*>(shape_of[k]), reinterpret_cast<const uint32_t*>(pairs[k]), (size_t)ns[k],
                   nullptr, nullptr, 0, now_us, reinterpret_cast<uint64_t*>(packed[k]),
                   reinterpret_cast<gck_item_error*>(errs[k]), err_cap, n_errs ? n_errs + k : nullptr, b);
+  });
+}
+
+// The same loop over cross requests (gck_check_submit_cross): request k = header hdrs[k], the
+// n_subjects[k] subject ids subjects[k] and the n_resources[k] resource ids resources[k] in;
+// packed[k] (n_subjects[k] rows of ceil(n_resources[k] / 32) words) and errs[k] out — 4 B per id
+// instead of 8 B per check.
+int gckd_run_cross(submit_cross_fn submit, wait_fn wait, gck_engine* e, const gck_consistency* cs, size_t n_batches,
+                   const gck_uniform* hdrs, const uint64_t* subjects, const uint64_t* n_subjects,
+                   const uint64_t* resources, const uint64_t* n_resources, const uint64_t* packed, const uint64_t* errs,
+                   size_t err_cap, size_t* n_errs, uint32_t depth, int64_t now_us, double* seconds) {
+  return run_loop(n_batches, depth, wait, e, seconds, [&](size_t k, gck_batch** b) {
+    return submit(e, cs, hdrs + k, reinterpret_cast<const uint32_t*>(subjects[k]), (size_t)n_subjects[k],
+                  reinterpret_cast<const uint32_t*>(resources[k]), (size_t)n_resources[k], nullptr, nullptr, 0, now_us,
+                  reinterpret_cast<uint64_t*>(packed[k]), reinterpret_cast<gck_item_error*>(errs[k]), err_cap,
+                  n_errs ? n_errs + k : nullptr, b);
   });
 }
 

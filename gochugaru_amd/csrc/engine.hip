@@ -215,6 +215,14 @@ struct CompactRun {
   gck_item_error* errs = nullptr;            // a submitted batch: the caller's error list (device_wait)
   size_t err_cap = 0;
   size_t* n_errs = nullptr;
+  // a cross request's batch (CompactReq::cross; `out` is the whole row-padded plane, R the request's
+  // resources). In place: the tile rows x cols at (row0, col0) — the batch is its padded checks,
+  // rows * ceil(cols / 32) * 32, `pad` of them idle — whose dense words the wait copies row by row
+  // into the plane. Expanded: the checks [pos, pos + n) of the request, row-major.
+  bool cross = false;
+  uint32_t rows = 0, cols = 0, row0 = 0, col0 = 0, pad = 0;
+  size_t R = 0;
+  bool grid() const { return mode == kInPlace && cross; }  // the join reads the id block
   bool in_place() const { return mode == kInPlace; }
   bool table_join() const { return mode == kInPlace && indexed; }  // the join reads index bytes and a shape table
 };
@@ -267,6 +275,8 @@ struct Workspace {
   CompactBatch cb;            // the batch is a compact request's chunk (submit_compact)
   void* aql_shapes = nullptr;   // aql.inc: the shape table the join reads (GCK_MAX_SHAPES entries, memory as aql_kernarg)
   alignas(16) unsigned char shapes_shadow[GCK_MAX_SHAPES * sizeof(gck_uniform)] = {};  // ... what it holds now
+  void* aql_ids = nullptr;      // aql.inc: the id block a cross batch's join reads (behind the shape table)
+  alignas(16) unsigned char ids_shadow[GCK_CROSS_IDS * 4 + 16] = {};  // ... what it holds now
   void* aql_kernarg = nullptr;  // aql.inc: kernarg block of the dispatched join (pinned host memory, or VRAM)
   bool aql_devargs = false;     // ... in VRAM (aql.inc AqlState::devargs)
   uint64_t aql_signal = 0;      // aql.inc: its completion signal (hsa_signal_t handle)
@@ -2554,9 +2564,10 @@ static bool join_on(const Engine& e) {
 // A batch over host memory can run zero-copy: its join, dispatched into the engine's queues, reads
 // the request from and writes the results into pinned host memory (submit_batch, submit_compact).
 // Not with check contexts, nor profiled (GCK_AQL=0 or a profiled batch take the DMA path).
-static bool zero_copy_ok(const Engine& e, const Workspace& w) {
-  return e.aql && w.aql_kernarg && !w.cav_on && !(e.cfg.flags & (GCK_FLAG_PROFILE | GCK_FLAG_NO_BUNDLE)) && join_on(e);
+static bool zero_copy_with(const Engine& e, const Workspace& w, bool cav_on) {
+  return e.aql && w.aql_kernarg && !cav_on && !(e.cfg.flags & (GCK_FLAG_PROFILE | GCK_FLAG_NO_BUNDLE)) && join_on(e);
 }
+static bool zero_copy_ok(const Engine& e, const Workspace& w) { return zero_copy_with(e, w, w.cav_on); }
 
 // An AQL-dispatched join reports through per-block summaries (closure.inc block_summary): its
 // arguments point at the workspace's slots, and its deferred-list counter is one of two words that
@@ -2611,6 +2622,8 @@ static void uniform_args(const Workspace& w, Args& j) {
     j.shape_of = c.shape_of;
     j.shapes = static_cast<const gck_uniform*>(w.aql_shapes);
     j.n_shapes = c.n_shapes;
+  } else if (c.grid()) {  // (a cross batch: `pairs` is the workspace's id block; the word is 0 otherwise)
+    j.cols = c.cols;
   }
   j.items = nullptr;
 }
@@ -2831,9 +2844,10 @@ static void closure_join_start(Engine& e, Workspace& w, const Route& r, const Ct
     aql_summaries(w, cj_args.j.mode, cj_args.j.h_out, cj_args.j.done, cj_args.j.n_deferred, grid.x);
   // the resident join (resident.inc) takes the request without a dispatch of its own
   // (a shaped batch is dispatched: the running launch would read the workspace's shape table, which
-  // the host rewrites between requests, without a dispatch's acquire in between)
+  // the host rewrites between requests, without a dispatch's acquire in between; a cross batch
+  // likewise: its id block)
   const bool res_ok = ak && e.res && !r.timed && w.b_sum_blocks == grid.x && (cj_args.j.mode & kPubBySignal) &&
-                      !w.cb.table_join();
+                      !w.cb.table_join() && !w.cb.grid();
   if (res_ok) {
     aql_after_build(e);
     res_post(e, w, cj_args.j, grid.x);
@@ -2949,11 +2963,13 @@ static float bundles_finish(Engine& e, Workspace& w) {
     // the join counts only its task-round checks (DevCounters::closure; usually none, so usually
     // no atomic): the rest of what it answered came from the slots
     const unsigned long long tasks = w.h_ctr->closure;
-    if (tasks > n - n_cj) throw Error(GCK_E_DEVICE, "engine invariant violated: closure-join task count");
+    // (a cross tile's padding lanes are no checks: neither answered nor left)
+    const uint32_t n_real = n - (w.cb.grid() ? w.cb.pad : 0u);
+    if (n_cj > n_real || tasks > n_real - n_cj) throw Error(GCK_E_DEVICE, "engine invariant violated: closure-join task count");
     std::lock_guard<std::mutex> lk(e.stats_mu);
-    e.stats.closure_checks += n - n_cj;
-    e.stats.slot_checks += n - n_cj - tasks;
-    if (w.b_label) e.stats.label_checks += n - n_cj;
+    e.stats.closure_checks += n_real - n_cj;
+    e.stats.slot_checks += n_real - n_cj - tasks;
+    if (w.b_label) e.stats.label_checks += n_real - n_cj;
     if (w.b_aql) e.stats.aql_batches++;
     if (w.b_res) e.stats.resident_batches++;
   }
@@ -3039,7 +3055,7 @@ static float bundles_finish(Engine& e, Workspace& w) {
       e.stats.giant_ms += gm;
       e.stats.bundle_launches++;
     }
-    e.stats.queries += n;
+    e.stats.queries += n - (w.cb.grid() ? w.cb.pad : 0u);
     e.stats.batches++;
     e.stats.deferred += n_def;
     e.stats.deferred_wide += n_def2;
@@ -3606,10 +3622,11 @@ static void compact_expand(const CompactReq& q, size_t pos, std::vector<gck_item
     gck_item& it = items[k];
     it.resource_type = h.resource_type;
     it.permission = h.permission;
-    it.resource_id = q.pairs[2 * (pos + k)];
+    // (a cross request: check pos + k is subject (pos + k) / R against resource (pos + k) % R)
+    it.resource_id = q.cross() ? q.resources[(pos + k) % q.R] : q.pairs[2 * (pos + k)];
     it.subject_type = h.subject_type;
     it.subject_relation = h.subject_relation;
-    it.subject_id = q.pairs[2 * (pos + k) + 1];
+    it.subject_id = q.cross() ? q.subjects[(pos + k) / q.R] : q.pairs[2 * (pos + k) + 1];
     it.context_slot = h.context_slot;
   }
 }
@@ -3635,29 +3652,70 @@ static void compact_stage(Engine& e, Workspace& w, const uint32_t* pairs, const 
   c.packed = host_pinned(e, c.out, words * 8u) ? c.out : reinterpret_cast<unsigned long long*>(w.h_err);
 }
 
-// Queues the chunk [pos, pos + len) of the request on w (pos: a multiple of 32).
+// A cross request's tile when it runs in place on the workspaces given (w1 may be null): the
+// in-place condition of a uniform chunk, the workspace's id block, and a tile from the tiling rule.
+static bool cross_plan(const Engine& e, const Workspace* w0, const Workspace* w1, const CavCall& cav, CompactReq& q) {
+  q.tile_rows = q.tile_cols = 0;
+  for (const Workspace* w : {w0, w1})
+    if (w && !(zero_copy_with(e, *w, cav.n_ctx > 0) && w->aql_ids)) return false;
+  uint32_t rows = 0, cols = 0;
+  if (!gck_cross_tile(q.S, q.R, w0->max_batch, &rows, &cols)) return false;
+  q.tile_rows = rows;
+  q.tile_cols = cols;
+  return true;
+}
+static size_t cross_tiles(const CompactReq& q) {
+  return ((q.S + q.tile_rows - 1) / q.tile_rows) * ((q.R + q.tile_cols - 1) / q.tile_cols);
+}
+
+// Queues the chunk [pos, pos + len) of the request on w (pos: a multiple of 32); of a cross request
+// in place (q.tile_rows != 0): its tile number pos, left to right and top to bottom.
 static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t pos, uint32_t len, int64_t now_us) {
   CompactRun c;
   c.indexed = q.shape_of != nullptr;
   c.n_shapes = q.n_shapes;
   c.pos = pos;
-  c.out = reinterpret_cast<unsigned long long*>(q.packed + pos / 32);
+  c.cross = q.cross();
+  c.R = q.R;
+  // (a cross batch's words go to their rows of the whole plane: uniform_collect)
+  c.out = reinterpret_cast<unsigned long long*>(c.cross ? q.packed : q.packed + pos / 32);
   c.errs = q.errs;  // (read by device_wait only: a synchronous request's chunks are collected by its caller)
   c.err_cap = q.err_cap;
   c.n_errs = q.n_errs;
+  const auto header = [&] {  // kernel input mode: the one header in the kernarg words, not a table of one (uniform_args)
+    const gck_uniform& h = q.shapes[0];
+    c.rp = (uint32_t)h.resource_type | (uint32_t)h.permission << 16;
+    c.ss = (uint32_t)h.subject_type | (uint32_t)h.subject_relation << 16;
+    c.ctx = h.context_slot;
+  };
+  if (c.cross && q.tile_rows) {
+    // the tile's ids into the workspace's id block; its join writes the tile's words densely into
+    // the pinned result staging (wave w word w, as a uniform batch's)
+    const size_t per_band = (q.R + q.tile_cols - 1) / q.tile_cols;
+    c.pos = 0;
+    c.row0 = (uint32_t)(pos / per_band) * q.tile_rows;
+    c.col0 = (uint32_t)(pos % per_band) * q.tile_cols;
+    c.rows = (uint32_t)std::min<size_t>(q.tile_rows, q.S - c.row0);
+    c.cols = (uint32_t)std::min<size_t>(q.tile_cols, q.R - c.col0);
+    const uint32_t padded = c.rows * ((c.cols + 31u) / 32u) * 32u;
+    if (padded > w.max_batch) throw Error(GCK_E_DEVICE, "engine invariant violated: cross tile above max_batch");
+    c.pad = padded - c.rows * c.cols;
+    c.mode = CompactRun::kInPlace;
+    aql_put_ids(*e.aql, w, q.resources + c.col0, c.cols, q.subjects + c.row0, c.rows);
+    c.pairs = static_cast<const uint32_t*>(w.aql_ids);
+    c.packed = reinterpret_cast<unsigned long long*>(w.h_err);
+    header();
+    submit_batch(e, w, w.d_items, padded, now_us, w.d_perm, w.d_err, w.stream, BatchMem::kEngineStream, c);
+    e.cross_in_place.fetch_add(1, std::memory_order_relaxed);
+    return;
+  }
   // in-place condition: a uniform chunk runs in place when a host batch could run zero-copy; a
-  // shaped chunk also needs the workspace's table block
-  if (zero_copy_ok(e, w) && (!c.indexed || w.aql_shapes)) {
+  // shaped chunk also needs the workspace's table block (a cross request's: cross_plan, above)
+  if (!c.cross && zero_copy_ok(e, w) && (!c.indexed || w.aql_shapes)) {
     c.mode = CompactRun::kInPlace;
     compact_stage(e, w, q.pairs + 2 * pos, c.indexed ? q.shape_of + pos : nullptr, len, c);
-    if (c.indexed) {
-      aql_put_shapes(*e.aql, w, q.shapes, q.n_shapes);
-    } else {  // kernel input mode: the one header in the kernarg words, not a table of one (uniform_args)
-      const gck_uniform& h = q.shapes[0];
-      c.rp = (uint32_t)h.resource_type | (uint32_t)h.permission << 16;
-      c.ss = (uint32_t)h.subject_type | (uint32_t)h.subject_relation << 16;
-      c.ctx = h.context_slot;
-    }
+    if (c.indexed) aql_put_shapes(*e.aql, w, q.shapes, q.n_shapes);
+    else header();
     submit_batch(e, w, w.d_items, len, now_us, w.d_perm, w.d_err, w.stream, BatchMem::kEngineStream, c);
   } else {
     c.mode = CompactRun::kExpanded;
@@ -3669,6 +3727,21 @@ static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t 
   }
   // (gck_shaped_stats counts shaped chunks only, one count per chunk)
   if (c.indexed) (c.in_place() ? e.shaped_in_place : e.shaped_expanded).fetch_add(1, std::memory_order_relaxed);
+  if (c.cross) e.cross_expanded.fetch_add(1, std::memory_order_relaxed);  // (gck_cross_stats: its chunks, likewise)
+}
+
+// The place of a cross batch's check i in its request: in place, i counts the tile's padded checks
+// (closure.inc cross_rc); expanded, the chunk's. s: its subject, r: its resource.
+static void cross_place(const CompactRun& c, uint32_t i, size_t& s, size_t& r) {
+  if (c.in_place()) {
+    uint32_t row, col;
+    cross_rc(i >> 5, i & 31u, (c.cols + 31u) / 32u, row, col);
+    s = (size_t)c.row0 + row;
+    r = (size_t)c.col0 + col;
+  } else {
+    s = (c.pos + i) / c.R;
+    r = (c.pos + i) % c.R;
+  }
 }
 
 // After a compact batch has finished (finish_batch, copy_out): its words into the caller's buffer
@@ -3689,11 +3762,35 @@ static void uniform_collect(Workspace& w, std::vector<gck_item_error>& errs) {
       HIP_OK(hipStreamSynchronize(w.stream));
       for (uint32_t i : idx) {
         if (i >= n) throw Error(GCK_E_DEVICE, "engine invariant violated: deferred index");
-        if (c.err[i]) errs.push_back(gck_item_error{pos + i, c.err[i]});
+        uint32_t at = pos + i;  // the check's index in its request (a cross tile's padded i: its s * R + r)
+        if (c.cross) {
+          size_t s, r;
+          cross_place(c, i, s, r);
+          at = (uint32_t)(s * c.R + r);
+        }
+        if (c.err[i]) errs.push_back(gck_item_error{at, c.err[i]});
         else out[i >> 5] |= (unsigned long long)(c.perm[i] & 3u) << (2u * (i & 31u));
       }
     }
-    if (out != c.out) std::memcpy(c.out, out, words * 8u);
+    if (c.cross) {  // each tile row to its place in the caller's plane (col0 is a multiple of 32)
+      const size_t wpr = (c.cols + 31u) / 32u, stride = (c.R + 31u) / 32u;
+      for (uint32_t row = 0; row < c.rows; ++row)
+        std::memcpy(c.out + ((size_t)c.row0 + row) * stride + c.col0 / 32u, out + row * wpr, wpr * 8u);
+    } else if (out != c.out) {
+      std::memcpy(c.out, out, words * 8u);
+    }
+  } else if (c.cross) {
+    // an expanded cross chunk: rows end inside words of the chunk's sequence, so each result is put
+    // at its own place in the plane. A row is cleared by the chunk that holds its first check
+    // (chunks complete in order, so a row continued here was opened by an earlier one)
+    const size_t stride = (c.R + 31u) / 32u;
+    for (uint32_t i = 0; i < n; ++i) {
+      size_t s, r;
+      cross_place(c, i, s, r);
+      if (r == 0) std::memset(c.out + s * stride, 0, stride * 8u);
+      if (c.err[i]) errs.push_back(gck_item_error{pos + i, c.err[i]});
+      else c.out[s * stride + r / 32u] |= (unsigned long long)(c.perm[i] & 3u) << (2u * (r % 32u));
+    }
   } else {
     for (size_t k = 0; k < words; ++k) {
       unsigned long long x = 0;
@@ -3720,9 +3817,13 @@ void device_submit_compact(Engine& e, Workspace* w, const CompactReq& req, int64
   HIP_OK(hipSetDevice(e.device));
   std::lock_guard<std::mutex> lk(w->m);
   if (req.n > w->max_batch) throw Error(GCK_E_INVALID_ARGUMENT, "submitted batch above max_batch");
+  CompactReq q = req;
+  // (a submitted cross request is one tile by the tiling rule — checked by the entry point — so
+  // in place it is tile 0 and expanded it is one chunk: S * R <= its padded size <= max_batch)
+  if (q.cross()) cross_plan(e, w, nullptr, cav, q);
   stage_caveats(*w, std::move(cav), w->stream);
   if (now_us == 0) now_us = wall_now_us();
-  submit_compact(e, *w, req, 0, (uint32_t)req.n, now_us);
+  submit_compact(e, *w, q, 0, (uint32_t)q.n, now_us);
 }
 
 // Synchronous: chunks of max_batch (a multiple of 32 checks, so that each chunk's words start a
@@ -3731,6 +3832,19 @@ void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const Compact
                           const CavCall& cav) {
   HIP_OK(hipSetDevice(e.device));
   if (now_us == 0) now_us = wall_now_us();
+  if (req.cross()) {
+    // in place: one batch per tile; else chunks of max_batch checks of the row-major sequence,
+    // expanded to items (a chunk need not end on a word: uniform_collect places each result)
+    CompactReq q = req;
+    const bool tiled = cross_plan(e, w0, w1, cav, q);
+    std::vector<gck_item_error> errs;
+    run_chunks(
+        e, w0, w1, tiled ? cross_tiles(q) : q.n, tiled ? 1 : w0->max_batch, cav,
+        [&](Workspace& w, size_t pos, uint32_t len) { submit_compact(e, w, q, pos, len, now_us); },
+        [&](Workspace& w) { uniform_collect(w, errs); });
+    uniform_errors(errs, q.errs, q.err_cap, q.n_errs);
+    return;
+  }
   const size_t mb = w0->max_batch >= 32 ? (w0->max_batch & ~(size_t)31) : w0->max_batch;
   if (req.n > mb && mb % 32 != 0)
     throw Error(GCK_E_CAPACITY, req.shape_of ? "a shaped request above max_batch needs max_batch >= 32"

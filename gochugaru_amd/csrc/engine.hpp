@@ -277,6 +277,8 @@ struct Engine {
   gck_stats stats{};
   // gck_shaped_stats: shaped requests (chunks) whose join read them in place / expanded to items
   std::atomic<uint64_t> shaped_in_place{0}, shaped_expanded{0};
+  // gck_cross_stats: cross tiles whose join read the id lists in place / chunks expanded to items
+  std::atomic<uint64_t> cross_in_place{0}, cross_expanded{0};
   // batches to come that chain the wave bundles behind the join in stage A (engine.hip
   // bundles_launch): reset to 16 by a batch whose join left kChainLeftovers or more, counted down by
   // one that left fewer
@@ -416,8 +418,18 @@ struct CompactReq {
   gck_item_error* errs;
   size_t err_cap;
   size_t* n_errs;
+  // a cross request (gck_check_bulk_cross; null pairs and shape_of, one header): check s * R + r of
+  // the n = S * R is (shapes[0], resources[r], subjects[s]), and `packed` is the row-padded plane
+  // (S rows of ceil(R / 32) words). tile_rows x tile_cols: the tile it is cut into when it runs in
+  // place (set by the engine from gck_cross_tile; 0: expanded to items in chunks of max_batch)
+  const uint32_t* subjects = nullptr;
+  const uint32_t* resources = nullptr;
+  size_t S = 0, R = 0;
+  uint32_t tile_rows = 0, tile_cols = 0;
+  bool cross() const { return resources != nullptr; }
 };
-// Synchronous: chunks of max_batch & ~31 checks over w0 and w1 (as device_check_host).
+// Synchronous: chunks of max_batch & ~31 checks over w0 and w1 (as device_check_host); a cross
+// request in place: its tiles, one batch each.
 void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const CompactReq& req, int64_t now_us,
                           const CavCall& cav);
 void device_submit_compact(Engine& e, Workspace* w, const CompactReq& req, int64_t now_us, CavCall cav);

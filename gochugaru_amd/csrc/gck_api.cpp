@@ -1179,6 +1179,103 @@ int gck_shaped_stats(gck_engine* ge, uint64_t out[2]) {
   });
 }
 
+// ---- cross requests (include/gck.h gck_check_bulk_cross) ------------------------------------
+
+int gck_cross_tile(size_t S, size_t R, size_t max_batch, uint32_t* rows, uint32_t* cols) {
+  size_t best_rows = 0, best_cols = 0;
+  // the candidate widths: every multiple of 32 up to R, and R itself; each with the most rows it
+  // admits. More checks win; on a tie the wider tile.
+  const auto consider = [&](size_t c) {
+    if (c == 0 || c > R || c >= GCK_CROSS_IDS) return;
+    const size_t r = std::min({S, max_batch / (32 * ((c + 31) / 32)), (size_t)GCK_CROSS_IDS - c});
+    if (r == 0) return;
+    const size_t have = best_rows * best_cols;
+    if (r * c > have || (r * c == have && c > best_cols)) best_rows = r, best_cols = c;
+  };
+  for (size_t c = 32; c <= R && c < GCK_CROSS_IDS; c += 32) consider(c);
+  consider(R);
+  // the thin rule: a request of more checks than the best tile, whose best tile is small
+  // (rows <= S and cols <= R: the request has more checks iff the tile is smaller in a dimension)
+  const bool thin = best_rows && (S > best_rows || R > best_cols) && best_rows * best_cols < max_batch / 4;
+  const bool ok = best_rows != 0 && !thin;
+  if (rows) *rows = ok ? (uint32_t)best_rows : 0u;
+  if (cols) *cols = ok ? (uint32_t)best_cols : 0u;
+  return ok ? 1 : 0;
+}
+
+// A cross request's arguments against the call, in the ABI's order, before anything else (no
+// snapshot is needed to fail them). Returns the request as the engine takes it; n = S * R.
+static CompactReq cross_request(const gck_uniform* hdr, const uint32_t* subjects, size_t S, const uint32_t* resources,
+                                size_t R, size_t n_contexts, uint64_t* out_packed, gck_item_error* out_errs,
+                                size_t err_cap, size_t* out_n_errs) {
+  check_uniform(hdr, n_contexts);
+  REQUIRE(hdr->reserved == 0, GCK_E_INVALID_ARGUMENT, "cross header: reserved must be 0");
+  REQUIRE(S == 0 || R == 0 || S <= 0xFFFFFFFFull / R, GCK_E_INVALID_ARGUMENT,
+          "cross request: " + std::to_string(S) + " x " + std::to_string(R) + " checks reach 2^32");
+  const size_t n = S * R;
+  REQUIRE(n == 0 || (subjects && resources && out_packed), GCK_E_INVALID_ARGUMENT, "null buffers");
+  REQUIRE(err_cap == 0 || out_errs, GCK_E_INVALID_ARGUMENT, "null error list");
+  if (out_n_errs) *out_n_errs = 0;
+  CompactReq q{hdr, 1u, nullptr, nullptr, n, out_packed, out_errs, err_cap, out_n_errs};
+  if (n) {  // (an empty request keeps resources null: it takes the empty uniform request's path)
+    q.subjects = subjects;
+    q.resources = resources;
+    q.S = S;
+    q.R = R;
+  }
+  return q;
+}
+
+int gck_check_bulk_cross(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr, const uint32_t* subjects,
+                         size_t n_subjects, const uint32_t* resources, size_t n_resources, const char* const* contexts,
+                         const size_t* context_lens, size_t n_contexts, int64_t now_us, uint64_t* out_packed,
+                         gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs, uint64_t* out_revision) {
+  return guard([&] {
+    Engine& e = need(ge);
+    const CompactReq req = cross_request(hdr, subjects, n_subjects, resources, n_resources, n_contexts, out_packed,
+                                         out_errs, err_cap, out_n_errs);
+    // two workspaces when the request is more than one batch either way: more than one tile, or
+    // (expanded) more than max_batch checks
+    uint32_t rows = 0, cols = 0;
+    const size_t mb = max_batch_of(e);
+    const size_t one = gck_cross_tile(n_subjects, n_resources, mb, &rows, &cols) ? std::min(mb, (size_t)rows * cols) : mb;
+    check_sync(e, {cs, contexts, context_lens, n_contexts}, req.n, one, out_revision,
+               [&](Workspace* w0, Workspace* w1, const CavCall& cav) { device_check_compact(e, w0, w1, req, now_us, cav); });
+  });
+}
+
+int gck_check_submit_cross(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr, const uint32_t* subjects,
+                           size_t n_subjects, const uint32_t* resources, size_t n_resources,
+                           const char* const* contexts, const size_t* context_lens, size_t n_contexts, int64_t now_us,
+                           uint64_t* out_packed, gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs,
+                           gck_batch** out) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    const CompactReq req = cross_request(hdr, subjects, n_subjects, resources, n_resources, n_contexts, out_packed,
+                                         out_errs, err_cap, out_n_errs);
+    uint32_t rows = 0, cols = 0;
+    REQUIRE(req.n == 0 || (gck_cross_tile(n_subjects, n_resources, max_batch_of(e), &rows, &cols) && rows == n_subjects &&
+                           cols == n_resources),
+            GCK_E_INVALID_ARGUMENT,
+            "submitted cross request of " + std::to_string(n_subjects) + " x " + std::to_string(n_resources) +
+                " is not one tile (gck_cross_tile)");
+    *out = submit_with(e, {cs, contexts, context_lens, n_contexts}, req.n, [&](Workspace* w, CavCall cav) {
+      device_submit_compact(e, w, req, now_us, std::move(cav));
+    });
+  });
+}
+
+int gck_cross_stats(gck_engine* ge, uint64_t out[2]) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    out[0] = e.cross_in_place.load(std::memory_order_relaxed);
+    out[1] = e.cross_expanded.load(std::memory_order_relaxed);
+  });
+}
+
 int gck_host_alloc(gck_engine* ge, size_t bytes, void** out) {
   return guard([&] {
     Engine& e = need(ge);

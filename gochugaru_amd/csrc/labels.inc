@@ -130,6 +130,7 @@ struct LjArgs {
   union {
     struct {
       uint32_t u_rp, u_ss, u_ctx;
+      uint32_t cols;  // a cross batch (closure.inc CjArgs::cols) when n_shapes == 0; else 0 or part of `shapes`
     };
     struct {
       const uint8_t* shape_of;
@@ -723,10 +724,25 @@ __global__ void __launch_bounds__(kBlock) k_label_join(LjArgs a) {
   u32x4 item_chunk{0u, 0u, 0u, 0u};
   if (items_fast && (threadIdx.x & 63u) < CPW * 20u / 16u)
     item_chunk = *(const GCK_GLOBAL u32x4*)(ibase + (threadIdx.x & 63u) * 16u);
-  if (uni && (threadIdx.x & 63u) < CPW && w0 + (threadIdx.x & 63u) < a.n) {  // (a uniform batch: the lane's pair)
+  // (not a cross batch's lanes: `pairs` is then the id block)
+  const bool grid = uni && a.n_shapes == 0u && a.cols != 0u;
+  if (uni && (threadIdx.x & 63u) < CPW && w0 + (threadIdx.x & 63u) < a.n && !grid) {  // (a uniform batch: the lane's pair)
     const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(a.pairs + 2ull * (w0 + (threadIdx.x & 63u)));
     item_chunk.x = (uint32_t)pr;
     item_chunk.y = (uint32_t)(pr >> 32);
+  }
+  // a cross batch (closure.inc cj_block): the lane's resource id and its row's subject id from the
+  // id block instead, in the same round (in the chunk's spare registers until the table's barrier,
+  // as there); a lane whose column is padding stays idle
+  bool grid_on = true;
+  if (__builtin_expect(grid, 0)) {
+    uint32_t row, col;
+    cross_rc((uint32_t)__builtin_amdgcn_readfirstlane((int)(w0 >> 5)), (w0 + threadIdx.x) & 31u, (a.cols + 31u) >> 5, row, col);
+    grid_on = col < a.cols;
+    if ((threadIdx.x & 63u) < CPW && w0 + (threadIdx.x & 63u) < a.n && grid_on) {
+      item_chunk.z = *(const GCK_GLOBAL uint32_t*)(a.pairs + col);
+      item_chunk.w = *(const GCK_GLOBAL uint32_t*)(a.pairs + cross_sub_off(a.cols) + row);
+    }
   }
   // a shaped batch (closure.inc cj_block): the lane's index byte, and entry l of the shape table by
   // lane l < n_shapes, in the same round; the entries are staged in the wave's own stage region
@@ -758,13 +774,14 @@ __global__ void __launch_bounds__(kBlock) k_label_join(LjArgs a) {
     for (uint32_t k = threadIdx.x; k < cl_nctx; k += kBlock) s_cav.slot[k] = (uint8_t)gptr(c.cav_slot)[k];
   }
   __syncthreads();
+  if (__builtin_expect(grid, 0)) item_chunk.x = item_chunk.z, item_chunk.y = item_chunk.w;
   const unsigned long long t_tab = (GCK_BUNDLE_TIMING && a.timing) ? wall_clock64() : 0ull;
   const uint16_t* root = reinterpret_cast<const uint16_t*>(s_tab);
   const LjMeta* meta = reinterpret_cast<const LjMeta*>(s_tab + a.o_meta);
   const int wib = threadIdx.x >> 6, lane = threadIdx.x & 63;
   uint32_t* const stage = s_stage[wib];
   const uint32_t i = w0 + (uint32_t)lane;
-  const bool active = (uint32_t)lane < CPW && i < a.n;
+  const bool active = (uint32_t)lane < CPW && i < a.n && grid_on;
   // ---- the wave's items: one contiguous block of CPW x 20 B -------------------------------------
   if (uni) {
     // (the pairs are in registers)
@@ -1057,9 +1074,15 @@ __global__ void __launch_bounds__(kBlock) k_label_join(LjArgs a) {
   const uint32_t at = wave_append(a.n_deferred, active && !res);  // (one counter add per wave)
   if (active && !res) a.deferred[at] = i;
   if (active && !res && uni) {  // the check's item where the bundle stages read it (its pair read again)
-    const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(a.pairs + 2ull * i);
-    if (shaped) a.items_out[i] = shaped_item_again(a.shape_of, a.shapes, n_shapes, i, (uint32_t)pr, (uint32_t)(pr >> 32));
-    else a.items_out[i] = uniform_item(a.u_rp, a.u_ss, a.u_ctx, (uint32_t)pr, (uint32_t)(pr >> 32));
+    if (grid) {  // (a cross batch: its two ids by (row, column))
+      uint32_t res_id, sub_id;
+      cross_ids_again(a.pairs, a.cols, i, res_id, sub_id);
+      a.items_out[i] = uniform_item(a.u_rp, a.u_ss, a.u_ctx, res_id, sub_id);
+    } else {
+      const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(a.pairs + 2ull * i);
+      if (shaped) a.items_out[i] = shaped_item_again(a.shape_of, a.shapes, n_shapes, i, (uint32_t)pr, (uint32_t)(pr >> 32));
+      else a.items_out[i] = uniform_item(a.u_rp, a.u_ss, a.u_ctx, (uint32_t)pr, (uint32_t)(pr >> 32));
+    }
   }
   if (a.coherent & kPubBySignal) {  // (closure.inc block_summary)
     const uint32_t nd = (uint32_t)__popcll(__ballot(active && !res));

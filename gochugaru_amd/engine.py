@@ -156,6 +156,26 @@ def unpack_results(words: np.ndarray, n: int) -> np.ndarray:
     return four[:n].astype(np.uint8)
 
 
+CROSS_IDS = 2048  # GCK_CROSS_IDS
+
+
+def unpack_cross(words: np.ndarray, S: int, R: int) -> np.ndarray:
+    """The Permissionship of every (subject, resource) of a cross request (gck_check_bulk_cross) as
+    uint8[S, R], from its row-padded plane: S rows of ceil(R / 32) words, padding ignored."""
+    stride = (R + 31) // 32
+    b = np.ascontiguousarray(words, dtype="<u8").reshape(-1)[:S * stride].view(np.uint8).reshape(S, stride * 8)
+    four = np.stack([(b >> s) & 3 for s in (0, 2, 4, 6)], axis=2).reshape(S, stride * 32)
+    return np.ascontiguousarray(four[:, :R]).astype(np.uint8)
+
+
+def cross_tile(S: int, R: int, max_batch: int = 65536) -> Optional[Tuple[int, int]]:
+    """gck_cross_tile: the (rows, cols) tile an in-place cross request of S subjects by R resources
+    is cut into on an engine of that max_batch, or None when the request is expanded to items."""
+    rows, cols = C.c_uint32(0), C.c_uint32(0)
+    ok = load_library().gck_cross_tile(S, R, max_batch, C.byref(rows), C.byref(cols))
+    return (rows.value, cols.value) if ok else None
+
+
 MAX_SHAPES = 64  # GCK_MAX_SHAPES
 _SHAPE_FIELDS = ("resource_type", "permission", "subject_type", "subject_relation", "context_slot")
 
@@ -269,6 +289,14 @@ _SIGS = {
                                           C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int64, _P,
                                           _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_P)]),
     "gck_shaped_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "gck_check_bulk_cross": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), _P, C.c_size_t, _P,
+                                       C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int64,
+                                       _P, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    "gck_check_submit_cross": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), _P, C.c_size_t, _P,
+                                         C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t,
+                                         C.c_int64, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_P)]),
+    "gck_cross_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "gck_cross_tile": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "gck_host_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "gck_host_free": (C.c_int, [_P, _P]),
     "gck_last_stats": (C.c_int, [_P, C.POINTER(_Stats)]),
@@ -368,6 +396,10 @@ def _driver():
         d.gckd_run_shaped.argtypes = [C.c_void_p, C.c_void_p, _P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.c_void_p, C.c_uint32, C.c_int64, C.POINTER(C.c_double)]
+        d.gckd_run_cross.restype = C.c_int
+        d.gckd_run_cross.argtypes = [C.c_void_p, C.c_void_p, _P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.c_uint32, C.c_int64, C.POINTER(C.c_double)]
         d.gckd_set_trace.restype = None
         d.gckd_set_trace.argtypes = [C.c_void_p, C.c_size_t]
         _DRIVER = d
@@ -794,6 +826,66 @@ class Engine:
         _check(self._lib.gck_shaped_stats(self._h, out))
         return int(out[0]), int(out[1])
 
+    def check_cross(self, header, subjects: np.ndarray, resources: np.ndarray,
+                    requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                    contexts: Optional[Sequence] = None, out_packed: Optional[np.ndarray] = None,
+                    out_errs: Optional[np.ndarray] = None):
+        """A cross request (gck_check_bulk_cross): every subject id of `subjects` against every
+        resource id of `resources` under one `header` (as check_uniform's). Returns (words, errors,
+        evaluated revision): words = the row-padded plane, len(subjects) rows of ceil(R / 32) u64
+        (unpack_cross gives uint8[S, R]); an error's index is s * R + r."""
+        subjects = np.ascontiguousarray(subjects, dtype=np.uint32).reshape(-1)
+        resources = np.ascontiguousarray(resources, dtype=np.uint32).reshape(-1)
+        S, R = len(subjects), len(resources)
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        n_words = S * ((R + 31) // 32)
+        words = out_packed if out_packed is not None else np.zeros(n_words, dtype=np.uint64)
+        errs = out_errs if out_errs is not None else np.zeros(min(S * R, 1 << 20), dtype=ITEM_ERROR_DTYPE)
+        cs = _Consistency(requirement, 0, revision)
+        ctx_arr, ctx_lens, n_ctx = _context_arrays(contexts)
+        n_errs = C.c_size_t(0)
+        rev = C.c_uint64(0)
+        _check(self._lib.gck_check_bulk_cross(self._h, C.byref(cs), C.byref(hdr), subjects.ctypes.data if S else None, S,
+                                              resources.ctypes.data if R else None, R, ctx_arr, ctx_lens, n_ctx, now_us,
+                                              words.ctypes.data if n_words else None,
+                                              errs.ctypes.data if len(errs) else None, len(errs), C.byref(n_errs),
+                                              C.byref(rev)))
+        return words, errs[:min(n_errs.value, len(errs))].copy(), rev.value
+
+    def submit_cross(self, header, subjects: np.ndarray, resources: np.ndarray, out_packed: np.ndarray,
+                     out_errs: np.ndarray, requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0,
+                     now_us: int = 0, contexts: Optional[Sequence] = None) -> "CrossBatch":
+        """gck_check_submit_cross (one tile: cross_tile(S, R, max_batch) == (S, R)): the results land
+        in out_packed / out_errs at wait(). The id lists are copied by the call."""
+        subjects = np.ascontiguousarray(subjects, dtype=np.uint32).reshape(-1)
+        resources = np.ascontiguousarray(resources, dtype=np.uint32).reshape(-1)
+        S, R = len(subjects), len(resources)
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        b = CrossBatch(self, hdr, None, out_packed, out_errs)
+        cs = _Consistency(requirement, 0, revision)
+        ctx_arr, ctx_lens, n_ctx = _context_arrays(contexts)
+        _check(self._lib.gck_check_submit_cross(self._h, C.byref(cs), C.byref(hdr), subjects.ctypes.data if S else None,
+                                                S, resources.ctypes.data if R else None, R, ctx_arr, ctx_lens, n_ctx,
+                                                now_us, out_packed.ctypes.data if S * R else None,
+                                                out_errs.ctypes.data if len(out_errs) else None, len(out_errs),
+                                                C.byref(b._n_errs), C.byref(b._h)))
+        return b
+
+    def prepare_cross(self, headers, subjects, n_subjects, resources, n_resources, packed, errs, err_cap: int,
+                      depth: int, now_us: int = 0) -> "PreparedCross":
+        """The compiled submit/wait loop over cross requests (libgck_driver.so gckd_run_cross):
+        request k = headers[k] and host pointers subjects[k] (n_subjects[k] ids), resources[k]
+        (n_resources[k] ids), packed[k], errs[k] (err_cap records), `depth` in flight."""
+        return PreparedCross(self, headers, subjects, n_subjects, resources, n_resources, packed, errs, err_cap, depth,
+                             now_us)
+
+    def cross_stats(self) -> Tuple[int, int]:
+        """gck_cross_stats: cross tiles whose join read the id lists in place, and chunks expanded to
+        items on the host, since the engine was created."""
+        out = (C.c_uint64 * 2)()
+        _check(self._lib.gck_cross_stats(self._h, out))
+        return int(out[0]), int(out[1])
+
     def check_bulk_device(self, d_items: int, n: int, d_perm: int, d_err: int,
                           stream: Optional[int] = None, now_us: int = 0,
                           contexts: Optional[Sequence] = None):
@@ -1130,6 +1222,19 @@ class PreparedShaped(_Prepared):
                       arr(shape_of), arr(pairs), arr(ns), arr(packed), arr(errs), err_cap, self.n_errs, depth, now_us)
 
 
+class PreparedCross(_Prepared):
+    """A compiled submit/wait loop over cross requests with its argument arrays built
+    (Engine.prepare_cross)."""
+
+    def __init__(self, engine, headers, subjects, n_subjects, resources, n_resources, packed, errs, err_cap, depth,
+                 now_us):
+        super().__init__(engine, "gckd_run_cross", "gck_check_submit_cross", len(subjects), depth)
+        arr = self._arr
+        hdrs = (Uniform * max(1, len(headers)))(*[_header(h) for h in headers])
+        self._args = (hdrs, arr(subjects), arr(n_subjects), arr(resources), arr(n_resources), arr(packed), arr(errs),
+                      err_cap, self.n_errs, depth, now_us)
+
+
 class Batch:
     """A submitted batch (gck_batch): wait() completes it exactly once."""
 
@@ -1184,6 +1289,11 @@ class UniformBatch:
 class ShapedBatch(UniformBatch):
     """A submitted shaped request (gck_check_submit_shaped): as UniformBatch; it keeps the shape
     table and the index bytes alive until the wait."""
+
+
+class CrossBatch(UniformBatch):
+    """A submitted cross request (gck_check_submit_cross): as UniformBatch; `packed` is the
+    row-padded plane (unpack_cross)."""
 
 
 def _context_json(ctx) -> str:

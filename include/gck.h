@@ -473,6 +473,49 @@ int gck_check_submit_shaped(gck_engine* e, const gck_consistency* cs, const gck_
  * one-round join). */
 int gck_shaped_stats(gck_engine* e, uint64_t out[2]);
 
+/* ---- cross requests (ABI 13, additive) -----------------------------------------------
+ * Every subject of one list against every resource of another, all of one shape — "which of
+ * these documents may this user see", an access review of a team against a folder — travels as
+ * one header and the two id lists: 4 (S + R) bytes in for S * R checks. Check (s, r) is
+ * (hdr, resources[r], subjects[s]); semantics, consistency and request errors are
+ * gck_check_bulk_at's. Ids are not deduplicated; a list may repeat an id.
+ * Results: rows by subject, each row padded to whole words, stride = ceil(R / 32) words — the
+ * Permissionship of (s, r) is bits 2 (r % 32) .. +1 of out_packed[s * stride + r / 32]; padding
+ * bits are 0 and every one of the S * stride words is written. The error records are the uniform
+ * call's (index, GCK_ITEM_*) with index = s * R + r, ascending, under the same err_cap / *out_n_errs
+ * protocol. GCK_E_INVALID_ARGUMENT for null buffers with S * R > 0, a header whose `reserved` is
+ * not 0 or whose context_slot exceeds n_contexts, and S * R >= 2^32. S == 0 or R == 0 is an empty
+ * request that succeeds.
+ * Lifetimes: both lists are copied by the call and need not outlive it (the submit call
+ * included); the outputs follow the uniform rule. */
+#define GCK_CROSS_IDS 2048 /* ids (subjects + resources) a tile holds in the workspace's id block */
+int gck_check_bulk_cross(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr, const uint32_t* subjects,
+                         size_t n_subjects, const uint32_t* resources, size_t n_resources, const char* const* contexts,
+                         const size_t* context_lens, size_t n_contexts, int64_t now_us, uint64_t* out_packed,
+                         gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs, uint64_t* out_revision);
+/* The same as an asynchronous batch of one tile — gck_cross_tile(S, R, max_batch) must return the
+ * whole request, else GCK_E_INVALID_ARGUMENT: completed by gck_check_wait or gck_check_wait_at,
+ * which write out_packed, out_errs and *out_n_errs. */
+int gck_check_submit_cross(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr, const uint32_t* subjects,
+                           size_t n_subjects, const uint32_t* resources, size_t n_resources,
+                           const char* const* contexts, const size_t* context_lens, size_t n_contexts, int64_t now_us,
+                           uint64_t* out_packed, gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs,
+                           gck_batch** out);
+/* Since the engine was created: out[0] = tiles whose join read the two lists in place, out[1] =
+ * chunks of max_batch checks expanded to items on the host (check contexts, profiling, no
+ * one-round join, GCK_AQL=0, or a thin request: gck_cross_tile returned 0). */
+int gck_cross_stats(gck_engine* e, uint64_t out[2]);
+/* The tiling rule (pure: no engine, no device; the engine itself calls it). Returns 1 with the
+ * tile *rows x *cols (subjects x resources) an in-place request is cut into, left to right and
+ * top to bottom with ragged last tiles, or 0 (*rows = *cols = 0) when the request is to be
+ * expanded. A tile satisfies rows * 32 * ceil(cols / 32) <= max_batch, rows + cols <=
+ * GCK_CROSS_IDS, cols % 32 == 0 or cols == R, rows <= S, cols <= R; among such tiles the one with
+ * the most checks, the wider one on a tie. 0 when no tile exists (an empty list, max_batch < 32),
+ * or when the request has more checks than the best tile and that tile holds fewer than
+ * max_batch / 4: a thin request (one subject against 60,000 resources) would become dozens of
+ * small dispatches. */
+int gck_cross_tile(size_t n_subjects, size_t n_resources, size_t max_batch, uint32_t* rows, uint32_t* cols);
+
 /* ---- lookups (Client.LookupResources / LookupSubjects, client/client.go:508-599) -------- */
 /* Ids of the `resource_type` objects on which the subject has `permission` — HAS or CONDITIONAL,
  * out_perm[k] says which — ascending. Every object of the type is checked on the device (the
