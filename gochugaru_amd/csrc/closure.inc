@@ -103,7 +103,9 @@ struct CjArgs {
   // kPubBySignal, and what the kernel would otherwise learn from a cold pointer's null test
   // (kCjUniform ...: set by cj_seal once the pointers are final)
   uint32_t mode;
-  uint32_t hot_pad;
+  // a list batch (below): kListOn | kListSubject | kListRange, 0 otherwise. The word lies in the hot
+  // line's padding, but the kernel never reads it there: cj_seal turns it into mode bits
+  uint32_t list;
   // ---- cold, bytes 104..183 ----
   unsigned* done;
   // host items read in place (a zero-copy batch): an item whose context_slot exceeds slot_limit
@@ -128,6 +130,7 @@ struct CjArgs {
   union {
     struct {
       uint32_t u_rp, u_ss, u_ctx;
+      uint32_t u_fixed;  // a list batch (below): the fixed id
     };
     struct {
       const uint8_t* shape_of;
@@ -140,15 +143,27 @@ struct CjArgs {
   // i of the n = rows * wpr * 32 (wpr = ceil(cols / 32)) is row (i / 32) / wpr, column
   // 32 * ((i / 32) % wpr) + i % 32 (cross_rc); a column >= cols is padding: the lane is idle and its
   // result bits are 0. The header is u_rp / u_ss / u_ctx. 0: not a cross batch.
+  // A list batch (gck_check_bulk_list; kCjList, `list` != 0, never shaped nor a cross batch): check i
+  // is the header, the fixed id u_fixed on one side — the subject's, or with kListSubject the
+  // resource's — and on the other the 4-B id pairs[i], or with kListRange (null `pairs`) the id
+  // cols + i: the word is then the range's first id, not a tile width.
   uint32_t cols;
 };
+// CjArgs::list / LjArgs::list
+constexpr uint32_t kListOn = 1u;       // a list batch
+constexpr uint32_t kListSubject = 2u;  // the subject id varies (the fixed id is the resource's)
+constexpr uint32_t kListRange = 4u;    // the varying id of check i is cols + i (no id list)
 // CjArgs::mode beside kPubCoherent | kPubBySignal (engine.hip)
-constexpr uint32_t kCjUniform = 4u;   // pairs != null
+constexpr uint32_t kCjUniform = 4u;   // pairs != null, or a list batch's range
 constexpr uint32_t kCjBadSlot = 8u;   // bad_slot != null
 constexpr uint32_t kCjSelfPub = 16u;  // h_out != null
 constexpr uint32_t kCjTimed = 32u;    // timing != null
 constexpr uint32_t kCjShaped = 64u;   // n_shapes != 0 (with kCjUniform)
-constexpr uint32_t kCjGrid = 128u;    // cols != 0 (with kCjUniform, never with kCjShaped)
+constexpr uint32_t kCjGrid = 128u;    // cols != 0 (with kCjUniform, never with kCjShaped or kCjList)
+constexpr uint32_t kCjListShift = 8u;  // `list` (with kCjUniform): kListOn, kListSubject, kListRange as bits 8..10
+constexpr uint32_t kCjList = kListOn << kCjListShift;
+constexpr uint32_t kCjListSub = kListSubject << kCjListShift;
+constexpr uint32_t kCjRange = kListRange << kCjListShift;
 
 struct CjHot {  // the hot line as the kernel holds it (scalar registers)
   const gck_item* items;
@@ -177,9 +192,10 @@ static_assert((sizeof(Ctx) + kCjHotOff) % 64 == 0, "the hot line is one 64-B lin
 // The mode bits that stand for a cold pointer's null test, once the pointers are final (before
 // the launch, the dispatch or the post).
 inline void cj_seal(CjArgs& j) {
-  j.mode = (j.mode & (kPubCoherent | kPubBySignal)) | (j.pairs ? kCjUniform : 0u) | (j.bad_slot ? kCjBadSlot : 0u) |
-           (j.h_out ? kCjSelfPub : 0u) | (j.timing ? kCjTimed : 0u) | (j.pairs && j.n_shapes ? kCjShaped : 0u) |
-           (j.pairs && !j.n_shapes && j.cols ? kCjGrid : 0u);
+  const uint32_t list = j.list & kListOn ? j.list & (kListOn | kListSubject | kListRange) : 0u;
+  j.mode = (j.mode & (kPubCoherent | kPubBySignal)) | (j.pairs || list ? kCjUniform : 0u) | (j.bad_slot ? kCjBadSlot : 0u) |
+           (j.h_out ? kCjSelfPub : 0u) | (j.timing ? kCjTimed : 0u) | (j.pairs && j.n_shapes && !list ? kCjShaped : 0u) |
+           (j.pairs && !j.n_shapes && j.cols && !list ? kCjGrid : 0u) | list << kCjListShift;
 }
 // The staged bytes of a table of `bytes` bytes (its device buffer is allocated to this size).
 constexpr uint32_t cj_table_bytes(size_t bytes) { return (uint32_t)((bytes + 15) & ~(size_t)15); }
@@ -193,6 +209,7 @@ constexpr uint32_t cj_table_bytes(size_t bytes) { return (uint32_t)((bytes + 15)
 typedef uint32_t u32x16_a8 __attribute__((ext_vector_type(16), aligned(8)));
 struct CjKernargs {
   CjHot h;
+  static constexpr bool kLists = true;  // a dispatched join takes list batches (cj_block)
   __device__ __forceinline__ static const GCK_CONST unsigned char* seg() {
     const GCK_CONST unsigned char* p = (const GCK_CONST unsigned char*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(p));
@@ -219,6 +236,9 @@ struct CjKernargs {
 // A resident join's chunk (resident.inc): the request's arguments are in registers already.
 struct CjLocalArgs {
   CjHot h;
+  // (list batches are always dispatched — engine.hip closure_join_start — so the resident kernel
+  // compiles their branches out and keeps its registers)
+  static constexpr bool kLists = false;
   const CjArgs* a;
   DevCounters* c;
   uint32_t n_chunks;
@@ -261,6 +281,16 @@ __device__ __forceinline__ void cross_ids_again(const uint32_t* ids, uint32_t co
   cross_rc(i >> 5, i & 31u, (cols + 31u) >> 5, row, col);
   res = *(const GCK_GLOBAL uint32_t*)(ids + col);
   sub = *(const GCK_GLOBAL uint32_t*)(ids + cross_sub_off(cols) + row);
+}
+
+// A list batch's check i (CjArgs::list), built again by the rare check the join leaves to the
+// bundle stages: its varying id read again — or, in range form, computed again — and the fixed id
+// on the other side.
+__device__ __forceinline__ void list_ids_again(const uint32_t* ids, uint32_t list, uint32_t first, uint32_t fixed, uint32_t i,
+                                               uint32_t& res, uint32_t& sub) {
+  const uint32_t v = (list & kListRange) ? first + i : *(const GCK_GLOBAL uint32_t*)(ids + i);
+  res = (list & kListSubject) ? fixed : v;
+  sub = (list & kListSubject) ? v : fixed;
 }
 
 // The packed results of a uniform batch: lane l of a wave whose first check is w0 (a multiple of
@@ -719,11 +749,13 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
   if (items_early && lane < 40)
     item_chunk = *(const GCK_GLOBAL u32x4*)(reinterpret_cast<const unsigned char*>(a.items) + (size_t)w0 * 20u + lane * 16u);
   // a uniform batch: each lane its own check's 8-B pair, requested before the table as the items
-  // are (into the same registers; not a cross batch's lanes: `pairs` is then the id block)
+  // are (into the same registers; not a cross batch's lanes: `pairs` is then the id block; nor a
+  // list batch's: the id list, or null)
   const bool grid = (a.mode & kCjGrid) != 0u;
+  const bool list = A::kLists && (a.mode & kCjList) != 0u;
   if (uni) {
     const uint32_t* pairs = ax.cold()->pairs;
-    if ((uint32_t)lane < CPW && w0 + (uint32_t)lane < a.n && !grid) {
+    if ((uint32_t)lane < CPW && w0 + (uint32_t)lane < a.n && !(grid || list)) {
       const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(pairs + 2ull * (w0 + (uint32_t)lane));
       item_chunk.x = (uint32_t)pr;
       item_chunk.y = (uint32_t)(pr >> 32);
@@ -751,6 +783,20 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
     if ((uint32_t)lane < CPW && w0 + (uint32_t)lane < a.n && grid_on) {
       item_chunk.z = *(const GCK_GLOBAL uint32_t*)(ids + col);
       item_chunk.w = *(const GCK_GLOBAL uint32_t*)(ids + cross_sub_off(cols) + row);
+    }
+  }
+  // a list batch: in the same round the lane's one 4-B id (32 consecutive words per result word:
+  // one request) — in range form computed, nothing loaded — into the chunk's spare register .z, the
+  // fixed id into .w, until the table's barrier. A branch of its own for the cross batch's reason;
+  // its arguments are read through cold() here, not with the hot line
+  if (__builtin_expect(list, 0)) {
+    const auto cold = ax.cold();
+    const uint32_t* ids = cold->pairs;
+    const uint32_t fixed = cold->u_fixed, first = cold->cols;
+    if ((uint32_t)lane < CPW && w0 + (uint32_t)lane < a.n) {
+      item_chunk.w = fixed;
+      if (a.mode & kCjRange) item_chunk.z = first + w0 + (uint32_t)lane;
+      else item_chunk.z = *(const GCK_GLOBAL uint32_t*)(ids + w0 + (uint32_t)lane);
     }
   }
   // a shaped batch: in the same round each check lane its index byte (32 consecutive bytes per
@@ -790,6 +836,11 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
   if (__builtin_expect(shaped, 0) && (uint32_t)lane < n_shapes) *reinterpret_cast<u32x4*>(&s_item_w[lane * 4u]) = shape_ent;
   __syncthreads();
   if (__builtin_expect(grid, 0)) item_chunk.x = item_chunk.z, item_chunk.y = item_chunk.w;
+  if (__builtin_expect(list, 0)) {  // (resource id, subject id): the varying id and the fixed one
+    const bool sub = (a.mode & kCjListSub) != 0u;
+    item_chunk.x = sub ? item_chunk.w : item_chunk.z;
+    item_chunk.y = sub ? item_chunk.z : item_chunk.w;
+  }
   const uint16_t* root = reinterpret_cast<const uint16_t*>(s_tab);
   const CjMeta* meta = reinterpret_cast<const CjMeta*>(s_tab + a.o_meta);
   const CjEntry* ent = reinterpret_cast<const CjEntry*>(s_tab + a.o_entries);
@@ -1223,6 +1274,10 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
         if (a.mode & kCjGrid) {  // (a cross batch: its two ids by (row, column))
           uint32_t res, sub;
           cross_ids_again(cold->pairs, cold->cols, i, res, sub);
+          cold->items_out[i] = uniform_item(cold->u_rp, cold->u_ss, cold->u_ctx, res, sub);
+        } else if (list) {  // (a list batch: its varying id again, the fixed one beside it)
+          uint32_t res, sub;
+          list_ids_again(cold->pairs, a.mode >> kCjListShift, cold->cols, cold->u_fixed, i, res, sub);
           cold->items_out[i] = uniform_item(cold->u_rp, cold->u_ss, cold->u_ctx, res, sub);
         } else {
           const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(cold->pairs + 2ull * i);

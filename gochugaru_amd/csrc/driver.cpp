@@ -23,6 +23,9 @@ using submit_shaped_fn = int (*)(gck_engine*, const gck_consistency*, const gck_
 using submit_cross_fn = int (*)(gck_engine*, const gck_consistency*, const gck_uniform*, const uint32_t*, size_t,
                                 const uint32_t*, size_t, const char* const*, const size_t*, size_t, int64_t, uint64_t*,
                                 gck_item_error*, size_t, size_t*, gck_batch**);
+using submit_list_fn = int (*)(gck_engine*, const gck_consistency*, const gck_uniform*, uint32_t, uint32_t,
+                               const uint32_t*, uint32_t, size_t, const char* const*, const size_t*, size_t, int64_t,
+                               uint64_t*, gck_item_error*, size_t, size_t*, gck_batch**);
 
 // Optional per-batch timeline of the next loops (gckd_set_trace): for batch k, the seconds after
 // the loop's start at which its submit and its wait returned (stamps[2k], stamps[2k + 1]).
@@ -143,6 +146,21 @@ int gckd_run_cross(submit_cross_fn submit, wait_fn wait, gck_engine* e, const gc
                   reinterpret_cast<const uint32_t*>(resources[k]), (size_t)n_resources[k], nullptr, nullptr, 0, now_us,
                   reinterpret_cast<uint64_t*>(packed[k]), reinterpret_cast<gck_item_error*>(errs[k]), err_cap,
                   n_errs ? n_errs + k : nullptr, b);
+  });
+}
+
+// The same loop over list requests (gck_check_submit_list): request k = header hdrs[k], the fixed
+// id fixed[k] on the side `vary` leaves, and ns[k] varying ids — the host list ids[k], or with
+// ids[k] == 0 the range from first[k] — in; packed[k] (ceil(ns[k] / 32) words) and errs[k] out: 4 or
+// 0 B per check instead of 8.
+int gckd_run_list(submit_list_fn submit, wait_fn wait, gck_engine* e, const gck_consistency* cs, size_t n_batches,
+                  const gck_uniform* hdrs, const uint32_t* fixed, uint32_t vary, const uint64_t* ids,
+                  const uint32_t* first, const uint64_t* ns, const uint64_t* packed, const uint64_t* errs,
+                  size_t err_cap, size_t* n_errs, uint32_t depth, int64_t now_us, double* seconds) {
+  return run_loop(n_batches, depth, wait, e, seconds, [&](size_t k, gck_batch** b) {
+    return submit(e, cs, hdrs + k, fixed[k], vary, reinterpret_cast<const uint32_t*>(ids[k]), first[k], (size_t)ns[k],
+                  nullptr, nullptr, 0, now_us, reinterpret_cast<uint64_t*>(packed[k]),
+                  reinterpret_cast<gck_item_error*>(errs[k]), err_cap, n_errs ? n_errs + k : nullptr, b);
   });
 }
 

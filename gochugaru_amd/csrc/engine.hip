@@ -223,6 +223,9 @@ struct CompactRun {
   uint32_t rows = 0, cols = 0, row0 = 0, col0 = 0, pad = 0;
   size_t R = 0;
   bool grid() const { return mode == kInPlace && cross; }  // the join reads the id block
+  // a list request's chunk (CompactReq::list) in place: the join's list word (closure.inc kListOn ...;
+  // 0: not a list batch), the fixed id, and — `pairs` is the chunk's id list, or null — its first id
+  uint32_t list = 0, fixed_id = 0, first_id = 0;
   bool in_place() const { return mode == kInPlace; }
   bool table_join() const { return mode == kInPlace && indexed; }  // the join reads index bytes and a shape table
 };
@@ -2624,6 +2627,10 @@ static void uniform_args(const Workspace& w, Args& j) {
     j.n_shapes = c.n_shapes;
   } else if (c.grid()) {  // (a cross batch: `pairs` is the workspace's id block; the word is 0 otherwise)
     j.cols = c.cols;
+  } else if (c.list) {  // (a list batch: `pairs` is the id list — null for a range, whose first id is `cols`)
+    j.list = c.list;
+    j.u_fixed = c.fixed_id;
+    j.cols = c.first_id;
   }
   j.items = nullptr;
 }
@@ -2845,9 +2852,9 @@ static void closure_join_start(Engine& e, Workspace& w, const Route& r, const Ct
   // the resident join (resident.inc) takes the request without a dispatch of its own
   // (a shaped batch is dispatched: the running launch would read the workspace's shape table, which
   // the host rewrites between requests, without a dispatch's acquire in between; a cross batch
-  // likewise: its id block)
+  // likewise: its id block; a list batch is dispatched too — the resident join takes pair requests)
   const bool res_ok = ak && e.res && !r.timed && w.b_sum_blocks == grid.x && (cj_args.j.mode & kPubBySignal) &&
-                      !w.cb.table_join() && !w.cb.grid();
+                      !w.cb.table_join() && !w.cb.grid() && !w.cb.list;
   if (res_ok) {
     aql_after_build(e);
     res_post(e, w, cj_args.j, grid.x);
@@ -3623,25 +3630,30 @@ static void compact_expand(const CompactReq& q, size_t pos, std::vector<gck_item
     it.resource_type = h.resource_type;
     it.permission = h.permission;
     // (a cross request: check pos + k is subject (pos + k) / R against resource (pos + k) % R)
-    it.resource_id = q.cross() ? q.resources[(pos + k) % q.R] : q.pairs[2 * (pos + k)];
+    it.resource_id = q.cross() ? q.resources[(pos + k) % q.R] : q.list() ? q.fixed_id : q.pairs[2 * (pos + k)];
     it.subject_type = h.subject_type;
     it.subject_relation = h.subject_relation;
-    it.subject_id = q.cross() ? q.subjects[(pos + k) / q.R] : q.pairs[2 * (pos + k) + 1];
+    it.subject_id = q.cross() ? q.subjects[(pos + k) / q.R] : q.list() ? q.fixed_id : q.pairs[2 * (pos + k) + 1];
     it.context_slot = h.context_slot;
+    if (q.list()) {  // (a list request: the varying id on its side, the fixed one on the other)
+      const uint32_t v = q.ids ? q.ids[pos + k] : q.first_id + (uint32_t)(pos + k);
+      (q.vary == GCK_VARY_SUBJECT ? it.subject_id : it.resource_id) = v;
+    }
   }
 }
 
 // Where the join of an in-place chunk reads and writes: the caller's buffers when they are pinned
 // (gck_host_alloc), else the workspace's pinned staging after one host copy — its item region
 // holds 20 B per check (the pairs first, then the index bytes if there are any), its result
-// region 4 B per check (room for the words).
-static void compact_stage(Engine& e, Workspace& w, const uint32_t* pairs, const uint8_t* shape_of, uint32_t n,
-                          CompactRun& c) {
+// region 4 B per check (room for the words). id_bytes: what a check has at `pairs` — 8, its pair; 4,
+// a list chunk's one id; null `pairs`: a range's chunk, which has nothing to read.
+static void compact_stage(Engine& e, Workspace& w, const uint32_t* pairs, size_t id_bytes, const uint8_t* shape_of,
+                          uint32_t n, CompactRun& c) {
   unsigned char* stage = reinterpret_cast<unsigned char*>(w.h_items);
   const size_t words = ((size_t)n + 31u) / 32u;
   c.pairs = pairs;
-  if (!host_pinned(e, pairs, (size_t)n * 8u)) {
-    std::memcpy(stage, pairs, (size_t)n * 8u);
+  if (pairs && !host_pinned(e, pairs, (size_t)n * id_bytes)) {
+    std::memcpy(stage, pairs, (size_t)n * id_bytes);
     c.pairs = reinterpret_cast<const uint32_t*>(stage);
   }
   c.shape_of = shape_of;
@@ -3713,7 +3725,15 @@ static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t 
   // shaped chunk also needs the workspace's table block (a cross request's: cross_plan, above)
   if (!c.cross && zero_copy_ok(e, w) && (!c.indexed || w.aql_shapes)) {
     c.mode = CompactRun::kInPlace;
-    compact_stage(e, w, q.pairs + 2 * pos, c.indexed ? q.shape_of + pos : nullptr, len, c);
+    if (q.list()) {
+      // a list chunk: its ids, 4 B per check; a range's chunk has none, only its own first id
+      compact_stage(e, w, q.ids ? q.ids + pos : nullptr, 4u, nullptr, len, c);
+      c.list = kListOn | (q.vary == GCK_VARY_SUBJECT ? kListSubject : 0u) | (q.ids ? 0u : kListRange);
+      c.fixed_id = q.fixed_id;
+      c.first_id = q.ids ? 0u : q.first_id + (uint32_t)pos;
+    } else {
+      compact_stage(e, w, q.pairs + 2 * pos, 8u, c.indexed ? q.shape_of + pos : nullptr, len, c);
+    }
     if (c.indexed) aql_put_shapes(*e.aql, w, q.shapes, q.n_shapes);
     else header();
     submit_batch(e, w, w.d_items, len, now_us, w.d_perm, w.d_err, w.stream, BatchMem::kEngineStream, c);
@@ -3728,6 +3748,7 @@ static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t 
   // (gck_shaped_stats counts shaped chunks only, one count per chunk)
   if (c.indexed) (c.in_place() ? e.shaped_in_place : e.shaped_expanded).fetch_add(1, std::memory_order_relaxed);
   if (c.cross) e.cross_expanded.fetch_add(1, std::memory_order_relaxed);  // (gck_cross_stats: its chunks, likewise)
+  if (q.list()) (c.in_place() ? e.list_in_place : e.list_expanded).fetch_add(1, std::memory_order_relaxed);  // (gck_list_stats)
 }
 
 // The place of a cross batch's check i in its request: in place, i counts the tile's padded checks
@@ -3826,8 +3847,23 @@ void device_submit_compact(Engine& e, Workspace* w, const CompactReq& req, int64
   submit_compact(e, *w, q, 0, (uint32_t)q.n, now_us);
 }
 
-// Synchronous: chunks of max_batch (a multiple of 32 checks, so that each chunk's words start a
-// word) on two workspaces in turn, as device_check_host.
+// The chunks of a request that is no cross request: max_batch checks each, rounded down to a multiple
+// of 32 so that each chunk's words start a word, on two workspaces in turn; every chunk's errors,
+// request-indexed and in no order, into `errs`. Returns the chunk size.
+static size_t compact_chunks(Engine& e, Workspace* w0, Workspace* w1, const CompactReq& req, int64_t now_us,
+                             const CavCall& cav, std::vector<gck_item_error>& errs) {
+  const size_t mb = w0->max_batch >= 32 ? (w0->max_batch & ~(size_t)31) : w0->max_batch;
+  if (req.n > mb && mb % 32 != 0)
+    throw Error(GCK_E_CAPACITY, req.shape_of ? "a shaped request above max_batch needs max_batch >= 32"
+                                             : "a uniform request above max_batch needs max_batch >= 32");
+  run_chunks(
+      e, w0, w1, req.n, mb, cav,
+      [&](Workspace& w, size_t pos, uint32_t len) { submit_compact(e, w, req, pos, len, now_us); },
+      [&](Workspace& w) { uniform_collect(w, errs); });
+  return mb;
+}
+
+// Synchronous: chunks on two workspaces in turn, as device_check_host.
 void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const CompactReq& req, int64_t now_us,
                           const CavCall& cav) {
   HIP_OK(hipSetDevice(e.device));
@@ -3845,15 +3881,8 @@ void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const Compact
     uniform_errors(errs, q.errs, q.err_cap, q.n_errs);
     return;
   }
-  const size_t mb = w0->max_batch >= 32 ? (w0->max_batch & ~(size_t)31) : w0->max_batch;
-  if (req.n > mb && mb % 32 != 0)
-    throw Error(GCK_E_CAPACITY, req.shape_of ? "a shaped request above max_batch needs max_batch >= 32"
-                                             : "a uniform request above max_batch needs max_batch >= 32");
   std::vector<gck_item_error> errs;
-  run_chunks(
-      e, w0, w1, req.n, mb, cav,
-      [&](Workspace& w, size_t pos, uint32_t len) { submit_compact(e, w, req, pos, len, now_us); },
-      [&](Workspace& w) { uniform_collect(w, errs); });
+  compact_chunks(e, w0, w1, req, now_us, cav, errs);
   uniform_errors(errs, req.errs, req.err_cap, req.n_errs);
 }
 

@@ -279,6 +279,8 @@ struct Engine {
   std::atomic<uint64_t> shaped_in_place{0}, shaped_expanded{0};
   // gck_cross_stats: cross tiles whose join read the id lists in place / chunks expanded to items
   std::atomic<uint64_t> cross_in_place{0}, cross_expanded{0};
+  // gck_list_stats: list chunks whose join read the ids in place / chunks expanded to items
+  std::atomic<uint64_t> list_in_place{0}, list_expanded{0};
   // batches to come that chain the wave bundles behind the join in stage A (engine.hip
   // bundles_launch): reset to 16 by a batch whose join left kChainLeftovers or more, counted down by
   // one that left fewer
@@ -427,6 +429,14 @@ struct CompactReq {
   size_t S = 0, R = 0;
   uint32_t tile_rows = 0, tile_cols = 0;
   bool cross() const { return resources != nullptr; }
+  // a list request (gck_check_bulk_list; null pairs and shape_of, one header): `vary` is
+  // GCK_VARY_RESOURCE or GCK_VARY_SUBJECT (0: not a list request), check i is shapes[0] with
+  // fixed_id on the other side and the varying id ids[i] — or, with null ids, first_id + i.
+  // `packed` is the uniform request's dense plane
+  uint32_t vary = 0;
+  uint32_t fixed_id = 0, first_id = 0;
+  const uint32_t* ids = nullptr;
+  bool list() const { return vary != 0; }
 };
 // Synchronous: chunks of max_batch & ~31 checks over w0 and w1 (as device_check_host); a cross
 // request in place: its tiles, one batch each.
@@ -449,6 +459,13 @@ void device_lookup(Engine& e, Workspace& w, const gck_item& proto, bool vary_res
                    int64_t now_us, std::vector<uint32_t>& ids, std::vector<uint8_t>& perms);
 void device_lookup_subjects(Engine& e, Workspace& w, const gck_item& proto, int64_t now_us, std::vector<uint32_t>& ids,
                             std::vector<uint8_t>& perms);
+// lookups among candidates (gck_lookup_resources_among / _subjects_among): the list request `req`
+// (without outputs; null ids: the range) run over w0 and w1 into a host vector — the joins write
+// each chunk's words into the workspace's pinned result staging, the wait copies them out — and
+// the plane scanned on the host: the candidates that are HAS or CONDITIONAL in request order,
+// repeats included. A per-item error fails the call as device_lookup does.
+void device_lookup_among(Engine& e, Workspace* w0, Workspace* w1, const CompactReq& req, int64_t now_us,
+                         std::vector<uint32_t>& ids, std::vector<uint8_t>& perms);
 // partitioned checks (partition.inc): one batch over every rank, the exchange over RCCL inside
 // libgck (part_check, after part_init) or the caller's transport (part_check_with)
 void part_unique_id(uint8_t* out);

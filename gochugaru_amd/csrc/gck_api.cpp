@@ -1276,6 +1276,71 @@ int gck_cross_stats(gck_engine* ge, uint64_t out[2]) {
   });
 }
 
+// ---- list requests (include/gck.h gck_check_bulk_list) ---------------------------------------
+
+// A list request's arguments against the call, in the ABI's order, before anything else (no snapshot
+// is needed to fail them). Returns the request as the engine takes it.
+static CompactReq list_request(const gck_uniform* hdr, uint32_t fixed_id, uint32_t vary, const uint32_t* ids,
+                               uint32_t first_id, size_t n, size_t n_contexts, uint64_t* out_packed,
+                               gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs) {
+  check_uniform(hdr, n_contexts);
+  REQUIRE(hdr->reserved == 0, GCK_E_INVALID_ARGUMENT, "list header: reserved must be 0");
+  REQUIRE(vary == GCK_VARY_RESOURCE || vary == GCK_VARY_SUBJECT, GCK_E_INVALID_ARGUMENT,
+          "list request: vary must be GCK_VARY_RESOURCE or GCK_VARY_SUBJECT");
+  if (!ids && n) {
+    REQUIRE(vary == GCK_VARY_RESOURCE, GCK_E_INVALID_ARGUMENT,
+            "list request: a range varies the resource id (the fixed id is the subject's)");
+    REQUIRE((uint64_t)first_id + n <= 0x100000000ull, GCK_E_INVALID_ARGUMENT,
+            "list request: the range " + std::to_string(first_id) + " + " + std::to_string(n) + " passes 2^32");
+  }
+  REQUIRE(n == 0 || out_packed, GCK_E_INVALID_ARGUMENT, "null buffers");
+  REQUIRE(err_cap == 0 || out_errs, GCK_E_INVALID_ARGUMENT, "null error list");
+  if (out_n_errs) *out_n_errs = 0;
+  CompactReq q{hdr, 1u, nullptr, nullptr, n, out_packed, out_errs, err_cap, out_n_errs};
+  q.vary = vary;
+  q.fixed_id = fixed_id;
+  q.first_id = ids ? 0u : first_id;
+  q.ids = ids;
+  return q;
+}
+
+int gck_check_bulk_list(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                        uint32_t vary, const uint32_t* ids, uint32_t first_id, size_t n, const char* const* contexts,
+                        const size_t* context_lens, size_t n_contexts, int64_t now_us, uint64_t* out_packed,
+                        gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs, uint64_t* out_revision) {
+  return guard([&] {
+    Engine& e = need(ge);
+    const CompactReq req =
+        list_request(hdr, fixed_id, vary, ids, first_id, n, n_contexts, out_packed, out_errs, err_cap, out_n_errs);
+    check_compact_sync(e, {cs, contexts, context_lens, n_contexts}, req, now_us, out_revision);
+  });
+}
+
+int gck_check_submit_list(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                          uint32_t vary, const uint32_t* ids, uint32_t first_id, size_t n, const char* const* contexts,
+                          const size_t* context_lens, size_t n_contexts, int64_t now_us, uint64_t* out_packed,
+                          gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs, gck_batch** out) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    const CompactReq req =
+        list_request(hdr, fixed_id, vary, ids, first_id, n, n_contexts, out_packed, out_errs, err_cap, out_n_errs);
+    *out = submit_with(e, {cs, contexts, context_lens, n_contexts}, n, [&](Workspace* w, CavCall cav) {
+      device_submit_compact(e, w, req, now_us, std::move(cav));
+    });
+  });
+}
+
+int gck_list_stats(gck_engine* ge, uint64_t out[2]) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    out[0] = e.list_in_place.load(std::memory_order_relaxed);
+    out[1] = e.list_expanded.load(std::memory_order_relaxed);
+  });
+}
+
 int gck_host_alloc(gck_engine* ge, size_t bytes, void** out) {
   return guard([&] {
     Engine& e = need(ge);
@@ -1423,8 +1488,59 @@ struct LookupCache {
   int64_t now_us = 0;
   std::vector<uint32_t> ids;
   std::vector<uint8_t> perms;
+  // a lookup among candidates (lookup_among): 1 with the caller's list `cand`, 2 over the whole type
+  int among = 0;
+  std::vector<uint32_t> cand;
 };
 thread_local LookupCache g_lookup;
+
+// What every lookup checks under the shared engine lock: the engine's state, the consistency asked
+// for, and the request's types and relations against the schema.
+static void lookup_checks(Engine& e, const gck_consistency* cs, const gck_item& proto) {
+  REQUIRE(e.committed, GCK_E_STATE, "no snapshot committed");
+  REQUIRE(e.part_world <= 1, GCK_E_STATE, "lookups are not available on a partitioned engine");
+  check_consistency(e, cs);
+  const Schema& sc = *e.schema;
+  REQUIRE(proto.resource_type < sc.types.size() && proto.subject_type < sc.types.size(), GCK_E_NOT_FOUND,
+          "object definition not found");
+  REQUIRE(proto.permission < sc.rels.size() && sc.rels[proto.permission].type == proto.resource_type,
+          GCK_E_NOT_FOUND, "relation/permission not found");
+  REQUIRE(proto.subject_relation == GCK_ELLIPSIS ||
+              (proto.subject_relation < sc.rels.size() && sc.rels[proto.subject_relation].type == proto.subject_type),
+          GCK_E_NOT_FOUND, "subject relation not found");
+}
+
+// The end of every lookup: the count, then the kept result (g_lookup) copied out and dropped — or,
+// when it exceeds `cap`, kept for the retry and GCK_E_CAPACITY.
+static void lookup_copy_out(uint32_t* out_ids, uint8_t* out_perm, size_t cap, size_t* out_n) {
+  *out_n = g_lookup.ids.size();
+  REQUIRE(cap >= g_lookup.ids.size(), GCK_E_CAPACITY,
+          "lookup result has " + std::to_string(g_lookup.ids.size()) + " ids: retry with that capacity");
+  if (!g_lookup.ids.empty()) {
+    std::memcpy(out_ids, g_lookup.ids.data(), g_lookup.ids.size() * 4);
+    std::memcpy(out_perm, g_lookup.perms.data(), g_lookup.perms.size());
+  }
+  g_lookup.generation = 0;
+  g_lookup.ids.clear();
+  g_lookup.perms.clear();
+  g_lookup.cand.clear();
+}
+
+// Whether the kept result answers this request (the candidates apart: lookup_among), and the request
+// remembered beside a result just computed.
+static bool lookup_kept(const Engine& e, const gck_item& proto, bool vary_res, int64_t now_us, int among) {
+  return now_us != 0 && g_lookup.generation != 0 && g_lookup.generation == e.generation && g_lookup.among == among &&
+         g_lookup.vary_res == vary_res && g_lookup.now_us == now_us &&
+         std::memcmp(&g_lookup.proto, &proto, sizeof(gck_item)) == 0;
+}
+static void lookup_keep(const Engine& e, const gck_item& proto, bool vary_res, int64_t now_us, int among) {
+  g_lookup.generation = e.generation;
+  g_lookup.proto = proto;
+  g_lookup.vary_res = vary_res;
+  g_lookup.now_us = now_us;
+  g_lookup.among = among;
+  g_lookup.cand.clear();
+}
 
 static void lookup(gck_engine* ge, const gck_consistency* cs, const gck_item& proto, bool vary_res, int64_t now_us,
                    uint32_t* out_ids, uint8_t* out_perm, size_t cap, size_t* out_n) {
@@ -1437,21 +1553,8 @@ static void lookup(gck_engine* ge, const gck_consistency* cs, const gck_item& pr
   }
   WsLease lease(e);  // before the engine lock (engine.hpp WsLease)
   std::shared_lock<std::shared_mutex> lk(e.mu);
-  REQUIRE(e.committed, GCK_E_STATE, "no snapshot committed");
-  REQUIRE(e.part_world <= 1, GCK_E_STATE, "lookups are not available on a partitioned engine");
-  check_consistency(e, cs);
-  const Schema& sc = *e.schema;
-  REQUIRE(proto.resource_type < sc.types.size() && proto.subject_type < sc.types.size(), GCK_E_NOT_FOUND,
-          "object definition not found");
-  REQUIRE(proto.permission < sc.rels.size() && sc.rels[proto.permission].type == proto.resource_type,
-          GCK_E_NOT_FOUND, "relation/permission not found");
-  REQUIRE(proto.subject_relation == GCK_ELLIPSIS ||
-              (proto.subject_relation < sc.rels.size() && sc.rels[proto.subject_relation].type == proto.subject_type),
-          GCK_E_NOT_FOUND, "subject relation not found");
-  const bool hit = now_us != 0 && g_lookup.generation != 0 && g_lookup.generation == e.generation &&
-                   g_lookup.vary_res == vary_res && g_lookup.now_us == now_us &&
-                   std::memcmp(&g_lookup.proto, &proto, sizeof(gck_item)) == 0;
-  if (!hit) {
+  lookup_checks(e, cs, proto);
+  if (!lookup_kept(e, proto, vary_res, now_us, 0)) {
     g_lookup.generation = 0;
     if (vary_res) {
       device_lookup(e, *lease.w, proto, true, e.interner[proto.resource_type].count, now_us, g_lookup.ids,
@@ -1459,21 +1562,9 @@ static void lookup(gck_engine* ge, const gck_consistency* cs, const gck_item& pr
     } else {
       device_lookup_subjects(e, *lease.w, proto, now_us, g_lookup.ids, g_lookup.perms);
     }
-    g_lookup.generation = e.generation;
-    g_lookup.proto = proto;
-    g_lookup.vary_res = vary_res;
-    g_lookup.now_us = now_us;
+    lookup_keep(e, proto, vary_res, now_us, 0);
   }
-  *out_n = g_lookup.ids.size();
-  REQUIRE(cap >= g_lookup.ids.size(), GCK_E_CAPACITY,
-          "lookup result has " + std::to_string(g_lookup.ids.size()) + " ids: retry with that capacity");
-  if (!g_lookup.ids.empty()) {
-    std::memcpy(out_ids, g_lookup.ids.data(), g_lookup.ids.size() * 4);
-    std::memcpy(out_perm, g_lookup.perms.data(), g_lookup.perms.size());
-  }
-  g_lookup.generation = 0;
-  g_lookup.ids.clear();
-  g_lookup.perms.clear();
+  lookup_copy_out(out_ids, out_perm, cap, out_n);
 }
 
 int gck_lookup_resources(gck_engine* ge, const gck_consistency* cs, uint16_t resource_type, uint16_t permission,
@@ -1492,6 +1583,61 @@ int gck_lookup_subjects(gck_engine* ge, const gck_consistency* cs, uint16_t reso
   return guard([&] {
     gck_item proto{resource_type, permission, resource_id, subject_type, subject_relation, 0, 0};
     lookup(ge, cs, proto, false, now_us, out_ids, out_perm, cap, out_n);
+  });
+}
+
+// gck_lookup_resources_among / gck_lookup_subjects_among: the candidates (null: every object of the
+// resource type, one range) as one list request (engine.hpp device_lookup_among), under `lookup`'s
+// argument checks and its capacity protocol — the kept result also remembers the candidates.
+static void lookup_among(gck_engine* ge, const gck_consistency* cs, const gck_item& proto, bool vary_res,
+                         const uint32_t* candidates, size_t n_candidates, int64_t now_us, uint32_t* out_ids,
+                         uint8_t* out_perm, size_t cap, size_t* out_n) {
+  Engine& e = need(ge);
+  REQUIRE(out_n && (cap == 0 || (out_ids && out_perm)), GCK_E_INVALID_ARGUMENT, "null buffers");
+  REQUIRE(vary_res || candidates || n_candidates == 0, GCK_E_INVALID_ARGUMENT,
+          "lookup among subjects needs a candidate list");
+  REQUIRE(n_candidates <= 0xFFFFFFFFull, GCK_E_INVALID_ARGUMENT, "too many candidates");
+  precheck(e);
+  WsPair p(e, 2);  // before the engine lock (engine.hpp WsLease)
+  std::shared_lock<std::shared_mutex> lk(e.mu);
+  lookup_checks(e, cs, proto);
+  const int among = candidates ? 1 : 2;
+  const size_t n = candidates ? n_candidates : (vary_res ? (size_t)e.interner[proto.resource_type].count : 0);
+  const bool hit = lookup_kept(e, proto, vary_res, now_us, among) && g_lookup.cand.size() == (candidates ? n : 0) &&
+                   (!candidates || n == 0 || std::memcmp(g_lookup.cand.data(), candidates, n * 4) == 0);
+  if (!hit) {
+    g_lookup.generation = 0;
+    const gck_uniform hdr{proto.resource_type, proto.permission, proto.subject_type, proto.subject_relation, 0, 0};
+    CompactReq q{&hdr, 1u, nullptr, nullptr, n, nullptr, nullptr, 0, nullptr};
+    q.vary = vary_res ? GCK_VARY_RESOURCE : GCK_VARY_SUBJECT;
+    q.fixed_id = vary_res ? proto.subject_id : proto.resource_id;
+    q.ids = candidates;
+    device_lookup_among(e, p.ws[0], p.ws[1], q, now_us, g_lookup.ids, g_lookup.perms);
+    lookup_keep(e, proto, vary_res, now_us, among);
+    // (the candidates are remembered only with a result that has to be kept for the retry)
+    if (candidates && g_lookup.ids.size() > cap) g_lookup.cand.assign(candidates, candidates + n);
+  }
+  lookup_copy_out(out_ids, out_perm, cap, out_n);
+}
+
+int gck_lookup_resources_among(gck_engine* ge, const gck_consistency* cs, uint16_t resource_type, uint16_t permission,
+                               uint16_t subject_type, uint16_t subject_relation, uint32_t subject_id,
+                               const uint32_t* candidates, size_t n_candidates, int64_t now_us, uint32_t* out_ids,
+                               uint8_t* out_perm, size_t cap, size_t* out_n) {
+  return guard([&] {
+    REQUIRE(subject_id != GCK_ID_WILDCARD, GCK_E_INVALID_ARGUMENT, "cannot perform lookup on wildcard subject");
+    gck_item proto{resource_type, permission, 0, subject_type, subject_relation, subject_id, 0};
+    lookup_among(ge, cs, proto, true, candidates, n_candidates, now_us, out_ids, out_perm, cap, out_n);
+  });
+}
+
+int gck_lookup_subjects_among(gck_engine* ge, const gck_consistency* cs, uint16_t resource_type, uint32_t resource_id,
+                              uint16_t permission, uint16_t subject_type, uint16_t subject_relation,
+                              const uint32_t* candidates, size_t n_candidates, int64_t now_us, uint32_t* out_ids,
+                              uint8_t* out_perm, size_t cap, size_t* out_n) {
+  return guard([&] {
+    gck_item proto{resource_type, permission, resource_id, subject_type, subject_relation, 0, 0};
+    lookup_among(ge, cs, proto, false, candidates, n_candidates, now_us, out_ids, out_perm, cap, out_n);
   });
 }
 

@@ -94,6 +94,7 @@ static_assert(sizeof(LjMeta) == 64, "LjMeta layout");
 struct LjArgs {
   const gck_item* items;
   uint32_t n;
+  uint32_t list;  // a list batch (closure.inc CjArgs::list: kListOn | kListSubject | kListRange); 0 otherwise
   uint8_t* out_perm;
   int32_t* out_err;
   uint32_t* deferred;          // checks left to the bundle stages
@@ -106,6 +107,7 @@ struct LjArgs {
   unsigned* done;
   uint32_t pub_words, seq;
   uint32_t coherent;  // results written through the L2 (engine-stream batches published by the join)
+  uint32_t u_fixed;   // a list batch: the fixed id (closure.inc CjArgs::u_fixed)
   // the call's check contexts (a device copy of the batch's Ctx: caveat outcomes, the lazy
   // evaluation's request set, cav_flag), or null: a caveated pair is then CONDITIONAL
   const Ctx* cx;
@@ -130,7 +132,9 @@ struct LjArgs {
   union {
     struct {
       uint32_t u_rp, u_ss, u_ctx;
-      uint32_t cols;  // a cross batch (closure.inc CjArgs::cols) when n_shapes == 0; else 0 or part of `shapes`
+      // a cross batch (closure.inc CjArgs::cols) when n_shapes == 0 and list == 0; a list batch's
+      // range: its first id; else 0 or part of `shapes`
+      uint32_t cols;
     };
     struct {
       const uint8_t* shape_of;
@@ -717,16 +721,17 @@ __global__ void __launch_bounds__(kBlock) k_label_join(LjArgs a) {
   if (threadIdx.x < 2) s_pub[threadIdx.x] = 0u;
   // the wave's items are requested before the table: both loads in flight together
   const uint32_t w0 = (blockIdx.x * kWaves + (threadIdx.x >> 6)) * CPW;
-  const bool uni = a.pairs != nullptr;  // a uniform batch (a scalar branch)
+  const bool list = a.list != 0u;  // a list batch (closure.inc cj_block): its range form has no `pairs`
+  const bool uni = a.pairs != nullptr || list;  // a uniform batch (a scalar branch)
   const uint32_t item_bytes = w0 < a.n ? min(CPW, a.n - w0) * 20u : 0u;
   const unsigned char* ibase = reinterpret_cast<const unsigned char*>(a.items) + (size_t)w0 * 20u;
   const bool items_fast = !uni && ((uintptr_t)a.items & 15u) == 0 && item_bytes == CPW * 20u;
   u32x4 item_chunk{0u, 0u, 0u, 0u};
   if (items_fast && (threadIdx.x & 63u) < CPW * 20u / 16u)
     item_chunk = *(const GCK_GLOBAL u32x4*)(ibase + (threadIdx.x & 63u) * 16u);
-  // (not a cross batch's lanes: `pairs` is then the id block)
-  const bool grid = uni && a.n_shapes == 0u && a.cols != 0u;
-  if (uni && (threadIdx.x & 63u) < CPW && w0 + (threadIdx.x & 63u) < a.n && !grid) {  // (a uniform batch: the lane's pair)
+  // (not a cross batch's lanes: `pairs` is then the id block; nor a list batch's: the id list, or null)
+  const bool grid = uni && a.n_shapes == 0u && a.cols != 0u && !list;
+  if (uni && (threadIdx.x & 63u) < CPW && w0 + (threadIdx.x & 63u) < a.n && !grid && !list) {  // (a uniform batch: the lane's pair)
     const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(a.pairs + 2ull * (w0 + (threadIdx.x & 63u)));
     item_chunk.x = (uint32_t)pr;
     item_chunk.y = (uint32_t)(pr >> 32);
@@ -744,10 +749,19 @@ __global__ void __launch_bounds__(kBlock) k_label_join(LjArgs a) {
       item_chunk.w = *(const GCK_GLOBAL uint32_t*)(a.pairs + cross_sub_off(a.cols) + row);
     }
   }
+  // a list batch (closure.inc cj_block): the lane's one id — in range form computed — and the fixed
+  // id, in the chunk's spare registers until the table's barrier
+  if (__builtin_expect(list, 0)) {
+    if ((threadIdx.x & 63u) < CPW && w0 + (threadIdx.x & 63u) < a.n) {
+      item_chunk.w = a.u_fixed;
+      if (a.list & kListRange) item_chunk.z = a.cols + w0 + (threadIdx.x & 63u);
+      else item_chunk.z = *(const GCK_GLOBAL uint32_t*)(a.pairs + w0 + (threadIdx.x & 63u));
+    }
+  }
   // a shaped batch (closure.inc cj_block): the lane's index byte, and entry l of the shape table by
   // lane l < n_shapes, in the same round; the entries are staged in the wave's own stage region
   // (idle in this mode until the slots) and read by index after the table's barrier
-  const bool shaped = uni && a.n_shapes != 0u;
+  const bool shaped = uni && a.n_shapes != 0u;  // (a list batch's n_shapes is 0)
   const uint32_t n_shapes = min(a.n_shapes, (uint32_t)GCK_MAX_SHAPES);
   static_assert(CPW * kStride >= GCK_MAX_SHAPES * 4u, "the stage region holds the shape table");
   u32x4 shape_ent{0u, 0u, 0u, 0u};
@@ -775,6 +789,11 @@ __global__ void __launch_bounds__(kBlock) k_label_join(LjArgs a) {
   }
   __syncthreads();
   if (__builtin_expect(grid, 0)) item_chunk.x = item_chunk.z, item_chunk.y = item_chunk.w;
+  if (__builtin_expect(list, 0)) {  // (resource id, subject id): the varying id and the fixed one
+    const bool sub = (a.list & kListSubject) != 0u;
+    item_chunk.x = sub ? item_chunk.w : item_chunk.z;
+    item_chunk.y = sub ? item_chunk.z : item_chunk.w;
+  }
   const unsigned long long t_tab = (GCK_BUNDLE_TIMING && a.timing) ? wall_clock64() : 0ull;
   const uint16_t* root = reinterpret_cast<const uint16_t*>(s_tab);
   const LjMeta* meta = reinterpret_cast<const LjMeta*>(s_tab + a.o_meta);
@@ -1077,6 +1096,10 @@ __global__ void __launch_bounds__(kBlock) k_label_join(LjArgs a) {
     if (grid) {  // (a cross batch: its two ids by (row, column))
       uint32_t res_id, sub_id;
       cross_ids_again(a.pairs, a.cols, i, res_id, sub_id);
+      a.items_out[i] = uniform_item(a.u_rp, a.u_ss, a.u_ctx, res_id, sub_id);
+    } else if (list) {  // (a list batch: its varying id again, the fixed one beside it)
+      uint32_t res_id, sub_id;
+      list_ids_again(a.pairs, a.list, a.cols, a.u_fixed, i, res_id, sub_id);
       a.items_out[i] = uniform_item(a.u_rp, a.u_ss, a.u_ctx, res_id, sub_id);
     } else {
       const unsigned long long pr = *(const GCK_GLOBAL unsigned long long*)(a.pairs + 2ull * i);

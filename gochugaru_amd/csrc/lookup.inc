@@ -96,6 +96,55 @@ void device_lookup(Engine& e, Workspace& w, const gck_item& proto, bool vary_res
   e.stats.kernel_ms = ms;
 }
 
+// The per-item error that fails a lookup among candidates: device_lookup's code and message (that
+// function and device_lookup_subjects, left as they are, keep their own text of it).
+[[noreturn]] static void lookup_item_error(unsigned code) {
+  throw Error(GCK_E_INVALID_ARGUMENT,
+              code == GCK_ITEM_ERR_MAX_DEPTH ? "max depth exceeded: this usually indicates a recursive or too "
+                                               "deep data dependency"
+                                             : "lookup failed: per-item error " + std::to_string(code));
+}
+
+// A lookup among the caller's candidates (engine.hpp): one list request — the candidates' 4-B ids,
+// or the range of a whole type — through the compact path, so that its chunks are in flight over
+// both workspaces and each costs one join dispatch; the 2-bit plane comes back through the
+// workspaces' pinned result staging and is scanned here, zero words skipped. A candidate with a
+// per-item error fails the call as device_lookup fails: the largest code of the first chunk that
+// has one — the same chunks as that sweep's when max_batch is a multiple of 32 (it steps by
+// max_batch, the compact path by max_batch & ~31), so the same code.
+void device_lookup_among(Engine& e, Workspace* w0, Workspace* w1, const CompactReq& req, int64_t now_us,
+                         std::vector<uint32_t>& ids, std::vector<uint8_t>& perms) {
+  ids.clear();
+  perms.clear();
+  if (req.n == 0) return;
+  HIP_OK(hipSetDevice(e.device));
+  if (now_us == 0) now_us = wall_now_us();
+  std::vector<uint64_t> plane((req.n + 31) / 32);
+  CompactReq q = req;
+  q.packed = plane.data();
+  std::vector<gck_item_error> errs;  // (every chunk's, whole: no list of the caller's bounds them)
+  const size_t mb = compact_chunks(e, w0, w1, q, now_us, CavCall(), errs);
+  if (!errs.empty()) {
+    size_t chunk = ~(size_t)0;
+    for (const gck_item_error& x : errs) chunk = std::min(chunk, (size_t)x.index / mb);
+    unsigned code = 0;
+    for (const gck_item_error& x : errs)
+      if (x.index / mb == chunk) code = std::max(code, (unsigned)x.code);
+    lookup_item_error(code);
+  }
+  for (size_t wd = 0; wd < plane.size(); ++wd) {
+    uint64_t x = plane[wd];
+    if (!x) continue;
+    for (uint32_t b = 0; x; ++b, x >>= 2) {
+      const uint8_t pm = (uint8_t)(x & 3u);
+      if (pm != GCK_PERM_HAS && pm != GCK_PERM_CONDITIONAL) continue;
+      const size_t i = wd * 32 + b;
+      ids.push_back(q.ids ? q.ids[i] : q.first_id + (uint32_t)i);
+      perms.push_back(pm);
+    }
+  }
+}
+
 // ---- LookupSubjects: the walk ------------------------------------------------------------------
 
 struct EnumArgs {

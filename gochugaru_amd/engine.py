@@ -157,6 +157,8 @@ def unpack_results(words: np.ndarray, n: int) -> np.ndarray:
 
 
 CROSS_IDS = 2048  # GCK_CROSS_IDS
+VARY_RESOURCE = 1  # GCK_VARY_RESOURCE: a list request's ids are resource ids (the fixed id is the subject's)
+VARY_SUBJECT = 2   # GCK_VARY_SUBJECT: ... subject ids (the fixed id is the resource's)
 
 
 def unpack_cross(words: np.ndarray, S: int, R: int) -> np.ndarray:
@@ -297,6 +299,20 @@ _SIGS = {
                                          C.c_int64, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_P)]),
     "gck_cross_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "gck_cross_tile": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "gck_check_bulk_list": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), C.c_uint32, C.c_uint32, _P,
+                                      C.c_uint32, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t,
+                                      C.c_int64, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    "gck_check_submit_list": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), C.c_uint32, C.c_uint32, _P,
+                                        C.c_uint32, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                        C.c_size_t, C.c_int64, _P, _P, C.c_size_t, C.POINTER(C.c_size_t),
+                                        C.POINTER(_P)]),
+    "gck_list_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "gck_lookup_resources_among": (C.c_int, [_P, C.POINTER(_Consistency), C.c_uint16, C.c_uint16, C.c_uint16,
+                                             C.c_uint16, C.c_uint32, _P, C.c_size_t, C.c_int64, _P, _P, C.c_size_t,
+                                             C.POINTER(C.c_size_t)]),
+    "gck_lookup_subjects_among": (C.c_int, [_P, C.POINTER(_Consistency), C.c_uint16, C.c_uint32, C.c_uint16,
+                                            C.c_uint16, C.c_uint16, _P, C.c_size_t, C.c_int64, _P, _P, C.c_size_t,
+                                            C.POINTER(C.c_size_t)]),
     "gck_host_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "gck_host_free": (C.c_int, [_P, _P]),
     "gck_last_stats": (C.c_int, [_P, C.POINTER(_Stats)]),
@@ -400,6 +416,10 @@ def _driver():
         d.gckd_run_cross.argtypes = [C.c_void_p, C.c_void_p, _P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p, C.c_uint32, C.c_int64, C.POINTER(C.c_double)]
+        d.gckd_run_list.restype = C.c_int
+        d.gckd_run_list.argtypes = [C.c_void_p, C.c_void_p, _P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                    C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                    C.c_void_p, C.c_uint32, C.c_int64, C.POINTER(C.c_double)]
         d.gckd_set_trace.restype = None
         d.gckd_set_trace.argtypes = [C.c_void_p, C.c_size_t]
         _DRIVER = d
@@ -886,6 +906,74 @@ class Engine:
         _check(self._lib.gck_cross_stats(self._h, out))
         return int(out[0]), int(out[1])
 
+    @staticmethod
+    def _list_ids(ids, first_id, n):
+        """A list request's varying ids as the C ABI takes them: (array or None, first_id, n)."""
+        if ids is None:
+            if n is None:
+                raise ValueError("a range needs n")
+            return None, int(first_id), int(n)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        return ids, 0, len(ids) if n is None else int(n)
+
+    def check_list(self, header, fixed_id: int, vary: int, ids: Optional[np.ndarray] = None, first_id: int = 0,
+                   n: Optional[int] = None, requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0,
+                   now_us: int = 0, contexts: Optional[Sequence] = None, out_packed: Optional[np.ndarray] = None,
+                   out_errs: Optional[np.ndarray] = None):
+        """A list request (gck_check_bulk_list): one fixed id against n ids of the other side under
+        one `header` (as check_uniform's). `vary` = VARY_RESOURCE (fixed_id is the subject id) or
+        VARY_SUBJECT (fixed_id is the resource id); the varying ids are `ids` (u32, 4 B per check) or,
+        with ids=None, the range first_id .. first_id + n - 1. Returns (words, errors, evaluated
+        revision) as check_uniform does: unpack_results(words, n) gives the Permissionships."""
+        ids, first_id, n = self._list_ids(ids, first_id, n)
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        words = out_packed if out_packed is not None else np.zeros((n + 31) // 32, dtype=np.uint64)
+        errs = out_errs if out_errs is not None else np.zeros(min(n, 1 << 20), dtype=ITEM_ERROR_DTYPE)
+        cs = _Consistency(requirement, 0, revision)
+        ctx_arr, ctx_lens, n_ctx = _context_arrays(contexts)
+        n_errs = C.c_size_t(0)
+        rev = C.c_uint64(0)
+        _check(self._lib.gck_check_bulk_list(self._h, C.byref(cs), C.byref(hdr), fixed_id, vary,
+                                             ids.ctypes.data if ids is not None and len(ids) else None, first_id, n,
+                                             ctx_arr, ctx_lens, n_ctx, now_us, words.ctypes.data if len(words) else None,
+                                             errs.ctypes.data if len(errs) else None, len(errs), C.byref(n_errs),
+                                             C.byref(rev)))
+        return words, errs[:min(n_errs.value, len(errs))].copy(), rev.value
+
+    def submit_list(self, header, fixed_id: int, vary: int, out_packed: np.ndarray, out_errs: np.ndarray,
+                    ids: Optional[np.ndarray] = None, first_id: int = 0, n: Optional[int] = None,
+                    requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                    contexts: Optional[Sequence] = None) -> "ListBatch":
+        """gck_check_submit_list (one chunk: n <= max_batch): the results land in out_packed /
+        out_errs at wait(). A pinned id list (host_array) is read in place until then."""
+        ids, first_id, n = self._list_ids(ids, first_id, n)
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        b = ListBatch(self, hdr, ids, out_packed, out_errs)
+        cs = _Consistency(requirement, 0, revision)
+        ctx_arr, ctx_lens, n_ctx = _context_arrays(contexts)
+        _check(self._lib.gck_check_submit_list(self._h, C.byref(cs), C.byref(hdr), fixed_id, vary,
+                                               ids.ctypes.data if ids is not None and len(ids) else None, first_id, n,
+                                               ctx_arr, ctx_lens, n_ctx, now_us,
+                                               out_packed.ctypes.data if n else None,
+                                               out_errs.ctypes.data if len(out_errs) else None, len(out_errs),
+                                               C.byref(b._n_errs), C.byref(b._h)))
+        return b
+
+    def prepare_list(self, headers, fixed, vary: int, ids, first, ns, packed, errs, err_cap: int, depth: int,
+                     now_us: int = 0) -> "PreparedList":
+        """The compiled submit/wait loop over list requests (libgck_driver.so gckd_run_list): request
+        k = headers[k], the fixed id fixed[k], and ns[k] varying ids — the host pointer ids[k], or
+        with ids[k] == 0 the range from first[k] — with host pointers packed[k], errs[k] (err_cap
+        records); every request varies the side `vary`; `depth` in flight."""
+        return PreparedList(self, headers, fixed, vary, ids, first, ns, packed, errs, err_cap, depth, now_us)
+
+    def list_stats(self) -> Tuple[int, int]:
+        """gck_list_stats: list chunks whose join read the ids in place (or computed a range), and
+        chunks expanded to items on the host, since the engine was created."""
+        out = (C.c_uint64 * 2)()
+        _check(self._lib.gck_list_stats(self._h, out))
+        return int(out[0]), int(out[1])
+
     def check_bulk_device(self, d_items: int, n: int, d_perm: int, d_err: int,
                           stream: Optional[int] = None, now_us: int = 0,
                           contexts: Optional[Sequence] = None):
@@ -1012,6 +1100,37 @@ class Engine:
         return self._lookup(self._lib.gck_lookup_subjects,
                             (resource_type, resource_id, permission, subject_type, subject_relation, now_us),
                             requirement, revision)
+
+    def lookup_resources_among(self, resource_type: int, permission: int, subject_type: int, subject_relation: int,
+                               subject_id: int, candidates: Optional[np.ndarray] = None,
+                               requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0,
+                               now_us: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """gck_lookup_resources_among: of the candidate resource ids, those the subject has
+        `permission` on — in the candidates' order, repeats included — and their permissionship.
+        candidates=None: every object of the type (lookup_resources' answer)."""
+        now_us = now_us or time.time_ns() // 1000
+        cand = None if candidates is None else np.ascontiguousarray(candidates, dtype=np.uint32).reshape(-1)
+        if cand is not None and len(cand) == 0:  # (nothing to ask: a null list would mean the whole type)
+            return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8)
+        return self._lookup(self._lib.gck_lookup_resources_among,
+                            (resource_type, permission, subject_type, subject_relation, subject_id,
+                             None if cand is None else cand.ctypes.data, 0 if cand is None else len(cand), now_us),
+                            requirement, revision)
+
+    def lookup_subjects_among(self, resource_type: int, resource_id: int, permission: int, subject_type: int,
+                              candidates: np.ndarray, subject_relation: int = ELLIPSIS,
+                              requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0,
+                              now_us: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """gck_lookup_subjects_among: of the candidate subject ids, those that have `permission` on
+        the resource, in the candidates' order; a wildcard grant makes every candidate match (no
+        ID_WILDCARD entry)."""
+        now_us = now_us or time.time_ns() // 1000
+        cand = np.ascontiguousarray(candidates, dtype=np.uint32).reshape(-1)
+        if len(cand) == 0:
+            return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8)
+        return self._lookup(self._lib.gck_lookup_subjects_among,
+                            (resource_type, resource_id, permission, subject_type, subject_relation,
+                             cand.ctypes.data, len(cand), now_us), requirement, revision)
 
     # ---- partitioned graphs (gck_part_*; driven by gochugaru_amd.partition) -----------------
     def set_partition(self, rank: int, world: int):
@@ -1235,6 +1354,19 @@ class PreparedCross(_Prepared):
                       err_cap, self.n_errs, depth, now_us)
 
 
+class PreparedList(_Prepared):
+    """A compiled submit/wait loop over list requests with its argument arrays built
+    (Engine.prepare_list)."""
+
+    def __init__(self, engine, headers, fixed, vary, ids, first, ns, packed, errs, err_cap, depth, now_us):
+        super().__init__(engine, "gckd_run_list", "gck_check_submit_list", len(ns), depth)
+        arr = self._arr
+        u32 = lambda xs: (C.c_uint32 * max(1, len(xs)))(*[int(x) for x in xs])
+        hdrs = (Uniform * max(1, len(headers)))(*[_header(h) for h in headers])
+        self._args = (hdrs, u32(fixed), vary, arr(ids), u32(first), arr(ns), arr(packed), arr(errs), err_cap, self.n_errs,
+                      depth, now_us)
+
+
 class Batch:
     """A submitted batch (gck_batch): wait() completes it exactly once."""
 
@@ -1294,6 +1426,11 @@ class ShapedBatch(UniformBatch):
 class CrossBatch(UniformBatch):
     """A submitted cross request (gck_check_submit_cross): as UniformBatch; `packed` is the
     row-padded plane (unpack_cross)."""
+
+
+class ListBatch(UniformBatch):
+    """A submitted list request (gck_check_submit_list): as UniformBatch; it keeps the id list alive
+    until the wait."""
 
 
 def _context_json(ctx) -> str:

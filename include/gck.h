@@ -516,6 +516,44 @@ int gck_cross_stats(gck_engine* e, uint64_t out[2]);
  * small dispatches. */
 int gck_cross_tile(size_t n_subjects, size_t n_resources, size_t max_batch, uint32_t* rows, uint32_t* cols);
 
+/* ---- list requests (ABI 13, additive) ------------------------------------------------
+ * One fixed id against many ids of the other side, all of one shape — "which of these 60,000
+ * documents may this user see", and its mirror, "which of these users may see this document":
+ * one header, the fixed id, and 4 B per check — or nothing per check. `vary` says which side the
+ * n ids are: GCK_VARY_RESOURCE (fixed_id is the subject id) or GCK_VARY_SUBJECT (fixed_id is the
+ * resource id). Check i is (hdr, fixed_id, v_i) with
+ *   - an id list: v_i = ids[i]; in gck_host_alloc memory the kernels read it in place, under the
+ *     lifetime rule of a uniform request's `pairs` (a pageable list is staged as pageable pairs
+ *     are); `first_id` is ignored;
+ *   - a range: ids == NULL and v_i = first_id + i, the form of a sweep over a whole type. A range
+ *     varies the resource id.
+ * Semantics, consistency and request errors are gck_check_bulk_uniform's, ids included: they are
+ * not deduplicated, may be GCK_ID_ABSENT or GCK_ID_WILDCARD where that call allows them, and an
+ * id beyond the type's objects is answered as that call answers it (NO: the object has no
+ * relationships). Results are the uniform call's too: the dense plane of ceil(n / 32) words
+ * (padding bits 0, every word written), the ascending (index, GCK_ITEM_*) records under the same
+ * err_cap / *out_n_errs protocol. GCK_E_INVALID_ARGUMENT also for a `vary` that is neither value,
+ * a header whose `reserved` is not 0, a range with first_id + n > 2^32, and a range with
+ * GCK_VARY_SUBJECT. n == 0 succeeds and writes nothing. */
+#define GCK_VARY_RESOURCE 1u
+#define GCK_VARY_SUBJECT 2u
+int gck_check_bulk_list(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                        uint32_t vary, const uint32_t* ids, uint32_t first_id, size_t n, const char* const* contexts,
+                        const size_t* context_lens, size_t n_contexts, int64_t now_us, uint64_t* out_packed,
+                        gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs, uint64_t* out_revision);
+/* The same as an asynchronous batch of one chunk (n <= max_batch): completed by gck_check_wait or
+ * gck_check_wait_at, which write out_packed, out_errs and *out_n_errs. An id list in
+ * gck_host_alloc memory must stay unchanged until the wait returns; any other list is copied by
+ * the call. */
+int gck_check_submit_list(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                          uint32_t vary, const uint32_t* ids, uint32_t first_id, size_t n, const char* const* contexts,
+                          const size_t* context_lens, size_t n_contexts, int64_t now_us, uint64_t* out_packed,
+                          gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs, gck_batch** out);
+/* Since the engine was created: out[0] = chunks (of max_batch checks) whose join read the ids in
+ * place or computed them from the range, out[1] = chunks expanded to items on the host (check
+ * contexts, profiling, no one-round join, GCK_AQL=0). */
+int gck_list_stats(gck_engine* e, uint64_t out[2]);
+
 /* ---- lookups (Client.LookupResources / LookupSubjects, client/client.go:508-599) -------- */
 /* Ids of the `resource_type` objects on which the subject has `permission` — HAS or CONDITIONAL,
  * out_perm[k] says which — ascending. Every object of the type is checked on the device (the
@@ -535,6 +573,27 @@ int gck_lookup_resources(gck_engine* e, const gck_consistency* cs, uint16_t reso
 int gck_lookup_subjects(gck_engine* e, const gck_consistency* cs, uint16_t resource_type, uint32_t resource_id,
                         uint16_t permission, uint16_t subject_type, uint16_t subject_relation, int64_t now_us,
                         uint32_t* out_ids, uint8_t* out_perm, size_t cap, size_t* out_n);
+
+/* Lookups among the caller's candidates (ABI 13, additive): of the `n_candidates` ids of
+ * `candidates`, those on which the subject has `permission` (HAS or CONDITIONAL, out_perm[k] says
+ * which) — in the candidates' order, an id as often as the list repeats it. The candidates run as
+ * one list request (above), 4 B per candidate in, 2 bits out, and the plane is scanned on the host.
+ * candidates == NULL: every object of the type, as the one range [0, object count) — the result
+ * of gck_lookup_resources. Protocol and errors are gck_lookup_resources': *out_n, GCK_E_CAPACITY
+ * and the per-thread kept result (a retry with the same arguments and candidates at the same
+ * explicit now_us does not check again); a candidate with a per-item error fails the call. */
+int gck_lookup_resources_among(gck_engine* e, const gck_consistency* cs, uint16_t resource_type, uint16_t permission,
+                               uint16_t subject_type, uint16_t subject_relation, uint32_t subject_id,
+                               const uint32_t* candidates, size_t n_candidates, int64_t now_us, uint32_t* out_ids,
+                               uint8_t* out_perm, size_t cap, size_t* out_n);
+/* The mirror: of the candidate subjects (of `subject_type` with `subject_relation`), those that
+ * have `permission` on one resource. A candidate list is required (NULL with n_candidates > 0 is
+ * GCK_E_INVALID_ARGUMENT). No wildcard entry is reported: a wildcard grant makes every candidate
+ * match. */
+int gck_lookup_subjects_among(gck_engine* e, const gck_consistency* cs, uint16_t resource_type, uint32_t resource_id,
+                              uint16_t permission, uint16_t subject_type, uint16_t subject_relation,
+                              const uint32_t* candidates, size_t n_candidates, int64_t now_us, uint32_t* out_ids,
+                              uint8_t* out_perm, size_t cap, size_t* out_n);
 
 /* ---- partitioned graphs (graphs above one GPU's 288 GB) ----------------
  * Rank r of `world` (one process per GPU) owns the objects whose names hash to it
