@@ -549,7 +549,7 @@ static UserLists build_user_slots(uint32_t bits, const uint32_t* off, const uint
     // (u32 offsets; a total that wrapped cannot be told apart, so stay well below 2^31)
     if (out.total > 0 && out.total < (1u << 31)) out.list = alloc_list((size_t)out.total * 4);
     if (out.total) {
-      hipLaunchKernelGGL(k_user_lists, dim3(grid_for(n)), dim3(kBlock), 0, 0, off, nbr, n, cov_off, cov_pre, len, loff,
+      hipLaunchKernelGGL(bits == 24 ? k_user_lists<24> : k_user_lists<32>, dim3(grid_for(n)), dim3(kBlock), 0, 0, off, nbr, n, cov_off, cov_pre, len, loff,
                          out.list, slots);
       HIP_OK(hipGetLastError());
     }

@@ -37,16 +37,13 @@ constexpr uint32_t kCjLdsBytesSmall = 2048;  // ... by the variant for small sch
 // slot fast path (below): entries a user / resource slot holds inline
 // cover entries a user slot holds inline: 32-bit preorder numbers, or 24-bit ones when the
 // hierarchy has at most 2^24 groups (the snapshot picks; slot_cap)
+// (the user slot's layout — kUSlotWords, slot_cap, kSlotOverflow, kSlotList and a listed slot's
+// inline entries and window — is slot_pack.hpp's)
 constexpr int kSlotG = 15;             // at 32 bits (the decision loop's bound is slot_cap<BITS>)
-template <int BITS> constexpr int slot_cap() { return BITS == 24 ? 20 : 15; }
 constexpr int kSlotGMax = 20;
 constexpr int kSlotV = 7;              // intervals of a resource's groups V(R) (more: the task rounds)
 constexpr uint32_t kCoverMax = 15;     // cover entries per group (more: the group overflows)
-constexpr uint32_t kUSlotWords = 16;   // 64 B per user: count, cover entries
 constexpr uint32_t kDSlotWords = 16;   // 64 B per resource: count, (pre, end) per group
-constexpr uint32_t kSlotOverflow = 0x80000000u;
-constexpr uint32_t kSlotList = 0x40000000u;  // user slot: the covers are a list (w[1] = its offset in ucov)
-template <int BITS> constexpr uint32_t kSlotUnused = BITS == 32 ? 0xFFFFFFFFu : (1u << BITS) - 1u;
 // half slots: what the first 32 B of a slot hold — the cover entries in words 1-7 (9 at 24 bits, 7
 // at 32) and the intervals in words 2-7 (3). The rest of a user slot is all ones then (unused
 // entries), the rest of a resource slot zero (empty intervals).
@@ -416,8 +413,10 @@ __device__ __forceinline__ bool sig_has(const uint32_t (&s)[kSigWords], uint32_t
 //                on the way up adds one entry. Proof of exactness: an upward path from g ends, after
 //                its last non-tree edge y -> p, in p's tree ancestors, and p is covered;
 //   user slot    64 B per user: the preorder numbers of the covers of all its groups — or, when
-//                they exceed the slot, where they lie in a list array (one more round for that
-//                user's check);
+//                they exceed the slot even sorted and without duplicates, 18 of them (13 at 32
+//                bits), the open range in which the others lie, and where the whole sorted list
+//                lies in a list array (slot_pack.hpp: one more round for that user's check only
+//                when neither the inline entries nor the range decide it);
 //   resource slot 64 B per resource: the interval [pre(v), end(v)) of each of its groups v.
 //
 // A check reads its two slots together and is HAS iff some cover entry lies in some interval —
@@ -434,7 +433,7 @@ __device__ __forceinline__ uint32_t user_cover_count(const uint32_t* t_off, cons
     const uint32_t g = t_nbr[b + k];
     if (g >= n_groups || (lab[2 * (size_t)g] & kSlotOverflow)) return kSlotOverflow;
     m += cov_off[g + 1] - cov_off[g];
-    if (m >= kSlotList) return kSlotOverflow;
+    if (m > kSlotCount) return kSlotOverflow;
   }
   return m;
 }
@@ -471,6 +470,19 @@ __device__ __forceinline__ void slot_put_at(uint32_t (&w)[kUSlotWords], uint32_t
   }
 }
 
+// The slot of a user whose `total` raw cover entries, more than a slot holds, were written to
+// e = list + list_at (slot_pack.hpp): up to kSlotSortMax of them are sorted there and lose their
+// duplicates — the user then gets an inline slot if they fit now (its list stays unused), and a
+// listed slot with inline entries and a window over the sorted list otherwise. More: a plain list.
+template <int BITS>
+__device__ __forceinline__ void user_slot_listed(uint32_t* e, uint32_t total, uint32_t list_at, uint32_t* w) {
+  if (total > kSlotSortMax) {
+    slot_pack_plain_list(BITS, total, list_at, w);
+    return;
+  }
+  slot_pack_sorted(BITS, e, slot_sort_unique(e, total), list_at, w);
+}
+
 // The slot of user u: the covers of its groups, inline, or in the list at `list_at` (kNone: no
 // list, such a user overflows).
 template <int BITS>
@@ -492,8 +504,10 @@ __device__ __forceinline__ void user_slot(const uint32_t* __restrict__ t_off, co
         const uint32_t g = t_nbr[b + k];
         for (uint32_t c = cov_off[g]; c < cov_off[g + 1]; ++c) list[list_at + m++] = cov_pre[c];
       }
-      w[0] = kSlotList | total;
-      w[1] = list_at;
+      uint32_t lw[kUSlotWords];  // (indexed by entry: memory, apart from the inline slot's registers)
+      user_slot_listed<BITS>(list + list_at, total, list_at, lw);
+#pragma unroll
+      for (uint32_t k = 0; k < kUSlotWords; ++k) w[k] = lw[k];
     } else {
       w[0] = kSlotOverflow;
     }
@@ -514,8 +528,9 @@ __device__ __forceinline__ void user_slot(const uint32_t* __restrict__ t_off, co
 }
 
 // One pass over every user (the random reads of its groups' labels and covers once): inline slots
-// written; a user whose covers need a list gets kSlotList | count in word 0 and its list length in
-// len[u] (0 for everyone else) — k_user_lists then writes the lists at the scanned offsets.
+// written; a user with more raw cover entries than a slot holds gets their number in len[u] (0 for
+// everyone else) and a placeholder slot — k_user_lists then writes the lists at the scanned offsets
+// and those users' slots whole (user_slot_listed, slot_pack.hpp: inline after all, or listed).
 template <int BITS>
 __global__ void __launch_bounds__(kBlock) k_user_slots_1p(const uint32_t* __restrict__ t_off, const uint32_t* __restrict__ t_nbr,
                                                           uint32_t n_users, const uint32_t* __restrict__ lab,
@@ -536,8 +551,9 @@ __global__ void __launch_bounds__(kBlock) k_user_slots_1p(const uint32_t* __rest
   for (uint32_t j = 1; j < kUSlotWords / 4; ++j) out[j] = make_uint4(0u, 0u, 0u, 0u);
 }
 
-// The cover lists of the users k_user_slots_1p marked (len[u] > 0) at list_off[u], and their slot's
-// word 1; without a list array (too large) those users overflow instead.
+// The cover lists of the users k_user_slots_1p marked (len[u] > 0) at list_off[u], and their slots
+// (user_slot_listed); without a list array (too large) those users overflow instead.
+template <int BITS>
 __global__ void __launch_bounds__(kBlock) k_user_lists(const uint32_t* __restrict__ t_off, const uint32_t* __restrict__ t_nbr,
                                                        uint32_t n_users, const uint32_t* __restrict__ cov_off,
                                                        const uint32_t* __restrict__ cov_pre, const uint32_t* __restrict__ len,
@@ -556,7 +572,10 @@ __global__ void __launch_bounds__(kBlock) k_user_lists(const uint32_t* __restric
     const uint32_t g = t_nbr[b + k];
     for (uint32_t c = cov_off[g]; c < cov_off[g + 1]; ++c) list[at + m++] = cov_pre[c];
   }
-  w[1] = at;
+  uint32_t lw[kUSlotWords];
+  user_slot_listed<BITS>(list + at, m, at, lw);
+  uint4* out = reinterpret_cast<uint4*>(w);
+  for (uint32_t j = 0; j < kUSlotWords / 4; ++j) out[j] = make_uint4(lw[4 * j], lw[4 * j + 1], lw[4 * j + 2], lw[4 * j + 3]);
 }
 
 // The slots of the users ids[0, n) only (a Watch batch's, delta.inc), into staged[i]; their lists
@@ -637,31 +656,45 @@ __device__ __forceinline__ void slot_unpack(const uint32_t (&w)[kUSlotWords], ui
   }
 }
 
+// The entries the decision loop runs over for a slot with header w0.
+template <int BITS>
+__device__ __forceinline__ uint32_t slot_inline_count(uint32_t w0) {
+  return (w0 & kSlotOverflow) ? 0u : (w0 & kSlotList) ? (uint32_t)slot_inline_cap<BITS>() : w0;
+}
+
 // The slot test of one check over its user slot w and resource slot d: 2 = HAS, 1 = NO,
-// 3 = the user's covers are a list (the list round decides), 0 = a slot overflowed (the task
-// rounds decide). The loops run to the wave's largest entry and interval counts
-// (ng_max, nv_max: wave-uniform, so the bounds are scalar branches), every lane over all of
-// them — unused entries are all ones and unused intervals empty, so neither can hit. One
-// unsigned compare per (entry, interval): lo <= p < hi iff p - lo < hi - lo.
+// 3 = the user's covers are a list and neither its inline entries nor its window decide (the list
+// round does), 0 = a slot overflowed (the task rounds decide). A listed slot (slot_pack.hpp) goes
+// through the same loop as an inline one: its last two entry positions, the list's offset, count
+// as unused, and beside each interval's entry tests stands the window's — can [lo, end) hold a
+// point of the open range (lo1 - 1, hi) in which every omitted entry lies. The loops run to the
+// wave's largest entry and interval counts (ng_max, nv_max: wave-uniform, so the bounds are scalar
+// branches), every lane over all of them — unused entries are all ones and unused intervals empty,
+// so neither can hit. One unsigned compare per (entry, interval): lo <= p < hi iff p - lo < hi - lo.
 template <int BITS>
 __device__ __forceinline__ uint32_t slot_decide_wave(const uint32_t (&w)[kUSlotWords], const uint32_t (&d)[kDSlotWords],
                                                      uint32_t ng_max, uint32_t nv_max) {
   if ((d[0] | w[0]) & kSlotOverflow) return 0u;
-  if (w[0] & kSlotList) return d[0] ? 3u : 1u;  // (no groups on the resource: NO)
+  const bool listed = (w[0] & kSlotList) != 0u;
   uint32_t p[kSlotGMax];
   slot_unpack<BITS>(w, p);
-  bool hit = false;
+  constexpr int kIn = slot_inline_cap<BITS>();
+  if (listed) p[kIn] = p[kIn + 1] = kSlotUnused<BITS>;
+  const uint32_t hi = (w[0] & kSlotHiOpen) ? 0xFFFFFFFFu : p[0];
+  const uint32_t lo1 = (w[0] & kSlotLoOpen) ? 0u : p[kIn - 1] + 1u;
+  bool hit = false, open = false;  // (open: an interval reaches into the window; empty intervals are [0, 0): never)
 #pragma unroll
   for (int j = 0; j < kSlotV; ++j) {
     if ((uint32_t)j >= nv_max) break;
     const uint32_t lo = d[2 + 2 * j], len = d[3 + 2 * j] - lo;
+    open |= lo < hi && d[3 + 2 * j] > lo1;
 #pragma unroll
     for (int k = 0; k < slot_cap<BITS>(); ++k) {
       if ((uint32_t)k >= ng_max) break;
       hit |= p[k] - lo < len;
     }
   }
-  return hit ? 2u : 1u;
+  return hit ? 2u : (listed && open) ? 3u : 1u;
 }
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -978,15 +1011,15 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
     }
     uint32_t ng_l = 0, nv_l = 0;
     if (ua) {
-      ng_l = (w[0] & (kSlotOverflow | kSlotList)) ? 0u : w[0];
+      ng_l = slot_inline_count<BITS>(w[0]);
       nv_l = (dd[0] & kSlotOverflow) ? 0u : dd[0];
     }
     const uint32_t ng_max = wave_max(ng_l), nv_max = wave_max(nv_l);
     if (ua) {
       fast = slot_decide_wave<BITS>(w, dd, ng_max, nv_max);
       if (fast == 3u) {
-        l_cnt = w[0] & ~(kSlotList | kSlotOverflow);
-        l_ptr = lbase + (unsigned long long)w[1] * 4u;
+        l_cnt = slot_list_count(w[0]);
+        l_ptr = lbase + (unsigned long long)slot_list_off(w) * 4u;
         if (!lbase) fast = 0u;  // (no list array: the task rounds)
       }
     }
@@ -1035,20 +1068,22 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
     // the wave's largest entry and interval counts bound the decision loops
     uint32_t ng_l = 0, nv_l = 0;
     if (ua) {
-      ng_l = (w[0] & (kSlotOverflow | kSlotList)) ? 0u : w[0];
+      ng_l = slot_inline_count<BITS>(w[0]);
       nv_l = (dd[0] & kSlotOverflow) ? 0u : dd[0];
     }
     const uint32_t ng_max = wave_max(ng_l), nv_max = wave_max(nv_l);
     if (ua) {
       fast = slot_decide_wave<BITS>(w, dd, ng_max, nv_max);
       if (fast == 3u) {
-        l_cnt = w[0] & ~(kSlotList | kSlotOverflow);
-        l_ptr = lbase + (unsigned long long)w[1] * 4u;
+        l_cnt = slot_list_count(w[0]);
+        l_ptr = lbase + (unsigned long long)slot_list_off(w) * 4u;
         if (!lbase) fast = 0u;  // (no list array: the task rounds)
       }
     }
   }
   const unsigned long long t_slot1 = timed ? wall_clock64() : 0ull;
+  // (timing builds: the wave's checks that go into round 1b; the bits above n_take in its word)
+  const uint32_t n_list = timed ? (uint32_t)__popcll(__ballot(fast == 3u)) : 0u;
   // ---- round 1b: the cover lists of users whose covers exceed a slot, one (check, entry) task
   // per lane slot, against the check's intervals staged in LDS ------------------------------------
   if (__builtin_expect(__ballot(fast == 3u) != 0, 0)) {
@@ -1100,8 +1135,9 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
   // well as the loops — and the branch is marked unlikely, as the other rare ones are, so that the
   // compiler lays the slot path out as straight-line code with the rare rounds behind it: a
   // skipped round in the middle of the path cost the waves of a batch, which start together after
-  // the dispatch has invalidated the instruction cache, a miss each (the timing build showed
-  // 1.2 us between the slot decisions and the extents in waves with no list at all).
+  // the dispatch has invalidated the instruction cache, a miss each. (The 1.2 us the timing build
+  // showed between the slot decisions and the extents was the list round itself: more than half of
+  // the flagship's waves held a listed check until listed slots carried inline entries and a window.)
   uint32_t total = 0, probes = 0;
   unsigned long long t_r1 = t_slots;
   if (__builtin_expect(__ballot(active && !fast) != 0, 0)) {
@@ -1338,7 +1374,7 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
       t[4] = wall_clock64();
       t[5] = total;
       t[6] = wave_probes;
-      t[7] = n_take;
+      t[7] = n_take | (unsigned long long)n_list << 32;
       t[8] = t_items;
       t[9] = t_slots;
       t[10] = t_slot1;

@@ -43,6 +43,7 @@
 #include <type_traits>
 
 #include "engine.hpp"
+#include "slot_pack.hpp"
 
 namespace gck {
 

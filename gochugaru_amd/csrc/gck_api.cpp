@@ -13,6 +13,7 @@
 #include <thread>
 
 #include "engine.hpp"
+#include "slot_pack.hpp"
 
 namespace gck {
 
@@ -1663,6 +1664,27 @@ int gck_reset_stats(gck_engine* ge) {
     Engine& e = need(ge);
     e.stats = gck_stats{};
   });
+}
+
+// Test hooks (gck_test_*: not in gck.h, no part of the ABI): the user-slot packing the slot-build
+// kernels run (slot_pack.hpp), on the host. gck_test_slot_window: where the omitted run of m sorted
+// unique entries begins when n_in stay inline. gck_test_slot_pack: n raw entries (sorted and
+// deduplicated in a copy; more than kSlotSortMax: a plain list of n) into the 16 words of a slot at
+// `bits` (24 or 32), as user_slot_listed does for more entries than a slot's cap; returns the number
+// of entries the list holds, or -1 for bad arguments.
+uint32_t gck_test_slot_window(const uint32_t* e, uint32_t m, uint32_t n_in) { return gck::slot_window(e, m, n_in); }
+
+int gck_test_slot_pack(uint32_t bits, const uint32_t* raw, uint32_t n, uint32_t list_at, uint32_t* w) {
+  if ((bits != 24 && bits != 32) || n > gck::kSlotCount || !raw || !w) return -1;
+  if (n > gck::kSlotSortMax) {
+    gck::slot_pack_plain_list(bits, n, list_at, w);
+    return (int)n;
+  }
+  uint32_t e[gck::kSlotSortMax];
+  for (uint32_t k = 0; k < n; ++k) e[k] = raw[k];
+  const uint32_t m = gck::slot_sort_unique(e, n);
+  gck::slot_pack_sorted(bits, e, m, list_at, w);
+  return (int)m;
 }
 
 }  // extern "C"

@@ -553,8 +553,8 @@ __device__ __noinline__ uint32_t lj_decide_wave(const LjMeta& M, uint32_t u, con
   const bool ext = (hdr & kLjHdrExt) != 0u;
   const uint32_t* rec = ext ? M.rext + rw[1] : nullptr;
   const bool list = (uw[0] & kSlotList) != 0u;
-  const uint32_t* lp = list ? M.ulist + uw[1] : nullptr;
-  const uint32_t ng = list ? uw[0] & ~(kSlotList | kSlotOverflow) : uw[0];
+  const uint32_t* lp = list ? M.ulist + slot_list_off(uw) : nullptr;
+  const uint32_t ng = list ? slot_list_count(uw[0]) : uw[0];
   uint32_t cov[kSlotGMax];
   if (!list) {
     uint32_t w[kUSlotWords];
@@ -622,8 +622,8 @@ __device__ __forceinline__ uint32_t lj_decide_wave_cav(const LjMeta& M, uint32_t
   const bool ext = (hdr & kLjHdrExt) != 0u;
   const uint32_t* rec = ext ? M.rext + rw[1] : nullptr;
   const bool list = (uw[0] & kSlotList) != 0u;
-  const uint32_t* lp = list ? M.ulist + uw[1] : nullptr;
-  const uint32_t ng = list ? uw[0] & ~(kSlotList | kSlotOverflow) : uw[0];
+  const uint32_t* lp = list ? M.ulist + slot_list_off(uw) : nullptr;
+  const uint32_t ng = list ? slot_list_count(uw[0]) : uw[0];
   uint32_t cov[kSlotGMax];
   if (!list) {
     uint32_t w[kUSlotWords];
@@ -933,7 +933,7 @@ __global__ void __launch_bounds__(kBlock) k_label_join(LjArgs a) {
           const uint32_t lo = rw[hub_w] & ~kSlotOverflow, len = rw[hub_w + 1] - lo;
           bool has;
           if (uw[0] & kSlotList) {
-            has = LjListCovers{M.ulist + uw[1], uw[0] & ~(kSlotList | kSlotOverflow)}.any_in(lo, len);
+            has = LjListCovers{M.ulist + slot_list_off(uw), slot_list_count(uw[0])}.any_in(lo, len);
           } else {
             LjInlineCovers<BITS> ci;
             slot_unpack<BITS>(uw, ci.p);
@@ -950,7 +950,7 @@ __global__ void __launch_bounds__(kBlock) k_label_join(LjArgs a) {
           // entry-by-entry walk tells the pairs apart)
           heavy = true;
         } else if (uw[0] & kSlotList) {
-          LjListCovers cl{M.ulist + uw[1], uw[0] & ~(kSlotList | kSlotOverflow)};
+          LjListCovers cl{M.ulist + slot_list_off(uw), slot_list_count(uw[0])};
           res = lj_decide_root(M, it.subject_id, hdr, rw, rec, cl, cavf);
         } else {
           LjInlineCovers<BITS> ci;
@@ -1073,7 +1073,7 @@ __global__ void __launch_bounds__(kBlock) k_label_join(LjArgs a) {
     const uint32_t hdr = rw[0];
     const uint32_t* rec = (hdr & kLjHdrExt) ? M3.rext + rw[1] : nullptr;
     if (uw[0] & kSlotList) {
-      LjListCovers cl{M3.ulist + uw[1], uw[0] & ~(kSlotList | kSlotOverflow)};
+      LjListCovers cl{M3.ulist + slot_list_off(uw), slot_list_count(uw[0])};
       res = lj_redecide<CL>(M3, a, it.resource_id, it.subject_id, hdr, rw, rec, cl, cavf, wres, wdirty);
     } else {
       LjInlineCovers<BITS> ci;
@@ -1369,7 +1369,7 @@ __global__ void __launch_bounds__(kBlock) k_pj_pack(LjTab T, const gck_item* __r
     if (w0 & kSlotOverflow) {
       has = false;  // (undecidable from slots: the level loop)
     } else if (w0 & kSlotList) {
-      n_cont = ((w0 & ~(kSlotList | kSlotOverflow)) + 15u) / 16u;
+      n_cont = (slot_list_count(w0) + 15u) / 16u;
       if (n_cont > kPjMaxCont) has = false;
     }
   }
@@ -1401,8 +1401,8 @@ __global__ void __launch_bounds__(kBlock) k_pj_pack(LjTab T, const gck_item* __r
 #pragma unroll
   for (uint32_t q = 0; q < kUSlotWords / 4; ++q) rec[(size_t)k * R4 + 1 + q] = v[q];
   if (n_cont) {
-    const uint32_t ng = v[0].x & ~(kSlotList | kSlotOverflow);
-    const uint32_t* list = M.ulist + v[0].y;
+    const uint32_t ng = slot_list_count(v[0].x);
+    const uint32_t* list = M.ulist + v[kUSlotWords / 4 - 1].w;  // (slot_list_off: the slot's last word)
     for (uint32_t c = 0; c < n_cont; ++c) {
       GCK_GLOBAL u32x4* cr = rec + (size_t)(k + 1 + c) * R4;
       cr[0] = u32x4{kPjCont, 0u, 0u, 0u};
@@ -1461,7 +1461,7 @@ __global__ void __launch_bounds__(kBlock) k_pj_decide(LjTab T, const gck_item* _
     if (hi & kLjDeep) return;
     const uint32_t lo = gptr(lab)[0] & ~kSlotOverflow, len = hi - lo;
     if (uw[0] & kSlotList) {  // (the list came along in the continuation records)
-      has = LjRecCovers{cont, uw[0] & ~(kSlotList | kSlotOverflow)}.any_in(lo, len);
+      has = LjRecCovers{cont, slot_list_count(uw[0])}.any_in(lo, len);
     } else {
       LjInlineCovers<BITS> ci;
       slot_unpack<BITS>(uw, ci.p);
@@ -1474,7 +1474,7 @@ __global__ void __launch_bounds__(kBlock) k_pj_decide(LjTab T, const gck_item* _
     if (hdr & kSlotOverflow) return;
     const uint32_t* rx = (hdr & kLjHdrExt) ? M.rext + gptr(rw)[1] : nullptr;
     if (uw[0] & kSlotList) {
-      const LjRecCovers cr{cont, uw[0] & ~(kSlotList | kSlotOverflow)};
+      const LjRecCovers cr{cont, slot_list_count(uw[0])};
       res = lj_decide_root(M, it.subject_id, hdr, rw, rx, cr, cavf);
     } else {
       LjInlineCovers<BITS> ci;
