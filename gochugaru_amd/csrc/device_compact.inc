@@ -1,0 +1,231 @@
+// Compact requests over device buffers (include/gck.h gck_check_bulk_uniform_device ...): what the
+// host does for a compact request over host buffers — expanding a chunk to items, packing the
+// 2-bit words, patching the checks the join left into them, listing the errors in ascending order
+// (compact_expand, uniform_collect, uniform_errors) — done by kernels, so that no per-check data
+// crosses PCIe. Included by engine.hip.
+//
+// In place (CompactRun::kInPlace with `device`): the join reads the caller's pairs / index bytes /
+// id list and writes the caller's plane; the checks it leaves are answered by the bundle stages
+// into the workspace's d_perm / d_err, and k_dc_patch + k_dc_emit put them into the plane and the
+// error list — only when the join left checks, so the common batch has no launch beyond its join.
+// Expanded (kExpanded with `device`): k_dc_expand writes the chunk's items into the workspace's item
+// array, the chunk runs as a device batch into d_perm / d_err, and k_dc_pack + k_dc_emit write the
+// plane and the list.
+//
+// The error list: a per-workspace bitmap, one bit per check of the chunk (set by k_dc_patch or
+// k_dc_pack, cleared by k_dc_emit, so it is zero between batches), turned into records by one block:
+// popcount per word, an exclusive scan over the block, records at base + rank while below err_cap.
+// `base` is the request's count so far on the device (the caller's *d_out_n_errs, or the word of the
+// request's first workspace), so the chunks of a request, emitted in chunk order, accumulate.
+
+// The shapes of a request, by value in the kernarg segment (a uniform or list request: one entry).
+struct DcShapes {
+  gck_uniform s[GCK_MAX_SHAPES];
+};
+
+struct DcExpand {
+  const uint32_t* ids;      // the chunk's pairs (8 B per check), or a list chunk's ids (4 B), or null: a range
+  const uint8_t* shape_of;  // the chunk's index bytes; null: every check is shape 0
+  gck_item* items;          // out: n items
+  uint32_t* bad;            // the smallest check of the chunk whose index byte is beyond the table (atomic min)
+  uint32_t n, n_shapes;
+  uint32_t vary;            // 0: pairs; GCK_VARY_RESOURCE / GCK_VARY_SUBJECT: a list chunk
+  uint32_t fixed_id, first_id;
+};
+
+// compact_expand on the device: check i of the chunk as a 20-B item. A check whose index byte is
+// beyond the table becomes shape 0's item (harmless: the request fails afterwards).
+__global__ void k_dc_expand(DcExpand a, DcShapes t) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  uint32_t s = a.shape_of ? a.shape_of[i] : 0u;
+  if (s >= a.n_shapes) {
+    atomicMin(a.bad, i);
+    s = 0u;
+  }
+  const gck_uniform h = t.s[s];
+  uint32_t res, sub;
+  if (a.vary) {
+    const uint32_t v = a.ids ? a.ids[i] : a.first_id + i;
+    res = a.vary == GCK_VARY_SUBJECT ? a.fixed_id : v;
+    sub = a.vary == GCK_VARY_SUBJECT ? v : a.fixed_id;
+  } else {
+    res = a.ids[2ull * i];
+    sub = a.ids[2ull * i + 1];
+  }
+  gck_item it;
+  it.resource_type = h.resource_type;
+  it.permission = h.permission;
+  it.resource_id = res;
+  it.subject_type = h.subject_type;
+  it.subject_relation = h.subject_relation;
+  it.subject_id = sub;
+  it.context_slot = h.context_slot;
+  a.items[i] = it;
+}
+
+// The chunk's results as 2-bit words and its error bits: a wave takes 64 checks, that is two words,
+// each half-wave OR-reducing its 32 results; lanes 0 and 32 write. Every word of the chunk
+// (ceil(n / 32)) is written, tail bits 0 (lanes beyond n contribute nothing).
+__global__ void k_dc_pack(const uint8_t* perm, const int32_t* err, uint32_t n, unsigned long long* out, uint32_t* bitmap) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t l = threadIdx.x & 31u;
+  const bool in = i < n;
+  const bool bad = in && err[i] != 0;
+  const uint32_t v = in && !bad ? (uint32_t)perm[i] & 3u : 0u;
+  uint32_t lo = l < 16u ? v << (2u * l) : 0u, hi = l >= 16u ? v << (2u * (l - 16u)) : 0u;
+  for (int d = 16; d >= 1; d >>= 1) {
+    lo |= (uint32_t)__shfl_xor((int)lo, d, 32);
+    hi |= (uint32_t)__shfl_xor((int)hi, d, 32);
+  }
+  const unsigned long long bits = __ballot(bad);
+  const uint32_t word = i >> 5, words = (n + 31u) / 32u;  // (n <= max_batch: no overflow)
+  if (l == 0u && word < words) {
+    out[word] = (unsigned long long)hi << 32 | lo;
+    bitmap[word] = (threadIdx.x & 32u) ? (uint32_t)(bits >> 32) : (uint32_t)bits;
+  }
+}
+
+// The checks the join of an in-place chunk left (its deferred list, n_left entries), answered by the
+// bundle stages into perm / err: an error sets the check's bit of the bitmap, a result is OR-ed
+// into the plane — the join wrote 0 there, and two such checks may share a word.
+__global__ void k_dc_patch(const uint32_t* left, uint32_t n_left, uint32_t n, const uint8_t* perm, const int32_t* err,
+                           unsigned long long* out, uint32_t* bitmap) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_left) return;
+  const uint32_t i = left[k];
+  if (i >= n) return;
+  if (err[i] != 0) {
+    atomicOr(&bitmap[i >> 5], 1u << (i & 31u));
+  } else {
+    const unsigned long long v = (unsigned long long)(perm[i] & 3u) << (2u * (i & 31u));
+    if (v) atomicOr(&out[i >> 5], v);
+  }
+}
+
+// The bitmap's `words` words as ascending (index, code) records: one block, a tile of blockDim words
+// at a time. Record r of the request (r counts from *count, the chunks before this one) is written
+// while r < cap; *count becomes the request's count so far. Clears the bitmap.
+__global__ void k_dc_emit(uint32_t* bitmap, uint32_t words, const int32_t* err, uint32_t pos, gck_item_error* out,
+                          uint32_t cap, uint32_t* count) {
+  __shared__ uint32_t wave_tot[kWaves];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t base = *count;
+  __syncthreads();  // (every thread has read the count before thread 0 writes it)
+  uint32_t run = 0;
+  for (uint32_t t0 = 0; t0 < words; t0 += blockDim.x) {
+    const uint32_t t = t0 + threadIdx.x;
+    uint32_t word = 0;
+    if (t < words) {
+      word = bitmap[t];
+      if (word) bitmap[t] = 0u;
+    }
+    const uint32_t pc = __popc(word);
+    uint32_t incl = pc;
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
+      if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63u) wave_tot[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, tot = 0;
+    for (uint32_t k = 0; k < (uint32_t)kWaves; ++k) {
+      if (k < wave) before += wave_tot[k];
+      tot += wave_tot[k];
+    }
+    uint32_t rank = base + run + before + incl - pc;
+    while (word) {
+      const uint32_t b = (uint32_t)__ffs((int)word) - 1u;
+      word &= word - 1u;
+      const uint32_t i = t * 32u + b;
+      if (rank < cap) out[rank] = gck_item_error{pos + i, err[i]};
+      ++rank;
+    }
+    run += tot;
+    __syncthreads();  // (wave_tot is rewritten by the next tile)
+  }
+  if (threadIdx.x == 0) *count = base + run;
+}
+
+// The word a device request counts its errors in, cleared on `st` before the request's first chunk:
+// the caller's, or the workspace's own (which stays 0 until an emit adds to it).
+// (the caller's word of a submitted batch is left to the batch: CompactRun::zero_cnt)
+static uint32_t* dc_count_begin(Workspace& w, const CompactReq& q, hipStream_t st, bool shared) {
+  uint32_t* cnt = q.d_n_errs ? q.d_n_errs : w.dc_aux;
+  if ((q.d_n_errs && !q.zero_cnt) || (!q.d_n_errs && w.dc_cnt_dirty) || shared) HIP_OK(hipMemsetAsync(cnt, 0, 4, st));
+  // (shared: the chunks on the request's other workspace add to this word too, unseen by this one)
+  if (!q.d_n_errs) w.dc_cnt_dirty = shared;
+  return cnt;
+}
+
+// *d_n_errs = 0 for an empty device request (no workspace, nothing else to run).
+void device_zero_count(Engine& e, uint32_t* d_n_errs, void* stream) {
+  if (!d_n_errs) return;
+  HIP_OK(hipSetDevice(e.device));
+  HIP_OK(hipMemsetAsync(d_n_errs, 0, 4, (hipStream_t)stream));
+  HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+}
+
+// A device request's chunk expanded to items on the device (submit_compact): the items into the
+// workspace's item array on the batch's stream.
+static void dc_expand(Workspace& w, const CompactReq& q, size_t pos, uint32_t len, hipStream_t st) {
+  DcExpand a{};
+  DcShapes t{};
+  std::memcpy(t.s, q.shapes, (size_t)q.n_shapes * sizeof(gck_uniform));
+  a.ids = q.list() ? (q.ids ? q.ids + pos : nullptr) : q.pairs + 2 * pos;
+  a.shape_of = q.shape_of ? q.shape_of + pos : nullptr;
+  a.items = w.d_items;
+  a.bad = w.dc_aux + 1;
+  a.n = len;
+  a.n_shapes = q.n_shapes;
+  a.vary = q.vary;
+  a.fixed_id = q.fixed_id;
+  a.first_id = q.first_id + (uint32_t)pos;
+  if (a.shape_of) HIP_OK(hipMemsetAsync(w.dc_aux + 1, 0xFF, 4, st));
+  hipLaunchKernelGGL(k_dc_expand, dim3((len + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a, t);
+  HIP_OK(hipGetLastError());
+  // (an engine-stream batch's join may be dispatched into the engine's HSA queue, which does not see
+  // this stream's order: the items are complete before it is)
+  if (st == w.stream) HIP_OK(hipStreamSynchronize(st));
+}
+
+// After a device request's batch has finished (finish_batch): the plane and the error list of its
+// chunk, by kernels on the batch's stream; returns with them written. The host reads nothing but an
+// expanded shaped chunk's bad-index word.
+static void device_collect(Engine& e, Workspace& w) {
+  (void)e;
+  CompactBatch& c = w.cb;
+  const uint32_t n = w.b_n;
+  const uint32_t words = (n + 31u) / 32u;
+  const hipStream_t st = w.b_st;
+  const uint32_t cap = c.errs ? (uint32_t)std::min<size_t>(c.err_cap, 0xFFFFFFFFu) : 0u;
+  bool launched = false;
+  if (c.in_place()) {
+    if (c.ncj) {
+      hipLaunchKernelGGL(k_dc_patch, dim3((c.ncj + kBlock - 1) / kBlock), dim3(kBlock), 0, st, w.c_deferred, c.ncj, n,
+                         w.d_perm, w.d_err, c.packed, w.dc_bitmap);
+      HIP_OK(hipGetLastError());
+      launched = true;
+    }
+  } else {
+    if (c.indexed) {
+      uint32_t bad = 0xFFFFFFFFu;
+      HIP_OK(hipMemcpyAsync(&bad, w.dc_aux + 1, 4, hipMemcpyDeviceToHost, st));
+      HIP_OK(hipStreamSynchronize(st));
+      if (bad != 0xFFFFFFFFu) shape_index_error(c.pos + bad, dc_shape_byte(c, bad), c.n_shapes);
+    }
+    hipLaunchKernelGGL(k_dc_pack, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, w.d_perm, w.d_err, n, c.packed,
+                       w.dc_bitmap);
+    HIP_OK(hipGetLastError());
+    launched = true;
+  }
+  if (launched) {
+    hipLaunchKernelGGL(k_dc_emit, dim3(1), dim3(kBlock), 0, st, w.dc_bitmap, words, w.d_err, (uint32_t)c.pos, c.errs, cap,
+                       c.d_cnt);
+    HIP_OK(hipGetLastError());
+    if (c.d_cnt == w.dc_aux) w.dc_cnt_dirty = true;
+  }
+  // (the count's clear — and the kernels above — are complete when the wait returns; a batch on the
+  // caller's stream that launched nothing is ordered by that stream alone)
+  if (launched || (w.b_own_stream && c.cnt_memset)) HIP_OK(hipStreamSynchronize(st));
+}

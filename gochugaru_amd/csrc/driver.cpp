@@ -26,6 +26,13 @@ using submit_cross_fn = int (*)(gck_engine*, const gck_consistency*, const gck_u
 using submit_list_fn = int (*)(gck_engine*, const gck_consistency*, const gck_uniform*, uint32_t, uint32_t,
                                const uint32_t*, uint32_t, size_t, const char* const*, const size_t*, size_t, int64_t,
                                uint64_t*, gck_item_error*, size_t, size_t*, gck_batch**);
+using submit_uniform_device_fn = int (*)(gck_engine*, const gck_consistency*, const gck_uniform*, const uint32_t*, size_t,
+                                         const char* const*, const size_t*, size_t, int64_t, uint64_t*, gck_item_error*,
+                                         size_t, uint32_t*, uint32_t, void*, gck_batch**);
+using submit_list_device_fn = int (*)(gck_engine*, const gck_consistency*, const gck_uniform*, uint32_t, uint32_t,
+                                      const uint32_t*, uint32_t, size_t, const char* const*, const size_t*, size_t,
+                                      int64_t, uint64_t*, gck_item_error*, size_t, uint32_t*, uint32_t, void*,
+                                      gck_batch**);
 
 // Optional per-batch timeline of the next loops (gckd_set_trace): for batch k, the seconds after
 // the loop's start at which its submit and its wait returned (stamps[2k], stamps[2k + 1]).
@@ -161,6 +168,37 @@ int gckd_run_list(submit_list_fn submit, wait_fn wait, gck_engine* e, const gck_
     return submit(e, cs, hdrs + k, fixed[k], vary, reinterpret_cast<const uint32_t*>(ids[k]), first[k], (size_t)ns[k],
                   nullptr, nullptr, 0, now_us, reinterpret_cast<uint64_t*>(packed[k]),
                   reinterpret_cast<gck_item_error*>(errs[k]), err_cap, n_errs ? n_errs + k : nullptr, b);
+  });
+}
+
+// The uniform loop over device buffers (gck_check_submit_uniform_device): pairs[k], packed[k],
+// errs[k] and n_errs[k] (0: no count word) are device pointers; request k is submitted on
+// streams[k % depth], or with flags = GCK_SUBMIT_ENGINE_STREAM on the engine's workspace streams.
+int gckd_run_uniform_device(submit_uniform_device_fn submit, wait_fn wait, gck_engine* e, const gck_consistency* cs,
+                            size_t n_batches, const gck_uniform* hdrs, const uint64_t* pairs, const uint64_t* ns,
+                            const uint64_t* packed, const uint64_t* errs, size_t err_cap, const uint64_t* n_errs,
+                            uint32_t depth, const uint64_t* streams, uint32_t flags, int64_t now_us, double* seconds) {
+  if (depth == 0) depth = 1;
+  return run_loop(n_batches, depth, wait, e, seconds, [&](size_t k, gck_batch** b) {
+    return submit(e, cs, hdrs + k, reinterpret_cast<const uint32_t*>(pairs[k]), (size_t)ns[k], nullptr, nullptr, 0,
+                  now_us, reinterpret_cast<uint64_t*>(packed[k]), reinterpret_cast<gck_item_error*>(errs[k]), err_cap,
+                  reinterpret_cast<uint32_t*>(n_errs[k]), flags, reinterpret_cast<void*>(streams[k % depth]), b);
+  });
+}
+
+// ... and the list loop (gck_check_submit_list_device): ids[k] is a device id list, or 0 for the
+// range from first[k].
+int gckd_run_list_device(submit_list_device_fn submit, wait_fn wait, gck_engine* e, const gck_consistency* cs,
+                         size_t n_batches, const gck_uniform* hdrs, const uint32_t* fixed, uint32_t vary,
+                         const uint64_t* ids, const uint32_t* first, const uint64_t* ns, const uint64_t* packed,
+                         const uint64_t* errs, size_t err_cap, const uint64_t* n_errs, uint32_t depth,
+                         const uint64_t* streams, uint32_t flags, int64_t now_us, double* seconds) {
+  if (depth == 0) depth = 1;
+  return run_loop(n_batches, depth, wait, e, seconds, [&](size_t k, gck_batch** b) {
+    return submit(e, cs, hdrs + k, fixed[k], vary, reinterpret_cast<const uint32_t*>(ids[k]), first[k], (size_t)ns[k],
+                  nullptr, nullptr, 0, now_us, reinterpret_cast<uint64_t*>(packed[k]),
+                  reinterpret_cast<gck_item_error*>(errs[k]), err_cap, reinterpret_cast<uint32_t*>(n_errs[k]), flags,
+                  reinterpret_cast<void*>(streams[k % depth]), b);
   });
 }
 

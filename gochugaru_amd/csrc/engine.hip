@@ -227,6 +227,13 @@ struct CompactRun {
   // a list request's chunk (CompactReq::list) in place: the join's list word (closure.inc kListOn ...;
   // 0: not a list batch), the fixed id, and — `pairs` is the chunk's id list, or null — its first id
   uint32_t list = 0, fixed_id = 0, first_id = 0;
+  // a request over device buffers (CompactReq::device): pairs / shape_of / packed / errs are device
+  // memory, kExpanded means expanded to items on the device, and the wait finishes the chunk by
+  // kernels (device_compact.inc device_collect). d_cnt: the device word the request counts its errors in
+  bool device = false;
+  uint32_t* d_cnt = nullptr;
+  bool zero_cnt = false;  // ... which this batch still has to clear (the join's block 0 does: dc_steal_clear; else a memset)
+  bool cnt_memset = false;  // ... cleared by a memset on the batch's stream
   bool in_place() const { return mode == kInPlace; }
   bool table_join() const { return mode == kInPlace && indexed; }  // the join reads index bytes and a shape table
 };
@@ -277,6 +284,11 @@ struct Workspace {
   uint32_t ws_index = 0;      // the workspace's place in the pool (its resident-join slot)
   uint32_t res_seq = 0;       // resident-join requests posted from it
   CompactBatch cb;            // the batch is a compact request's chunk (submit_compact)
+  uint32_t* dc_bitmap = nullptr;  // device_compact.inc: one error bit per check of a device request's chunk (zero between batches)
+  uint32_t* dc_aux = nullptr;     // ... [0] the errors so far of a request that gives no count word, [1] an expanded chunk's bad index
+  bool dc_cnt_dirty = false;      // ... dc_aux[0] may be non-zero
+  uint32_t pair_dirty = 0;        // one of the two alternating deferred-list counters (aql_summaries) may be non-zero:
+                                  // the next so many dispatched joins must clear the other one themselves
   void* aql_shapes = nullptr;   // aql.inc: the shape table the join reads (GCK_MAX_SHAPES entries, memory as aql_kernarg)
   alignas(16) unsigned char shapes_shadow[GCK_MAX_SHAPES * sizeof(gck_uniform)] = {};  // ... what it holds now
   void* aql_ids = nullptr;      // aql.inc: the id block a cross batch's join reads (behind the shape table)
@@ -2067,6 +2079,10 @@ static Workspace* create_workspace(Engine& e) {
     w->d_perm = dalloc<uint8_t>(w->allocs, w->max_batch, &w->bytes);
     w->d_err = dalloc<int32_t>(w->allocs, w->max_batch, &w->bytes);
     w->cav_flag = dalloc<uint8_t>(w->allocs, w->max_batch, &w->bytes);
+    w->dc_bitmap = dalloc<uint32_t>(w->allocs, w->max_batch / 32 + 1, &w->bytes);
+    w->dc_aux = dalloc<uint32_t>(w->allocs, 2, &w->bytes);
+    HIP_OK(hipMemsetAsync(w->dc_bitmap, 0, (w->max_batch / 32 + 1) * sizeof(uint32_t), nullptr));
+    HIP_OK(hipMemsetAsync(w->dc_aux, 0, 2 * sizeof(uint32_t), nullptr));
     w->d_ctx = reinterpret_cast<Ctx*>(dalloc<unsigned char>(w->allocs, sizeof(Ctx), &w->bytes));
     HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&w->h_ctx), sizeof(Ctx), hipHostMallocDefault));
     HIP_OK(hipHostMalloc(&w->h_ctr, sizeof(DevCounters) + (kBCtrs + 4) * sizeof(unsigned),
@@ -2461,6 +2477,7 @@ constexpr uint32_t kPubWords = (sizeof(DevCounters) + kBCtrs * sizeof(unsigned))
 
 static void publish_launch(Workspace& w, hipStream_t st) {
   const unsigned seq = ++w.pub_seq;
+  w.pair_dirty = 0;  // (k_publish zeroes every counter)
   hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, reinterpret_cast<unsigned*>(w.ctr), kPubWords, w.d_hpub,
                      w.d_hpub + kPubWords, seq);
   HIP_OK(hipGetLastError());
@@ -2587,6 +2604,21 @@ static void aql_summaries(Workspace& w, uint32_t& coherent, unsigned*& h_out, un
   w.b_sum_blocks = blocks;
 }
 
+// A submitted device request's count word (CompactRun::zero_cnt) cleared by the dispatched join
+// itself: block 0 of a join that reports through summaries stores 0 to `clear` — the counter the
+// next batch will use — and that counter is zero already unless a join on this workspace left
+// checks since the last publication zeroed the counters (Workspace::pair_dirty). Then the store
+// goes to the caller's word instead, and the batch needs no memset and no stream wait.
+static void dc_steal_clear(const Engine& e, Workspace& w, uint32_t mode, unsigned*& clear) {
+  if (!(mode & kPubBySignal)) return;
+  if (w.cb.zero_cnt && !e.res && w.pair_dirty == 0) {
+    clear = w.cb.d_cnt;
+    w.cb.zero_cnt = false;
+  } else if (w.pair_dirty) {
+    --w.pair_dirty;
+  }
+}
+
 // After the completion signal: the batch's counters from its blocks' summaries into the host copy
 // the rest of the engine reads (*h_ctr, h_bctrs[4]); the device counters only when a block touched
 // them (task rounds, probes, a bad context slot), read and cleared synchronously.
@@ -2606,6 +2638,7 @@ static void aql_collect(Workspace& w) {
     HIP_OK(hipMemset(w.ctr, 0, sizeof(DevCounters)));
   }
   w.h_bctrs[4] = deferred;
+  if (deferred) w.pair_dirty = 2;  // (until a publication zeroes the counters, or two joins have cleared one each)
 }
 
 // A uniform batch's join arguments (closure.inc CjArgs::pairs; labels.inc LjArgs): the pairs and
@@ -2794,6 +2827,7 @@ static void label_join_start(Engine& e, Workspace& w, const Route& r, const Ctx&
   }
   if (ak) {
     if (j.h_out) aql_summaries(w, j.coherent, j.h_out, j.done, j.n_deferred, lj_blocks(n));
+    if (j.h_out) dc_steal_clear(e, w, j.coherent, j.done);
     aql_after_build(e);
     aql_dispatch(*e.aql, w, *ak, &j, sizeof(j), lj_blocks(n), r.timed, cav ? &c : nullptr, cav ? sizeof(Ctx) : 0);
     w.b_aql = true;
@@ -2850,6 +2884,7 @@ static void closure_join_start(Engine& e, Workspace& w, const Route& r, const Ct
     throw Error(GCK_E_DEVICE, "engine invariant violated: kernarg block alignment");
   if (ak && j.h_out)
     aql_summaries(w, cj_args.j.mode, cj_args.j.h_out, cj_args.j.done, cj_args.j.n_deferred, grid.x);
+  if (ak && j.h_out) dc_steal_clear(e, w, cj_args.j.mode, cj_args.j.done);
   // the resident join (resident.inc) takes the request without a dispatch of its own
   // (a shaped batch is dispatched: the running launch would read the workspace's shape table, which
   // the host rewrites between requests, without a dispatch's acquire in between; a cross batch
@@ -2888,7 +2923,10 @@ static void bundles_launch(Engine& e, Workspace& w) {
   BundleArgs a = bundle_args(e, w, w.b_items, n, w.b_dperm, w.b_derr);
   const Route r = stage_a_route(e, w);
   if (a.timing) HIP_OK(hipMemsetAsync(w.timing, 0, w.timing_cap * 8, st));  // (GCK_DEBUG_TIMING)
-  if (!w.ctr_clean) HIP_OK(hipMemsetAsync(w.ctr, 0, sizeof(DevCounters) + kBCtrs * sizeof(unsigned), st));  // + b_ctrs
+  if (!w.ctr_clean) {
+    HIP_OK(hipMemsetAsync(w.ctr, 0, sizeof(DevCounters) + kBCtrs * sizeof(unsigned), st));  // + b_ctrs
+    w.pair_dirty = 0;
+  }
   w.ctr_clean = false;
   // the checks' caveat flags start cleared: by the label join with the caveat plane itself (an AQL
   // dispatch is not ordered after this stream's work), else here
@@ -2935,6 +2973,15 @@ static void bundles_launch(Engine& e, Workspace& w) {
 
 static void debug_dump(Engine& e, Workspace& w, uint32_t n);
 
+// Index byte i of a shaped chunk, for the message of a bad one: the caller's buffer, read from the
+// device when the request's buffers are device memory.
+static uint32_t dc_shape_byte(const CompactRun& c, uint32_t i) {
+  if (!c.device) return c.shape_of[i];
+  uint8_t b = 0;
+  HIP_OK(hipMemcpy(&b, c.shape_of + i, 1, hipMemcpyDeviceToHost));
+  return b;
+}
+
 constexpr uint32_t kChainLeftovers = 1;  // leftovers of a batch that make the next 16 chain their bundles
 
 // Stages B and C of a bundle batch after stage A was published: the checks stage A deferred
@@ -2956,7 +3003,7 @@ static float bundles_finish(Engine& e, Workspace& w) {
   if (w.h_ctr->bad_slot) {  // (a zero-copy batch's join found a context slot out of range)
     const uint32_t i = 0xFFFFFFFFu - w.h_ctr->bad_slot;
     // (a shaped batch's table was checked by the host: the join reports an index byte beyond it)
-    if (w.cb.table_join()) shape_index_error(w.cb.pos + i, i < n ? w.cb.shape_of[i] : 0u, w.cb.n_shapes);
+    if (w.cb.table_join()) shape_index_error(w.cb.pos + i, i < n ? dc_shape_byte(w.cb, i) : 0u, w.cb.n_shapes);
     slot_error(i, i < n ? d_items[i].context_slot : 0u, w.cav.n_given);
   }
   const bool profile = w.b_timed;
@@ -3665,6 +3712,8 @@ static void compact_stage(Engine& e, Workspace& w, const uint32_t* pairs, size_t
   c.packed = host_pinned(e, c.out, words * 8u) ? c.out : reinterpret_cast<unsigned long long*>(w.h_err);
 }
 
+#include "device_compact.inc"
+
 // A cross request's tile when it runs in place on the workspaces given (w1 may be null): the
 // in-place condition of a uniform chunk, the workspace's id block, and a tile from the tiling rule.
 static bool cross_plan(const Engine& e, const Workspace* w0, const Workspace* w1, const CavCall& cav, CompactReq& q) {
@@ -3683,8 +3732,12 @@ static size_t cross_tiles(const CompactReq& q) {
 
 // Queues the chunk [pos, pos + len) of the request on w (pos: a multiple of 32); of a cross request
 // in place (q.tile_rows != 0): its tile number pos, left to right and top to bottom.
-static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t pos, uint32_t len, int64_t now_us) {
+static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t pos, uint32_t len, int64_t now_us,
+                           uint32_t* d_cnt = nullptr) {
   CompactRun c;
+  c.device = q.device;
+  c.d_cnt = d_cnt;
+  c.zero_cnt = q.device && q.zero_cnt;
   c.indexed = q.shape_of != nullptr;
   c.n_shapes = q.n_shapes;
   c.pos = pos;
@@ -3726,18 +3779,36 @@ static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t 
   // shaped chunk also needs the workspace's table block (a cross request's: cross_plan, above)
   if (!c.cross && zero_copy_ok(e, w) && (!c.indexed || w.aql_shapes)) {
     c.mode = CompactRun::kInPlace;
+    if (q.device) {
+      // device buffers: the join reads and writes them where they are, on the workspace's stream or
+      // — a submit on the caller's stream — on that one, through a HIP launch
+      c.pairs = q.list() ? (q.ids ? q.ids + pos : nullptr) : q.pairs + 2 * pos;
+      c.shape_of = c.indexed ? q.shape_of + pos : nullptr;
+      c.packed = c.out;
+    }
     if (q.list()) {
       // a list chunk: its ids, 4 B per check; a range's chunk has none, only its own first id
-      compact_stage(e, w, q.ids ? q.ids + pos : nullptr, 4u, nullptr, len, c);
+      if (!q.device) compact_stage(e, w, q.ids ? q.ids + pos : nullptr, 4u, nullptr, len, c);
       c.list = kListOn | (q.vary == GCK_VARY_SUBJECT ? kListSubject : 0u) | (q.ids ? 0u : kListRange);
       c.fixed_id = q.fixed_id;
       c.first_id = q.ids ? 0u : q.first_id + (uint32_t)pos;
-    } else {
+    } else if (!q.device) {
       compact_stage(e, w, q.pairs + 2 * pos, 8u, c.indexed ? q.shape_of + pos : nullptr, len, c);
     }
     if (c.indexed) aql_put_shapes(*e.aql, w, q.shapes, q.n_shapes);
     else header();
-    submit_batch(e, w, w.d_items, len, now_us, w.d_perm, w.d_err, w.stream, BatchMem::kEngineStream, c);
+    const bool own = !q.device || q.engine_stream;
+    submit_batch(e, w, w.d_items, len, now_us, w.d_perm, w.d_err, own ? w.stream : (hipStream_t)q.stream,
+                 own ? BatchMem::kEngineStream : BatchMem::kCallerStream, c);
+  } else if (q.device) {
+    // expanded on the device: the chunk's items into the workspace's item array, then a device batch
+    c.mode = CompactRun::kExpanded;
+    c.packed = c.out;
+    c.shape_of = c.indexed ? q.shape_of + pos : nullptr;  // (read for the message of a bad index only)
+    const hipStream_t st = q.engine_stream ? w.stream : (hipStream_t)q.stream;
+    dc_expand(w, q, pos, len, st);
+    submit_batch(e, w, w.d_items, len, now_us, w.d_perm, w.d_err, st,
+                 q.engine_stream ? BatchMem::kEngineStream : BatchMem::kCallerStream, c);
   } else {
     c.mode = CompactRun::kExpanded;
     w.cb.items.resize(len);
@@ -3745,6 +3816,10 @@ static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t 
     w.cb.perm.resize(len);
     w.cb.err.resize(len);
     submit_batch(e, w, w.cb.items.data(), len, now_us, w.cb.perm.data(), w.cb.err.data(), nullptr, BatchMem::kHost, c);
+  }
+  if (q.device) {  // (gck_device_compact_stats; the host requests' counts below leave device requests out)
+    (c.in_place() ? e.dev_in_place : e.dev_expanded).fetch_add(1, std::memory_order_relaxed);
+    return;
   }
   // (gck_shaped_stats counts shaped chunks only, one count per chunk)
   if (c.indexed) (c.in_place() ? e.shaped_in_place : e.shaped_expanded).fetch_add(1, std::memory_order_relaxed);
@@ -3843,9 +3918,16 @@ void device_submit_compact(Engine& e, Workspace* w, const CompactReq& req, int64
   // (a submitted cross request is one tile by the tiling rule — checked by the entry point — so
   // in place it is tile 0 and expanded it is one chunk: S * R <= its padded size <= max_batch)
   if (q.cross()) cross_plan(e, w, nullptr, cav, q);
-  stage_caveats(*w, std::move(cav), w->stream);
+  const hipStream_t st = (q.device && !q.engine_stream) ? (hipStream_t)q.stream : w->stream;
+  q.zero_cnt = q.device && q.d_n_errs;  // (cleared by the batch: its dispatched join, or the memset below)
+  stage_caveats(*w, std::move(cav), st);
   if (now_us == 0) now_us = wall_now_us();
-  submit_compact(e, *w, q, 0, (uint32_t)q.n, now_us);
+  submit_compact(e, *w, q, 0, (uint32_t)q.n, now_us, q.device ? dc_count_begin(*w, q, st, false) : nullptr);
+  if (w->cb.zero_cnt) {  // (no dispatched join took the clear of the caller's count word)
+    HIP_OK(hipMemsetAsync(w->cb.d_cnt, 0, 4, st));
+    w->cb.zero_cnt = false;
+    w->cb.cnt_memset = true;
+  }
 }
 
 // The chunks of a request that is no cross request: max_batch checks each, rounded down to a multiple
@@ -3857,10 +3939,22 @@ static size_t compact_chunks(Engine& e, Workspace* w0, Workspace* w1, const Comp
   if (req.n > mb && mb % 32 != 0)
     throw Error(GCK_E_CAPACITY, req.shape_of ? "a shaped request above max_batch needs max_batch >= 32"
                                              : "a uniform request above max_batch needs max_batch >= 32");
+  uint32_t* d_cnt = nullptr;
+  if (req.device) {
+    // a synchronous device request runs on the workspaces' streams: what the caller's stream holds
+    // completes first, and so does the clear of the count the chunks' lists accumulate in
+    HIP_OK(hipStreamSynchronize((hipStream_t)req.stream));
+    d_cnt = dc_count_begin(*w0, req, w0->stream, true);
+    HIP_OK(hipStreamSynchronize(w0->stream));
+  }
   run_chunks(
       e, w0, w1, req.n, mb, cav,
-      [&](Workspace& w, size_t pos, uint32_t len) { submit_compact(e, w, req, pos, len, now_us); },
-      [&](Workspace& w) { uniform_collect(w, errs); });
+      [&](Workspace& w, size_t pos, uint32_t len) { submit_compact(e, w, req, pos, len, now_us, d_cnt); },
+      [&](Workspace& w) {
+        // (chunks complete in request order, each list written before the next is begun: ascending)
+        if (req.device) device_collect(e, w);
+        else uniform_collect(w, errs);
+      });
   return mb;
 }
 
@@ -3884,7 +3978,7 @@ void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const Compact
   }
   std::vector<gck_item_error> errs;
   compact_chunks(e, w0, w1, req, now_us, cav, errs);
-  uniform_errors(errs, req.errs, req.err_cap, req.n_errs);
+  if (!req.device) uniform_errors(errs, req.errs, req.err_cap, req.n_errs);
 }
 
 // Completes a submitted batch. Takes no engine lock: a writer that wants to replace the
@@ -3900,7 +3994,9 @@ void device_wait(Engine& e, Workspace* w) {
   finish_batch(e, *w);  // no-op when a writer already finished it (drain_batches)
   if (w->fail_code) throw Error(w->fail_code, w->fail_msg);
   copy_out(*w);
-  if (w->cb.mode != CompactRun::kOff) {
+  if (w->cb.device) {
+    device_collect(e, *w);
+  } else if (w->cb.mode != CompactRun::kOff) {
     std::vector<gck_item_error> errs;
     uniform_collect(*w, errs);
     uniform_errors(errs, w->cb.errs, w->cb.err_cap, w->cb.n_errs);

@@ -281,6 +281,7 @@ struct Engine {
   std::atomic<uint64_t> cross_in_place{0}, cross_expanded{0};
   // gck_list_stats: list chunks whose join read the ids in place / chunks expanded to items
   std::atomic<uint64_t> list_in_place{0}, list_expanded{0};
+  std::atomic<uint64_t> dev_in_place{0}, dev_expanded{0};  // gck_device_compact_stats
   // batches to come that chain the wave bundles behind the join in stage A (engine.hip
   // bundles_launch): reset to 16 by a batch whose join left kChainLeftovers or more, counted down by
   // one that left fewer
@@ -437,7 +438,18 @@ struct CompactReq {
   uint32_t fixed_id = 0, first_id = 0;
   const uint32_t* ids = nullptr;
   bool list() const { return vary != 0; }
+  // a request over device buffers (gck_check_bulk_uniform_device ...; never a cross request):
+  // shape_of, pairs, ids, packed and errs are device memory, n_errs is null and the count goes to
+  // *d_n_errs (device memory; may be null). The synchronous form completes `stream` and runs on the
+  // workspaces' streams; a submitted batch runs on the workspace's stream (engine_stream) or on `stream`
+  bool device = false;
+  bool engine_stream = true;
+  void* stream = nullptr;
+  uint32_t* d_n_errs = nullptr;
+  bool zero_cnt = false;  // set by the engine: a submitted batch clears *d_n_errs itself (engine.hip dc_steal_clear)
 };
+// *d_n_errs = 0 for an empty device request (synchronous on `stream`; a null pointer: nothing).
+void device_zero_count(Engine& e, uint32_t* d_n_errs, void* stream);
 // Synchronous: chunks of max_batch & ~31 checks over w0 and w1 (as device_check_host); a cross
 // request in place: its tiles, one batch each.
 void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const CompactReq& req, int64_t now_us,

@@ -1342,6 +1342,167 @@ int gck_list_stats(gck_engine* ge, uint64_t out[2]) {
   });
 }
 
+// ---- compact requests over device buffers (include/gck.h gck_check_bulk_uniform_device) ------
+
+// What the device forms check beyond their host forms, before anything is launched, and the request
+// as the engine takes it: `q` is the host form's request built over the device pointers (its checks
+// have passed; none of them reads a buffer).
+static CompactReq device_request(CompactReq q, const void* d_errs, uint32_t* d_n_errs, void* stream,
+                                 bool engine_stream) {
+  const auto aligned = [](const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+  REQUIRE(q.n < 0x100000000ull, GCK_E_INVALID_ARGUMENT, "device request: " + std::to_string(q.n) + " checks reach 2^32");
+  REQUIRE(aligned(q.pairs, 8), GCK_E_INVALID_ARGUMENT, "device request: d_pairs is not 8-byte aligned");
+  REQUIRE(aligned(q.packed, 8), GCK_E_INVALID_ARGUMENT, "device request: d_out_packed is not 8-byte aligned");
+  REQUIRE(aligned(q.ids, 4), GCK_E_INVALID_ARGUMENT, "device request: d_ids is not 4-byte aligned");
+  REQUIRE(aligned(d_errs, 4), GCK_E_INVALID_ARGUMENT, "device request: d_out_errs is not 4-byte aligned");
+  REQUIRE(aligned(d_n_errs, 4), GCK_E_INVALID_ARGUMENT, "device request: d_out_n_errs is not 4-byte aligned");
+  q.device = true;
+  q.engine_stream = engine_stream;
+  q.stream = stream;
+  q.d_n_errs = d_n_errs;
+  return q;
+}
+
+// A synchronous device request after its argument checks: an empty one clears the count and takes
+// no workspace.
+static void check_device_sync(Engine& e, const CallCtx& c, const CompactReq& req, int64_t now_us,
+                              uint64_t* out_revision) {
+  if (req.n == 0) {
+    std::shared_lock<std::shared_mutex> lk(e.mu);
+    check_request(e, c.cs, c.contexts, c.context_lens, c.n_contexts);
+    device_zero_count(e, req.d_n_errs, req.stream);
+    if (out_revision) *out_revision = e.revision;
+    return;
+  }
+  check_compact_sync(e, c, req, now_us, out_revision);
+}
+
+// ... and a submitted one (flags: GCK_SUBMIT_ENGINE_STREAM or the caller's stream; GCK_SUBMIT_DEVICE is implied).
+static gck_batch* submit_device(Engine& e, const CallCtx& c, const CompactReq& req, int64_t now_us) {
+  gck_batch* b = submit_with(e, c, req.n, [&](Workspace* w, CavCall cav) {
+    device_submit_compact(e, w, req, now_us, std::move(cav));
+  });
+  if (req.n == 0) {
+    try {
+      device_zero_count(e, req.d_n_errs, req.engine_stream ? nullptr : req.stream);
+    } catch (...) {
+      delete b;
+      throw;
+    }
+  }
+  return b;
+}
+
+static void check_submit_flags(uint32_t flags) {
+  REQUIRE(!(flags & ~(GCK_SUBMIT_DEVICE | GCK_SUBMIT_ENGINE_STREAM)), GCK_E_INVALID_ARGUMENT, "unknown submit flags");
+}
+
+int gck_check_bulk_uniform_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr,
+                                  const uint32_t* d_pairs, size_t n, const char* const* contexts,
+                                  const size_t* context_lens, size_t n_contexts, int64_t now_us, uint64_t* d_out_packed,
+                                  gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, void* stream,
+                                  uint64_t* out_revision) {
+  return guard([&] {
+    Engine& e = need(ge);
+    check_uniform(hdr, n_contexts);
+    const CompactReq req =
+        device_request(compact_request(hdr, 1, false, nullptr, d_pairs, n, d_out_packed, d_out_errs, err_cap, nullptr),
+                       d_out_errs, d_out_n_errs, stream, true);
+    check_device_sync(e, {cs, contexts, context_lens, n_contexts}, req, now_us, out_revision);
+  });
+}
+
+int gck_check_submit_uniform_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr,
+                                    const uint32_t* d_pairs, size_t n, const char* const* contexts,
+                                    const size_t* context_lens, size_t n_contexts, int64_t now_us,
+                                    uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                    uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    check_submit_flags(flags);
+    check_uniform(hdr, n_contexts);
+    const CompactReq req =
+        device_request(compact_request(hdr, 1, false, nullptr, d_pairs, n, d_out_packed, d_out_errs, err_cap, nullptr),
+                       d_out_errs, d_out_n_errs, stream, (flags & GCK_SUBMIT_ENGINE_STREAM) != 0);
+    *out = submit_device(e, {cs, contexts, context_lens, n_contexts}, req, now_us);
+  });
+}
+
+int gck_check_bulk_shaped_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* shapes, size_t n_shapes,
+                                 const uint8_t* d_shape_of, const uint32_t* d_pairs, size_t n,
+                                 const char* const* contexts, const size_t* context_lens, size_t n_contexts,
+                                 int64_t now_us, uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                 uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision) {
+  return guard([&] {
+    Engine& e = need(ge);
+    check_shapes(shapes, n_shapes, n_contexts);
+    const CompactReq req = device_request(
+        compact_request(shapes, n_shapes, true, d_shape_of, d_pairs, n, d_out_packed, d_out_errs, err_cap, nullptr),
+        d_out_errs, d_out_n_errs, stream, true);
+    check_device_sync(e, {cs, contexts, context_lens, n_contexts}, req, now_us, out_revision);
+  });
+}
+
+int gck_check_submit_shaped_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* shapes,
+                                   size_t n_shapes, const uint8_t* d_shape_of, const uint32_t* d_pairs, size_t n,
+                                   const char* const* contexts, const size_t* context_lens, size_t n_contexts,
+                                   int64_t now_us, uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                   uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    check_submit_flags(flags);
+    check_shapes(shapes, n_shapes, n_contexts);
+    const CompactReq req = device_request(
+        compact_request(shapes, n_shapes, true, d_shape_of, d_pairs, n, d_out_packed, d_out_errs, err_cap, nullptr),
+        d_out_errs, d_out_n_errs, stream, (flags & GCK_SUBMIT_ENGINE_STREAM) != 0);
+    *out = submit_device(e, {cs, contexts, context_lens, n_contexts}, req, now_us);
+  });
+}
+
+int gck_check_bulk_list_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                               uint32_t vary, const uint32_t* d_ids, uint32_t first_id, size_t n,
+                               const char* const* contexts, const size_t* context_lens, size_t n_contexts,
+                               int64_t now_us, uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                               uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision) {
+  return guard([&] {
+    Engine& e = need(ge);
+    const CompactReq req = device_request(
+        list_request(hdr, fixed_id, vary, d_ids, first_id, n, n_contexts, d_out_packed, d_out_errs, err_cap, nullptr),
+        d_out_errs, d_out_n_errs, stream, true);
+    check_device_sync(e, {cs, contexts, context_lens, n_contexts}, req, now_us, out_revision);
+  });
+}
+
+int gck_check_submit_list_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                                 uint32_t vary, const uint32_t* d_ids, uint32_t first_id, size_t n,
+                                 const char* const* contexts, const size_t* context_lens, size_t n_contexts,
+                                 int64_t now_us, uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                 uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    check_submit_flags(flags);
+    const CompactReq req = device_request(
+        list_request(hdr, fixed_id, vary, d_ids, first_id, n, n_contexts, d_out_packed, d_out_errs, err_cap, nullptr),
+        d_out_errs, d_out_n_errs, stream, (flags & GCK_SUBMIT_ENGINE_STREAM) != 0);
+    *out = submit_device(e, {cs, contexts, context_lens, n_contexts}, req, now_us);
+  });
+}
+
+int gck_device_compact_stats(gck_engine* ge, uint64_t out[2]) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    out[0] = e.dev_in_place.load(std::memory_order_relaxed);
+    out[1] = e.dev_expanded.load(std::memory_order_relaxed);
+  });
+}
+
 int gck_host_alloc(gck_engine* ge, size_t bytes, void** out) {
   return guard([&] {
     Engine& e = need(ge);

@@ -307,6 +307,27 @@ _SIGS = {
                                         C.c_size_t, C.c_int64, _P, _P, C.c_size_t, C.POINTER(C.c_size_t),
                                         C.POINTER(_P)]),
     "gck_list_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "gck_check_bulk_uniform_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), _P, C.c_size_t,
+                                                C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int64,
+                                                _P, _P, C.c_size_t, _P, _P, C.POINTER(C.c_uint64)]),
+    "gck_check_bulk_shaped_device": (C.c_int, [_P, C.POINTER(_Consistency), _P, C.c_size_t, _P, _P, C.c_size_t,
+                                               C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int64,
+                                               _P, _P, C.c_size_t, _P, _P, C.POINTER(C.c_uint64)]),
+    "gck_check_bulk_list_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), C.c_uint32, C.c_uint32,
+                                             _P, C.c_uint32, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                             C.c_size_t, C.c_int64, _P, _P, C.c_size_t, _P, _P,
+                                             C.POINTER(C.c_uint64)]),
+    "gck_check_submit_uniform_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), _P, C.c_size_t,
+                                                  C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int64,
+                                                  _P, _P, C.c_size_t, _P, C.c_uint32, _P, C.POINTER(_P)]),
+    "gck_check_submit_shaped_device": (C.c_int, [_P, C.POINTER(_Consistency), _P, C.c_size_t, _P, _P, C.c_size_t,
+                                                 C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int64,
+                                                 _P, _P, C.c_size_t, _P, C.c_uint32, _P, C.POINTER(_P)]),
+    "gck_check_submit_list_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), C.c_uint32,
+                                               C.c_uint32, _P, C.c_uint32, C.c_size_t, C.POINTER(C.c_char_p),
+                                               C.POINTER(C.c_size_t), C.c_size_t, C.c_int64, _P, _P, C.c_size_t, _P,
+                                               C.c_uint32, _P, C.POINTER(_P)]),
+    "gck_device_compact_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "gck_lookup_resources_among": (C.c_int, [_P, C.POINTER(_Consistency), C.c_uint16, C.c_uint16, C.c_uint16,
                                              C.c_uint16, C.c_uint32, _P, C.c_size_t, C.c_int64, _P, _P, C.c_size_t,
                                              C.POINTER(C.c_size_t)]),
@@ -420,6 +441,15 @@ def _driver():
         d.gckd_run_list.argtypes = [C.c_void_p, C.c_void_p, _P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                     C.c_void_p, C.c_uint32, C.c_int64, C.POINTER(C.c_double)]
+        d.gckd_run_uniform_device.restype = C.c_int
+        d.gckd_run_uniform_device.argtypes = [C.c_void_p, C.c_void_p, _P, C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.c_uint32, C.c_void_p, C.c_uint32, C.c_int64, C.POINTER(C.c_double)]
+        d.gckd_run_list_device.restype = C.c_int
+        d.gckd_run_list_device.argtypes = [C.c_void_p, C.c_void_p, _P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int64,
+                                           C.POINTER(C.c_double)]
         d.gckd_set_trace.restype = None
         d.gckd_set_trace.argtypes = [C.c_void_p, C.c_size_t]
         _DRIVER = d
@@ -974,6 +1004,129 @@ class Engine:
         _check(self._lib.gck_list_stats(self._h, out))
         return int(out[0]), int(out[1])
 
+    # ---- compact requests over device buffers (gck_check_bulk_uniform_device ...) ------------
+    # Device buffers are integer addresses on the engine's device (torch: tensor.data_ptr()):
+    # d_pairs (n, 2) u32, d_shape_of u8, d_ids u32, d_out_packed ceil(n / 32) u64, d_out_errs err_cap
+    # ITEM_ERROR_DTYPE records, d_out_n_errs one u32 (0 / None: no count). `stream` as
+    # check_bulk_device's. The synchronous forms return the evaluated revision.
+    def _device_tail(self, requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap, d_out_n_errs):
+        cs = _Consistency(requirement, 0, revision)
+        ctx_arr, ctx_lens, n_ctx = _context_arrays(contexts)
+        return cs, (ctx_arr, ctx_lens, n_ctx, now_us, d_out_packed or None, d_out_errs or None, err_cap,
+                    d_out_n_errs or None)
+
+    def check_uniform_device(self, header, d_pairs: int, n: int, d_out_packed: int, d_out_errs: int = 0,
+                             err_cap: int = 0, d_out_n_errs: int = 0, stream: Optional[int] = None,
+                             requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                             contexts: Optional[Sequence] = None) -> int:
+        """gck_check_bulk_uniform_device: check_uniform over device buffers; results on the device."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        rev = C.c_uint64(0)
+        _check(self._lib.gck_check_bulk_uniform_device(self._h, C.byref(cs), C.byref(hdr), d_pairs or None, n, *tail,
+                                                       stream, C.byref(rev)))
+        return rev.value
+
+    def check_shaped_device(self, shapes, d_shape_of: int, d_pairs: int, n: int, d_out_packed: int,
+                            d_out_errs: int = 0, err_cap: int = 0, d_out_n_errs: int = 0,
+                            stream: Optional[int] = None, requirement: int = CONSISTENCY_MIN_LATENCY,
+                            revision: int = 0, now_us: int = 0, contexts: Optional[Sequence] = None) -> int:
+        """gck_check_bulk_shaped_device: check_shaped over device buffers (the table is host memory)."""
+        table, n_shapes = _shape_table(shapes)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        rev = C.c_uint64(0)
+        _check(self._lib.gck_check_bulk_shaped_device(self._h, C.byref(cs), C.addressof(table), n_shapes,
+                                                      d_shape_of or None, d_pairs or None, n, *tail, stream,
+                                                      C.byref(rev)))
+        return rev.value
+
+    def check_list_device(self, header, fixed_id: int, vary: int, n: int, d_out_packed: int, d_ids: int = 0,
+                          first_id: int = 0, d_out_errs: int = 0, err_cap: int = 0, d_out_n_errs: int = 0,
+                          stream: Optional[int] = None, requirement: int = CONSISTENCY_MIN_LATENCY,
+                          revision: int = 0, now_us: int = 0, contexts: Optional[Sequence] = None) -> int:
+        """gck_check_bulk_list_device: check_list over a device id list, or (d_ids = 0) the range
+        first_id .. first_id + n - 1."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        rev = C.c_uint64(0)
+        _check(self._lib.gck_check_bulk_list_device(self._h, C.byref(cs), C.byref(hdr), fixed_id, vary, d_ids or None,
+                                                    first_id, n, *tail, stream, C.byref(rev)))
+        return rev.value
+
+    def submit_uniform_device(self, header, d_pairs: int, n: int, d_out_packed: int, d_out_errs: int = 0,
+                              err_cap: int = 0, d_out_n_errs: int = 0, stream: Optional[int] = None,
+                              engine_stream: bool = False, requirement: int = CONSISTENCY_MIN_LATENCY,
+                              revision: int = 0, now_us: int = 0,
+                              contexts: Optional[Sequence] = None) -> "DeviceCompactBatch":
+        """gck_check_submit_uniform_device (n <= max_batch): on `stream`, or with engine_stream on the
+        stream of the workspace the batch holds; wait() completes it and returns its revision."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        b = DeviceCompactBatch(self, hdr)
+        _check(self._lib.gck_check_submit_uniform_device(self._h, C.byref(cs), C.byref(hdr), d_pairs or None, n, *tail,
+                                                         SUBMIT_ENGINE_STREAM if engine_stream else 0, stream,
+                                                         C.byref(b._h)))
+        return b
+
+    def submit_shaped_device(self, shapes, d_shape_of: int, d_pairs: int, n: int, d_out_packed: int,
+                             d_out_errs: int = 0, err_cap: int = 0, d_out_n_errs: int = 0,
+                             stream: Optional[int] = None, engine_stream: bool = False,
+                             requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                             contexts: Optional[Sequence] = None) -> "DeviceCompactBatch":
+        """gck_check_submit_shaped_device: as submit_uniform_device."""
+        table, n_shapes = _shape_table(shapes)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        b = DeviceCompactBatch(self, table)
+        _check(self._lib.gck_check_submit_shaped_device(self._h, C.byref(cs), C.addressof(table), n_shapes,
+                                                        d_shape_of or None, d_pairs or None, n, *tail,
+                                                        SUBMIT_ENGINE_STREAM if engine_stream else 0, stream,
+                                                        C.byref(b._h)))
+        return b
+
+    def submit_list_device(self, header, fixed_id: int, vary: int, n: int, d_out_packed: int, d_ids: int = 0,
+                           first_id: int = 0, d_out_errs: int = 0, err_cap: int = 0, d_out_n_errs: int = 0,
+                           stream: Optional[int] = None, engine_stream: bool = False,
+                           requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                           contexts: Optional[Sequence] = None) -> "DeviceCompactBatch":
+        """gck_check_submit_list_device: as submit_uniform_device."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        b = DeviceCompactBatch(self, hdr)
+        _check(self._lib.gck_check_submit_list_device(self._h, C.byref(cs), C.byref(hdr), fixed_id, vary, d_ids or None,
+                                                      first_id, n, *tail, SUBMIT_ENGINE_STREAM if engine_stream else 0,
+                                                      stream, C.byref(b._h)))
+        return b
+
+    def prepare_uniform_device(self, headers, pairs, ns, packed, errs, err_cap: int, depth: int, n_errs=None,
+                               streams=None, engine_streams: bool = True,
+                               now_us: int = 0) -> "PreparedUniformDevice":
+        """The compiled submit/wait loop over uniform device requests (libgck_driver.so
+        gckd_run_uniform_device): as prepare_uniform with device pointers; n_errs[k] is request k's
+        device count word (None: none), batch k on streams[k % depth] or the engine's streams."""
+        return PreparedUniformDevice(self, headers, pairs, ns, packed, errs, err_cap, depth, n_errs, streams,
+                                     engine_streams, now_us)
+
+    def prepare_list_device(self, headers, fixed, vary: int, ids, first, ns, packed, errs, err_cap: int, depth: int,
+                            n_errs=None, streams=None, engine_streams: bool = True,
+                            now_us: int = 0) -> "PreparedListDevice":
+        """The compiled loop over list device requests (gckd_run_list_device): as prepare_list with
+        device pointers (ids[k] == 0: the range from first[k])."""
+        return PreparedListDevice(self, headers, fixed, vary, ids, first, ns, packed, errs, err_cap, depth, n_errs,
+                                  streams, engine_streams, now_us)
+
+    def device_compact_stats(self) -> Tuple[int, int]:
+        """gck_device_compact_stats: chunks of device requests whose join read and wrote the caller's
+        device buffers in place, and chunks expanded to items on the device."""
+        out = (C.c_uint64 * 2)()
+        _check(self._lib.gck_device_compact_stats(self._h, out))
+        return int(out[0]), int(out[1])
+
     def check_bulk_device(self, d_items: int, n: int, d_perm: int, d_err: int,
                           stream: Optional[int] = None, now_us: int = 0,
                           contexts: Optional[Sequence] = None):
@@ -1365,6 +1518,57 @@ class PreparedList(_Prepared):
         hdrs = (Uniform * max(1, len(headers)))(*[_header(h) for h in headers])
         self._args = (hdrs, u32(fixed), vary, arr(ids), u32(first), arr(ns), arr(packed), arr(errs), err_cap, self.n_errs,
                       depth, now_us)
+
+
+class PreparedUniformDevice(_Prepared):
+    """A compiled submit/wait loop over uniform device requests (Engine.prepare_uniform_device)."""
+
+    def __init__(self, engine, headers, pairs, ns, packed, errs, err_cap, depth, n_errs, streams, engine_streams,
+                 now_us):
+        super().__init__(engine, "gckd_run_uniform_device", "gck_check_submit_uniform_device", len(pairs), depth)
+        arr = self._arr
+        hdrs = (Uniform * max(1, len(headers)))(*[_header(h) for h in headers])
+        self._args = (hdrs, arr(pairs), arr(ns), arr(packed), arr(errs), err_cap, arr(n_errs or [0] * len(pairs)), depth,
+                      arr(streams or [0]), SUBMIT_ENGINE_STREAM if engine_streams else 0, now_us)
+
+
+class PreparedListDevice(_Prepared):
+    """A compiled submit/wait loop over list device requests (Engine.prepare_list_device)."""
+
+    def __init__(self, engine, headers, fixed, vary, ids, first, ns, packed, errs, err_cap, depth, n_errs, streams,
+                 engine_streams, now_us):
+        super().__init__(engine, "gckd_run_list_device", "gck_check_submit_list_device", len(ns), depth)
+        arr = self._arr
+        u32 = lambda xs: (C.c_uint32 * max(1, len(xs)))(*[int(x) for x in xs])
+        hdrs = (Uniform * max(1, len(headers)))(*[_header(h) for h in headers])
+        self._args = (hdrs, u32(fixed), vary, arr(ids), u32(first), arr(ns), arr(packed), arr(errs), err_cap,
+                      arr(n_errs or [0] * len(ns)), depth, arr(streams or [0]),
+                      SUBMIT_ENGINE_STREAM if engine_streams else 0, now_us)
+
+
+class DeviceCompactBatch:
+    """A submitted compact request over device buffers (gck_check_submit_uniform_device ...): wait()
+    completes it exactly once and returns the evaluated revision; the results are in the caller's
+    device buffers. It keeps the header or shape table alive until the wait."""
+
+    def __init__(self, engine, head):
+        self._engine, self._head = engine, head
+        self._h = _P()
+        self.revision = None
+
+    def wait(self):
+        if self._h is not None and self._h.value is not None:
+            h, self._h = self._h, None
+            rev = C.c_uint64(0)
+            _check(self._engine._lib.gck_check_wait_at(self._engine._h, h, C.byref(rev)))
+            self.revision = rev.value
+        return self.revision
+
+    def __del__(self):
+        try:
+            self.wait()
+        except Exception:
+            pass
 
 
 class Batch:

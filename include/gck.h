@@ -48,6 +48,11 @@
  *   gck_check_bulk_shaped / gck_check_submit_shaped
  *       any request of that loop that mixes at most GCK_MAX_SHAPES shapes check by check: a table
  *       of headers, one table index byte and one id pair per check (9 bytes), answered the same way.
+ *   gck_check_bulk_uniform_device / _shaped_device / _list_device and their gck_check_submit_* forms
+ *       the same compact requests for a caller whose ids already live in device memory (a device-side
+ *       candidate generator, a PyTorch pipeline): pairs, index bytes and id lists are read from, and
+ *       the packed plane and the ascending error list written to, device buffers; nothing per check
+ *       crosses PCIe.
  *
  * Ownership: all inputs and outputs are caller-allocated; the engine never retains a caller
  * pointer after a call returns, except that gck_check_submit keeps the output pointers (and, for
@@ -553,6 +558,64 @@ int gck_check_submit_list(gck_engine* e, const gck_consistency* cs, const gck_un
  * place or computed them from the range, out[1] = chunks expanded to items on the host (check
  * contexts, profiling, no one-round join, GCK_AQL=0). */
 int gck_list_stats(gck_engine* e, uint64_t out[2]);
+
+/* ---- compact requests over device buffers (ABI 13, additive) -------------------------
+ * The uniform, shaped and list requests above for ids that live in device memory: d_pairs,
+ * d_shape_of, d_ids, d_out_packed, d_out_errs and d_out_n_errs (a uint32_t) are device memory on the
+ * engine's device; hdr, shapes (copied by the call), contexts and out_revision are host memory.
+ * d_ids == NULL is the range form (first_id + i, GCK_VARY_RESOURCE only), which reads nothing.
+ * Check k, the word layout (padding bits 0, every one of the ceil(n / 32) words written,
+ * GCK_PERM_UNSPECIFIED for a check with an error) and the err_cap / count protocol are the host
+ * calls': the (index, GCK_ITEM_*) records in ascending index order, the first min(count, err_cap)
+ * written to d_out_errs, the count to *d_out_n_errs — always, 0 and n == 0 included, when the pointer
+ * is not NULL. d_out_n_errs may be NULL; d_out_errs may be NULL when err_cap == 0. The list is
+ * produced on the device: no per-check data crosses PCIe.
+ * Ordering is gck_check_bulk_device's and gck_check_submit's: a synchronous call orders on `stream`
+ * (NULL: the null stream) and returns with the results written; it chunks as the host forms do. A
+ * submitted batch (n <= max_batch) with flags 0 runs on the caller's `stream`; with
+ * GCK_SUBMIT_ENGINE_STREAM on the stream of its workspace: the inputs must be complete at the call
+ * and the results are complete when gck_check_wait / gck_check_wait_at returns. GCK_SUBMIT_DEVICE is
+ * accepted and implied. Buffers stay valid and unchanged until the synchronous call or the wait
+ * returns. Consistency, request errors and the evaluated revision are the host calls'.
+ * GCK_E_INVALID_ARGUMENT also for a d_pairs or d_out_packed that is not 8-byte aligned (the joins
+ * load a pair as one 64-bit word), a d_ids, d_out_errs or d_out_n_errs that is not 4-byte aligned,
+ * n >= 2^32 (nothing is launched for any of these), and a shape_of[k] >= n_shapes found on the
+ * device, reported by the synchronous call or by the wait with the smallest such k of the request. */
+int gck_check_bulk_uniform_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr,
+                                  const uint32_t* d_pairs, size_t n, const char* const* contexts,
+                                  const size_t* context_lens, size_t n_contexts, int64_t now_us, uint64_t* d_out_packed,
+                                  gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, void* stream,
+                                  uint64_t* out_revision);
+int gck_check_bulk_shaped_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* shapes, size_t n_shapes,
+                                 const uint8_t* d_shape_of, const uint32_t* d_pairs, size_t n,
+                                 const char* const* contexts, const size_t* context_lens, size_t n_contexts,
+                                 int64_t now_us, uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                 uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision);
+int gck_check_bulk_list_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                               uint32_t vary, const uint32_t* d_ids, uint32_t first_id, size_t n,
+                               const char* const* contexts, const size_t* context_lens, size_t n_contexts,
+                               int64_t now_us, uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                               uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision);
+int gck_check_submit_uniform_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr,
+                                    const uint32_t* d_pairs, size_t n, const char* const* contexts,
+                                    const size_t* context_lens, size_t n_contexts, int64_t now_us,
+                                    uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                    uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out);
+int gck_check_submit_shaped_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* shapes,
+                                   size_t n_shapes, const uint8_t* d_shape_of, const uint32_t* d_pairs, size_t n,
+                                   const char* const* contexts, const size_t* context_lens, size_t n_contexts,
+                                   int64_t now_us, uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                   uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out);
+int gck_check_submit_list_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                                 uint32_t vary, const uint32_t* d_ids, uint32_t first_id, size_t n,
+                                 const char* const* contexts, const size_t* context_lens, size_t n_contexts,
+                                 int64_t now_us, uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                 uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out);
+/* Since the engine was created: out[0] = chunks (of max_batch checks) of device requests whose join
+ * read the request and wrote the words in place in device memory, out[1] = chunks expanded to items
+ * on the device (check contexts, profiling, no one-round join, GCK_AQL=0, GCK_FLAG_NO_BUNDLE).
+ * gck_shaped_stats, gck_list_stats and gck_cross_stats do not count device requests. */
+int gck_device_compact_stats(gck_engine* e, uint64_t out[2]);
 
 /* ---- lookups (Client.LookupResources / LookupSubjects, client/client.go:508-599) -------- */
 /* Ids of the `resource_type` objects on which the subject has `permission` — HAS or CONDITIONAL,
