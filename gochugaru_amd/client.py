@@ -27,8 +27,8 @@ from . import rel as _rel
 from .consistency import Background, Context, Strategy
 from .engine import (CONSISTENCY_AT_LEAST, CONSISTENCY_FULL, CONSISTENCY_MIN_LATENCY,
                      CONSISTENCY_SNAPSHOT, ELLIPSIS, GCK_E_DEVICE, GCK_E_NOT_FOUND, GCK_E_REVISION,
-                     ID_ABSENT, ID_WILDCARD, ITEM_ERROR_MESSAGES, PERM_HAS, REL_INVALID, TYPE_INVALID, Engine,
-                     GckError, shape_request, unpack_cross, unpack_results)
+                     ID_ABSENT, ID_WILDCARD, ITEM_ERROR_MESSAGES, PERM_HAS, REL_INVALID, TYPE_INVALID,
+                     VARY_RESOURCE, VARY_SUBJECT, Engine, GckError, shape_request, unpack_cross, unpack_results)
 
 CHECK_ITER_CHUNK = 1000  # client/client.go:166
 
@@ -402,6 +402,73 @@ class Client:
             return
         yield from self._filter(ctx, cs, "FilterSubjects",
                                 [(i, (t, rel if rel not in ("", "...") else "")) for t, i, rel in sub], among)
+
+    # ---- the same over candidates that live on the device (Engine.filter_ids) -----------------
+    def _filter_device(self, ctx, what, candidates, run):
+        """FilterResourcesDevice / FilterSubjectsDevice after their own parsing: run() resolves the
+        names and filters the tensor (per attempt, as _filter does). Returns (ids, err)."""
+        try:
+            import torch
+            if not isinstance(candidates, torch.Tensor) or candidates.dtype not in (torch.int32, torch.uint32) \
+                    or not candidates.is_cuda:
+                raise InvalidArgument(f"{what}: the candidates must be a device int32 / uint32 tensor of interned ids")
+            if candidates.numel() == 0:
+                return candidates.reshape(-1)[:0], None
+            return retryRetriableErrors(ctx or Background, run), None
+        except Exception as e:  # noqa: BLE001
+            return None, e
+
+    def FilterResourcesDevice(self, ctx: Optional[Context], cs: Optional[Strategy], permission: str, subject: str,
+                              candidates):
+        """``FilterResources`` for candidates in device memory: ``candidates`` is a device int32 /
+        uint32 tensor of interned ids (``Engine.intern``) of ``permission``'s type ("document#view").
+        Returns ``(tensor, err)``: the ids on which ``subject`` has the permission (HAS or
+        CONDITIONAL), on the device, in the tensor's order and as often as it repeats them — checked
+        and compacted by kernels (Engine.filter_ids); only two count words come back to the host."""
+        self.checkOverlap(ctx)
+        try:
+            subj_type, subj_id, subj_rel = _rel.ParseObjectSet(subject)
+            obj_type, obj_rel = _rel.ParseTypedRelation(permission)
+            requirement, revision = _requirement(cs)
+            eng = self.engine
+
+            def run():
+                rt, st = eng.type_id(obj_type), eng.type_id(subj_type)
+                perm = eng.relation_id(rt, obj_rel)
+                srel = ELLIPSIS if subj_rel in ("", "...") else eng.relation_id(st, subj_rel)
+                if TYPE_INVALID in (rt, st) or REL_INVALID in (perm, srel):
+                    raise GckError(GCK_E_NOT_FOUND, "object definition or relation not found")
+                sid = int(eng.intern(st, [subj_id])[0])
+                return eng.filter_ids((rt, perm, st, srel), sid, VARY_RESOURCE, candidates, requirement=requirement,
+                                      revision=revision)
+        except Exception as e:  # noqa: BLE001
+            return None, e
+        return self._filter_device(ctx, "FilterResourcesDevice", candidates, run)
+
+    def FilterSubjectsDevice(self, ctx: Optional[Context], cs: Optional[Strategy], resource: str, permission: str,
+                             subject_type: str, candidates):
+        """The mirror: of the candidate subjects — interned ids of ``subject_type`` ("user", or
+        "team#member") in a device tensor — those that have ``permission`` on ``resource``
+        ("document:readme"). A wildcard grant makes every candidate match."""
+        self.checkOverlap(ctx)
+        try:
+            res_type, res_id, _ = _rel.ParseObjectSet(resource)
+            stype, srel_name, _ = _rel._cut(subject_type, "#")
+            requirement, revision = _requirement(cs)
+            eng = self.engine
+
+            def run():
+                rt, st = eng.type_id(res_type), eng.type_id(stype)
+                perm = eng.relation_id(rt, permission)
+                srel = ELLIPSIS if srel_name in ("", "...") else eng.relation_id(st, srel_name)
+                if TYPE_INVALID in (rt, st) or REL_INVALID in (perm, srel):
+                    raise GckError(GCK_E_NOT_FOUND, "object definition or relation not found")
+                rid = int(eng.intern(rt, [res_id])[0])
+                return eng.filter_ids((rt, perm, st, srel), rid, VARY_SUBJECT, candidates, requirement=requirement,
+                                      revision=revision)
+        except Exception as e:  # noqa: BLE001
+            return None, e
+        return self._filter_device(ctx, "FilterSubjectsDevice", candidates, run)
 
     # ---- snapshot plumbing (ReadSchema + ExportRelationships at its revision) -------------
     def LoadSnapshot(self, schema: str, revision: int, relationships: Iterable) -> None:

@@ -17,6 +17,9 @@
 // popcount per word, an exclusive scan over the block, records at base + rank while below err_cap.
 // `base` is the request's count so far on the device (the caller's *d_out_n_errs, or the word of the
 // request's first workspace), so the chunks of a request, emitted in chunk order, accumulate.
+//
+// A filter request (gck_filter_list_device) adds k_dc_select behind them, for every batch: the
+// survivors of the finished plane, in the caller's order, at their ranks in the request.
 
 // The shapes of a request, by value in the kernarg segment (a uniform or list request: one entry).
 struct DcShapes {
@@ -147,6 +150,60 @@ __global__ void k_dc_emit(uint32_t* bitmap, uint32_t words, const int32_t* err, 
   if (threadIdx.x == 0) *count = base + run;
 }
 
+// A filter request's chunk (include/gck.h gck_filter_list_device): the survivors of the finished
+// plane — the checks whose 2-bit value `mask` selects — as ascending records at their ranks in the
+// request (select_plane.hpp). One thread per word, a tile of blockDim words per block. A block's
+// first rank is the request's count before this chunk (*prev; null: 0, the first chunk) plus the
+// survivors of the words before its tile, which the block counts again itself, plus the exclusive
+// scan inside the tile (k_dc_emit's). No block waits on another, and none reads a word another one
+// writes: the block of the last tile writes the count so far to *next — never the word `prev`
+// names — and to *out_n.
+struct DcSelect {
+  const unsigned long long* plane;
+  uint32_t words, mask;
+  gck::SelectOut o;
+  const uint32_t* prev;
+  uint32_t* next;
+  uint32_t* out_n;
+};
+
+static_assert(gck::kSelBlock == (uint32_t)kBlock, "the host hook tiles as the kernel's blocks do");
+
+__global__ void __launch_bounds__(kBlock) k_dc_select(DcSelect a) {
+  __shared__ uint32_t before_tot[kWaves];
+  __shared__ uint32_t wave_tot[kWaves];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t tile0 = blockIdx.x * blockDim.x, t = tile0 + threadIdx.x;
+  const uint64_t* plane = reinterpret_cast<const uint64_t*>(a.plane);
+  uint32_t mine = gck::select_count_strided(plane, threadIdx.x, tile0, blockDim.x, a.mask);
+  for (int d = 32; d >= 1; d >>= 1) mine += (uint32_t)__shfl_xor((int)mine, d, 64);
+  const uint64_t word = t < a.words ? plane[t] : 0ull;
+  const uint64_t m = gck::select_mask(word, a.mask);
+  const uint32_t pc = gck::select_count(m);
+  uint32_t incl = pc;
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
+    if (lane >= (uint32_t)d) incl += up;
+  }
+  if (lane == 63u) {
+    wave_tot[wave] = incl;
+    before_tot[wave] = mine;
+  }
+  __syncthreads();
+  uint32_t base = a.prev ? *a.prev : 0u, tot = 0;
+  for (uint32_t k = 0; k < (uint32_t)kWaves; ++k) {
+    base += before_tot[k];
+    if (k < wave) base += wave_tot[k];
+    tot += wave_tot[k];
+  }
+  gck::select_write(word, m, t, base + incl - pc, a.o);
+  if (threadIdx.x == 0 && tile0 + blockDim.x >= a.words) {  // (wave 0: base holds nothing of this tile)
+    const uint32_t total = base + tot;
+    if (a.next) *a.next = total;
+    *a.out_n = total;
+  }
+}
+
 // The word a device request counts its errors in, cleared on `st` before the request's first chunk:
 // the caller's, or the workspace's own (which stays 0 until an emit adds to it).
 // (the caller's word of a submitted batch is left to the batch: CompactRun::zero_cnt)
@@ -224,6 +281,23 @@ static void device_collect(Engine& e, Workspace& w) {
                        c.d_cnt);
     HIP_OK(hipGetLastError());
     if (c.d_cnt == w.dc_aux) w.dc_cnt_dirty = true;
+  }
+  if (c.select) {
+    // the survivors of the finished plane: after the patch or the pack on this stream, for every
+    // filter batch. The chunk before this one was collected — its stream completed, below — before
+    // this one is, so *sel_prev holds its total
+    DcSelect a{};
+    a.plane = c.packed;
+    a.words = words;
+    a.mask = c.sel.mask;
+    a.o = gck::SelectOut{c.sel.d_out_ids, c.sel.d_out_pos, c.sel.d_out_perm,
+                         (uint32_t)std::min<size_t>(c.sel.cap, 0xFFFFFFFFu), c.sel_ids, c.sel_first, (uint32_t)c.pos};
+    a.prev = c.sel_prev;
+    a.next = c.sel_next;
+    a.out_n = c.sel.d_out_n;
+    hipLaunchKernelGGL(k_dc_select, dim3((words + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+    HIP_OK(hipGetLastError());
+    launched = true;
   }
   // (the count's clear — and the kernels above — are complete when the wait returns; a batch on the
   // caller's stream that launched nothing is ordered by that stream alone)

@@ -33,6 +33,10 @@ using submit_list_device_fn = int (*)(gck_engine*, const gck_consistency*, const
                                       const uint32_t*, uint32_t, size_t, const char* const*, const size_t*, size_t,
                                       int64_t, uint64_t*, gck_item_error*, size_t, uint32_t*, uint32_t, void*,
                                       gck_batch**);
+using submit_filter_device_fn = int (*)(gck_engine*, const gck_consistency*, const gck_uniform*, uint32_t, uint32_t,
+                                        const uint32_t*, uint32_t, size_t, const char* const*, const size_t*, size_t,
+                                        int64_t, const gck_select*, uint64_t*, gck_item_error*, size_t, uint32_t*,
+                                        uint32_t, void*, gck_batch**);
 
 // Optional per-batch timeline of the next loops (gckd_set_trace): for batch k, the seconds after
 // the loop's start at which its submit and its wait returned (stamps[2k], stamps[2k + 1]).
@@ -197,6 +201,32 @@ int gckd_run_list_device(submit_list_device_fn submit, wait_fn wait, gck_engine*
   return run_loop(n_batches, depth, wait, e, seconds, [&](size_t k, gck_batch** b) {
     return submit(e, cs, hdrs + k, fixed[k], vary, reinterpret_cast<const uint32_t*>(ids[k]), first[k], (size_t)ns[k],
                   nullptr, nullptr, 0, now_us, reinterpret_cast<uint64_t*>(packed[k]),
+                  reinterpret_cast<gck_item_error*>(errs[k]), err_cap, reinterpret_cast<uint32_t*>(n_errs[k]), flags,
+                  reinterpret_cast<void*>(streams[k % depth]), b);
+  });
+}
+
+// The list loop with the survivors compacted on the device (gck_filter_submit_list_device): request k
+// also has its own outputs — out_ids[k], out_pos[k], out_perm[k] (cap entries each; 0: not wanted)
+// and the count word out_n[k] — under the one mask; packed[k] may be 0.
+int gckd_run_filter_device(submit_filter_device_fn submit, wait_fn wait, gck_engine* e, const gck_consistency* cs,
+                           size_t n_batches, const gck_uniform* hdrs, const uint32_t* fixed, uint32_t vary,
+                           const uint64_t* ids, const uint32_t* first, const uint64_t* ns, uint32_t mask,
+                           const uint64_t* out_ids, const uint64_t* out_pos, const uint64_t* out_perm, size_t cap,
+                           const uint64_t* out_n, const uint64_t* packed, const uint64_t* errs, size_t err_cap,
+                           const uint64_t* n_errs, uint32_t depth, const uint64_t* streams, uint32_t flags,
+                           int64_t now_us, double* seconds) {
+  if (depth == 0) depth = 1;
+  return run_loop(n_batches, depth, wait, e, seconds, [&](size_t k, gck_batch** b) {
+    gck_select sel{};  // (copied by the call)
+    sel.mask = mask;
+    sel.d_out_ids = reinterpret_cast<uint32_t*>(out_ids[k]);
+    sel.d_out_pos = reinterpret_cast<uint32_t*>(out_pos[k]);
+    sel.d_out_perm = reinterpret_cast<uint8_t*>(out_perm[k]);
+    sel.cap = cap;
+    sel.d_out_n = reinterpret_cast<uint32_t*>(out_n[k]);
+    return submit(e, cs, hdrs + k, fixed[k], vary, reinterpret_cast<const uint32_t*>(ids[k]), first[k], (size_t)ns[k],
+                  nullptr, nullptr, 0, now_us, &sel, reinterpret_cast<uint64_t*>(packed[k]),
                   reinterpret_cast<gck_item_error*>(errs[k]), err_cap, reinterpret_cast<uint32_t*>(n_errs[k]), flags,
                   reinterpret_cast<void*>(streams[k % depth]), b);
   });

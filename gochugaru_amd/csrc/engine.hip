@@ -44,6 +44,7 @@
 
 #include "engine.hpp"
 #include "slot_pack.hpp"
+#include "select_plane.hpp"
 
 namespace gck {
 
@@ -234,6 +235,16 @@ struct CompactRun {
   uint32_t* d_cnt = nullptr;
   bool zero_cnt = false;  // ... which this batch still has to clear (the join's block 0 does: dc_steal_clear; else a memset)
   bool cnt_memset = false;  // ... cleared by a memset on the batch's stream
+  // a filter request's chunk (CompactReq::sel): the survivors of the finished plane go to the caller's
+  // arrays (k_dc_select). sel_ids / sel_first: the chunk's varying ids (a device list, or null and the
+  // chunk's first id); sel_prev: the word that holds the request's count before this chunk (null: the
+  // first chunk, 0), sel_next: the other word of the pair, which takes the count after it
+  bool select = false;
+  gck_select sel{};
+  const uint32_t* sel_ids = nullptr;
+  uint32_t sel_first = 0;
+  const uint32_t* sel_prev = nullptr;
+  uint32_t* sel_next = nullptr;
   bool in_place() const { return mode == kInPlace; }
   bool table_join() const { return mode == kInPlace && indexed; }  // the join reads index bytes and a shape table
 };
@@ -285,7 +296,9 @@ struct Workspace {
   uint32_t res_seq = 0;       // resident-join requests posted from it
   CompactBatch cb;            // the batch is a compact request's chunk (submit_compact)
   uint32_t* dc_bitmap = nullptr;  // device_compact.inc: one error bit per check of a device request's chunk (zero between batches)
-  uint32_t* dc_aux = nullptr;     // ... [0] the errors so far of a request that gives no count word, [1] an expanded chunk's bad index
+  uint32_t* dc_aux = nullptr;     // ... [0] the errors so far of a request that gives no count word, [1] an expanded chunk's bad index,
+                                  // [2], [3] a filter request's survivors so far, by chunk parity (k_dc_select)
+  unsigned long long* dc_plane = nullptr;  // ... the plane of a filter request that gives none (max_batch / 32 words)
   bool dc_cnt_dirty = false;      // ... dc_aux[0] may be non-zero
   uint32_t pair_dirty = 0;        // one of the two alternating deferred-list counters (aql_summaries) may be non-zero:
                                   // the next so many dispatched joins must clear the other one themselves
@@ -2080,9 +2093,10 @@ static Workspace* create_workspace(Engine& e) {
     w->d_err = dalloc<int32_t>(w->allocs, w->max_batch, &w->bytes);
     w->cav_flag = dalloc<uint8_t>(w->allocs, w->max_batch, &w->bytes);
     w->dc_bitmap = dalloc<uint32_t>(w->allocs, w->max_batch / 32 + 1, &w->bytes);
-    w->dc_aux = dalloc<uint32_t>(w->allocs, 2, &w->bytes);
+    w->dc_aux = dalloc<uint32_t>(w->allocs, 4, &w->bytes);
+    w->dc_plane = dalloc<unsigned long long>(w->allocs, w->max_batch / 32 + 1, &w->bytes);
     HIP_OK(hipMemsetAsync(w->dc_bitmap, 0, (w->max_batch / 32 + 1) * sizeof(uint32_t), nullptr));
-    HIP_OK(hipMemsetAsync(w->dc_aux, 0, 2 * sizeof(uint32_t), nullptr));
+    HIP_OK(hipMemsetAsync(w->dc_aux, 0, 4 * sizeof(uint32_t), nullptr));
     w->d_ctx = reinterpret_cast<Ctx*>(dalloc<unsigned char>(w->allocs, sizeof(Ctx), &w->bytes));
     HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&w->h_ctx), sizeof(Ctx), hipHostMallocDefault));
     HIP_OK(hipHostMalloc(&w->h_ctr, sizeof(DevCounters) + (kBCtrs + 4) * sizeof(unsigned),
@@ -3733,10 +3747,21 @@ static size_t cross_tiles(const CompactReq& q) {
 // Queues the chunk [pos, pos + len) of the request on w (pos: a multiple of 32); of a cross request
 // in place (q.tile_rows != 0): its tile number pos, left to right and top to bottom.
 static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t pos, uint32_t len, int64_t now_us,
-                           uint32_t* d_cnt = nullptr) {
+                           uint32_t* d_cnt = nullptr, uint32_t* sel_pair = nullptr) {
   CompactRun c;
   c.device = q.device;
   c.d_cnt = d_cnt;
+  if (q.sel) {  // a filter request (a list request over device buffers)
+    c.select = true;
+    c.sel = *q.sel;
+    c.sel_ids = q.ids ? q.ids + pos : nullptr;
+    c.sel_first = q.ids ? 0u : q.first_id + (uint32_t)pos;
+    if (sel_pair) {  // (chunks of max_batch & ~31: compact_chunks)
+      const size_t k = pos / std::max<size_t>(w.max_batch & ~(size_t)31, 1);
+      c.sel_prev = k ? sel_pair + ((k - 1) & 1) : nullptr;
+      c.sel_next = sel_pair + (k & 1);
+    }
+  }
   c.zero_cnt = q.device && q.zero_cnt;
   c.indexed = q.shape_of != nullptr;
   c.n_shapes = q.n_shapes;
@@ -3744,7 +3769,9 @@ static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t 
   c.cross = q.cross();
   c.R = q.R;
   // (a cross batch's words go to their rows of the whole plane: uniform_collect)
-  c.out = reinterpret_cast<unsigned long long*>(c.cross ? q.packed : q.packed + pos / 32);
+  // (a filter request without a plane of its own: the chunk's words stay in the workspace)
+  c.out = q.sel && !q.packed ? w.dc_plane
+                             : reinterpret_cast<unsigned long long*>(c.cross ? q.packed : q.packed + pos / 32);
   c.errs = q.errs;  // (read by device_wait only: a synchronous request's chunks are collected by its caller)
   c.err_cap = q.err_cap;
   c.n_errs = q.n_errs;
@@ -3949,7 +3976,9 @@ static size_t compact_chunks(Engine& e, Workspace* w0, Workspace* w1, const Comp
   }
   run_chunks(
       e, w0, w1, req.n, mb, cav,
-      [&](Workspace& w, size_t pos, uint32_t len) { submit_compact(e, w, req, pos, len, now_us, d_cnt); },
+      [&](Workspace& w, size_t pos, uint32_t len) {
+        submit_compact(e, w, req, pos, len, now_us, d_cnt, req.sel ? w0->dc_aux + 2 : nullptr);
+      },
       [&](Workspace& w) {
         // (chunks complete in request order, each list written before the next is begun: ascending)
         if (req.device) device_collect(e, w);

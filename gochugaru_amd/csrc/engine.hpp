@@ -447,6 +447,10 @@ struct CompactReq {
   void* stream = nullptr;
   uint32_t* d_n_errs = nullptr;
   bool zero_cnt = false;  // set by the engine: a submitted batch clears *d_n_errs itself (engine.hip dc_steal_clear)
+  // a filter request (gck_filter_list_device; a list request over device buffers): the survivors of
+  // each chunk's finished plane go to *sel's arrays, their number to *sel->d_out_n (copied per chunk).
+  // `packed` may then be null: the plane stays in the workspace
+  const gck_select* sel = nullptr;
 };
 // *d_n_errs = 0 for an empty device request (synchronous on `stream`; a null pointer: nothing).
 void device_zero_count(Engine& e, uint32_t* d_n_errs, void* stream);

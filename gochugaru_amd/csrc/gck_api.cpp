@@ -14,6 +14,7 @@
 
 #include "engine.hpp"
 #include "slot_pack.hpp"
+#include "select_plane.hpp"
 
 namespace gck {
 
@@ -1283,7 +1284,8 @@ int gck_cross_stats(gck_engine* ge, uint64_t out[2]) {
 // is needed to fail them). Returns the request as the engine takes it.
 static CompactReq list_request(const gck_uniform* hdr, uint32_t fixed_id, uint32_t vary, const uint32_t* ids,
                                uint32_t first_id, size_t n, size_t n_contexts, uint64_t* out_packed,
-                               gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs) {
+                               gck_item_error* out_errs, size_t err_cap, size_t* out_n_errs,
+                               bool need_plane = true) {
   check_uniform(hdr, n_contexts);
   REQUIRE(hdr->reserved == 0, GCK_E_INVALID_ARGUMENT, "list header: reserved must be 0");
   REQUIRE(vary == GCK_VARY_RESOURCE || vary == GCK_VARY_SUBJECT, GCK_E_INVALID_ARGUMENT,
@@ -1294,7 +1296,7 @@ static CompactReq list_request(const gck_uniform* hdr, uint32_t fixed_id, uint32
     REQUIRE((uint64_t)first_id + n <= 0x100000000ull, GCK_E_INVALID_ARGUMENT,
             "list request: the range " + std::to_string(first_id) + " + " + std::to_string(n) + " passes 2^32");
   }
-  REQUIRE(n == 0 || out_packed, GCK_E_INVALID_ARGUMENT, "null buffers");
+  REQUIRE(n == 0 || out_packed || !need_plane, GCK_E_INVALID_ARGUMENT, "null buffers");
   REQUIRE(err_cap == 0 || out_errs, GCK_E_INVALID_ARGUMENT, "null error list");
   if (out_n_errs) *out_n_errs = 0;
   CompactReq q{hdr, 1u, nullptr, nullptr, n, out_packed, out_errs, err_cap, out_n_errs};
@@ -1371,6 +1373,7 @@ static void check_device_sync(Engine& e, const CallCtx& c, const CompactReq& req
     std::shared_lock<std::shared_mutex> lk(e.mu);
     check_request(e, c.cs, c.contexts, c.context_lens, c.n_contexts);
     device_zero_count(e, req.d_n_errs, req.stream);
+    if (req.sel) device_zero_count(e, req.sel->d_out_n, req.stream);
     if (out_revision) *out_revision = e.revision;
     return;
   }
@@ -1385,6 +1388,7 @@ static gck_batch* submit_device(Engine& e, const CallCtx& c, const CompactReq& r
   if (req.n == 0) {
     try {
       device_zero_count(e, req.d_n_errs, req.engine_stream ? nullptr : req.stream);
+      if (req.sel) device_zero_count(e, req.sel->d_out_n, req.engine_stream ? nullptr : req.stream);
     } catch (...) {
       delete b;
       throw;
@@ -1490,6 +1494,59 @@ int gck_check_submit_list_device(gck_engine* ge, const gck_consistency* cs, cons
     const CompactReq req = device_request(
         list_request(hdr, fixed_id, vary, d_ids, first_id, n, n_contexts, d_out_packed, d_out_errs, err_cap, nullptr),
         d_out_errs, d_out_n_errs, stream, (flags & GCK_SUBMIT_ENGINE_STREAM) != 0);
+    *out = submit_device(e, {cs, contexts, context_lens, n_contexts}, req, now_us);
+  });
+}
+
+// ---- filter requests (include/gck.h gck_filter_list_device) -----------------------------------
+
+// A filter request's selection against the call, before anything is launched; then the list device
+// request with it (`sel` is the caller's: the engine copies it per chunk before the call returns).
+static CompactReq filter_request(const gck_select* sel, CompactReq q) {
+  const auto aligned = [](const void* p) { return ((uintptr_t)p & 3u) == 0; };
+  REQUIRE(sel, GCK_E_INVALID_ARGUMENT, "filter request: null gck_select");
+  REQUIRE(sel->mask != 0 && !(sel->mask & ~0xEu), GCK_E_INVALID_ARGUMENT,
+          "filter request: mask must select among GCK_SELECT_NO, GCK_SELECT_HAS and GCK_SELECT_CONDITIONAL");
+  REQUIRE(sel->reserved == 0, GCK_E_INVALID_ARGUMENT, "filter request: gck_select.reserved must be 0");
+  REQUIRE(sel->d_out_n, GCK_E_INVALID_ARGUMENT, "filter request: null d_out_n");
+  REQUIRE(sel->cap == 0 || sel->d_out_ids || sel->d_out_pos || sel->d_out_perm, GCK_E_INVALID_ARGUMENT,
+          "filter request: cap > 0 without an output array");
+  REQUIRE(aligned(sel->d_out_ids) && aligned(sel->d_out_pos) && aligned(sel->d_out_n), GCK_E_INVALID_ARGUMENT,
+          "filter request: d_out_ids, d_out_pos or d_out_n is not 4-byte aligned");
+  q.sel = sel;
+  return q;
+}
+
+int gck_filter_list_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                           uint32_t vary, const uint32_t* d_ids, uint32_t first_id, size_t n,
+                           const char* const* contexts, const size_t* context_lens, size_t n_contexts, int64_t now_us,
+                           const gck_select* sel, uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                           uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision) {
+  return guard([&] {
+    Engine& e = need(ge);
+    const CompactReq req = filter_request(
+        sel, device_request(list_request(hdr, fixed_id, vary, d_ids, first_id, n, n_contexts, d_out_packed, d_out_errs,
+                                         err_cap, nullptr, false),
+                            d_out_errs, d_out_n_errs, stream, true));
+    check_device_sync(e, {cs, contexts, context_lens, n_contexts}, req, now_us, out_revision);
+  });
+}
+
+int gck_filter_submit_list_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                                  uint32_t vary, const uint32_t* d_ids, uint32_t first_id, size_t n,
+                                  const char* const* contexts, const size_t* context_lens, size_t n_contexts,
+                                  int64_t now_us, const gck_select* sel, uint64_t* d_out_packed,
+                                  gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, uint32_t flags,
+                                  void* stream, gck_batch** out) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    check_submit_flags(flags);
+    const CompactReq req = filter_request(
+        sel, device_request(list_request(hdr, fixed_id, vary, d_ids, first_id, n, n_contexts, d_out_packed, d_out_errs,
+                                         err_cap, nullptr, false),
+                            d_out_errs, d_out_n_errs, stream, (flags & GCK_SUBMIT_ENGINE_STREAM) != 0));
     *out = submit_device(e, {cs, contexts, context_lens, n_contexts}, req, now_us);
   });
 }
@@ -1846,6 +1903,30 @@ int gck_test_slot_pack(uint32_t bits, const uint32_t* raw, uint32_t n, uint32_t 
   const uint32_t m = gck::slot_sort_unique(e, n);
   gck::slot_pack_sorted(bits, e, m, list_at, w);
   return (int)m;
+}
+
+// gck_test_select_plane: the ordered selection of k_dc_select (select_plane.hpp) over a chunk's plane
+// of n_words words on the host, tile by tile as the kernel's blocks take it: a tile's first rank is
+// `base` (the request's count before the chunk) plus a recount of the words before the tile, ranks
+// inside the tile run on. Survivors' positions and GCK_PERM_* go to out_pos / out_perm (either may
+// be null) while their rank is below cap; *out_n = base + the chunk's survivors. -1 for a bad mask
+// or null arguments.
+int gck_test_select_plane(const uint64_t* words, uint32_t n_words, uint32_t mask, uint32_t base, uint32_t cap,
+                          uint32_t* out_pos, uint8_t* out_perm, uint32_t* out_n) {
+  if (mask == 0 || (mask & ~0xEu) || (!words && n_words) || !out_n) return -1;
+  const gck::SelectOut o{nullptr, out_pos, out_perm, cap, nullptr, 0u, 0u};
+  uint32_t total = base;
+  for (uint32_t tile0 = 0; tile0 < n_words; tile0 += gck::kSelBlock) {
+    uint32_t rank = base + gck::select_count_strided(words, 0, tile0, 1, mask);
+    for (uint32_t t = tile0; t < n_words && t < tile0 + gck::kSelBlock; ++t) {
+      const uint64_t m = gck::select_mask(words[t], mask);
+      gck::select_write(words[t], m, t, rank, o);
+      rank += gck::select_count(m);
+    }
+    total = rank;
+  }
+  *out_n = total;
+  return 0;
 }
 
 }  // extern "C"

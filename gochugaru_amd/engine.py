@@ -156,6 +156,18 @@ def unpack_results(words: np.ndarray, n: int) -> np.ndarray:
     return four[:n].astype(np.uint8)
 
 
+class Select(C.Structure):
+    """gck_select (include/gck.h): which Permissionships survive a filter request, and the device
+    arrays the survivors go to."""
+    _fields_ = [("mask", C.c_uint32), ("reserved", C.c_uint32), ("d_out_ids", C.c_void_p), ("d_out_pos", C.c_void_p),
+                ("d_out_perm", C.c_void_p), ("cap", C.c_size_t), ("d_out_n", C.c_void_p)]
+
+
+SELECT_NO = 1 << PERM_NO                       # GCK_SELECT_NO
+SELECT_HAS = 1 << PERM_HAS                     # GCK_SELECT_HAS
+SELECT_CONDITIONAL = 1 << PERM_CONDITIONAL     # GCK_SELECT_CONDITIONAL
+SELECT_LOOKUP = SELECT_HAS | SELECT_CONDITIONAL  # GCK_SELECT_LOOKUP: LookupResources' rule
+
 CROSS_IDS = 2048  # GCK_CROSS_IDS
 VARY_RESOURCE = 1  # GCK_VARY_RESOURCE: a list request's ids are resource ids (the fixed id is the subject's)
 VARY_SUBJECT = 2   # GCK_VARY_SUBJECT: ... subject ids (the fixed id is the resource's)
@@ -328,6 +340,14 @@ _SIGS = {
                                                C.POINTER(C.c_size_t), C.c_size_t, C.c_int64, _P, _P, C.c_size_t, _P,
                                                C.c_uint32, _P, C.POINTER(_P)]),
     "gck_device_compact_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "gck_filter_list_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), C.c_uint32, C.c_uint32, _P,
+                                         C.c_uint32, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                         C.c_size_t, C.c_int64, C.POINTER(Select), _P, _P, C.c_size_t, _P, _P,
+                                         C.POINTER(C.c_uint64)]),
+    "gck_filter_submit_list_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), C.c_uint32,
+                                                C.c_uint32, _P, C.c_uint32, C.c_size_t, C.POINTER(C.c_char_p),
+                                                C.POINTER(C.c_size_t), C.c_size_t, C.c_int64, C.POINTER(Select), _P,
+                                                _P, C.c_size_t, _P, C.c_uint32, _P, C.POINTER(_P)]),
     "gck_lookup_resources_among": (C.c_int, [_P, C.POINTER(_Consistency), C.c_uint16, C.c_uint16, C.c_uint16,
                                              C.c_uint16, C.c_uint32, _P, C.c_size_t, C.c_int64, _P, _P, C.c_size_t,
                                              C.POINTER(C.c_size_t)]),
@@ -450,6 +470,12 @@ def _driver():
                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int64,
                                            C.POINTER(C.c_double)]
+        d.gckd_run_filter_device.restype = C.c_int
+        d.gckd_run_filter_device.argtypes = [C.c_void_p, C.c_void_p, _P, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                             C.c_int64, C.POINTER(C.c_double)]
         d.gckd_set_trace.restype = None
         d.gckd_set_trace.argtypes = [C.c_void_p, C.c_size_t]
         _DRIVER = d
@@ -520,7 +546,8 @@ class Engine:
         _check(lib.gck_create(C.byref(cfg), C.byref(h)))
         self._h = h
         self._lib = lib
-        self._pins = 0          # live host_array() buffers (each keeps the engine handle alive)
+        self.device = device    # the HIP device the engine lives on (filter_ids allocates there)
+        self._pins = 0         # live host_array() buffers (each keeps the engine handle alive)
         self._closing = False
         self._staged = {}       # ticket -> the staged Watch batch's array (kept alive until applied)
         self._type_ids = {}
@@ -1120,6 +1147,105 @@ class Engine:
         return PreparedListDevice(self, headers, fixed, vary, ids, first, ns, packed, errs, err_cap, depth, n_errs,
                                   streams, engine_streams, now_us)
 
+    # ---- filter requests (gck_filter_list_device): the list device request, its survivors compacted
+    # on the device. d_out_n: one u32 (required); d_out_ids / d_out_pos (u32) and d_out_perm (u8): `cap`
+    # entries each, 0: not wanted; d_out_packed may be 0 (the plane stays in the engine).
+    def filter_list_device(self, header, fixed_id: int, vary: int, n: int, d_out_n: int, cap: int, d_out_ids: int = 0,
+                           d_out_pos: int = 0, d_out_perm: int = 0, select: int = SELECT_LOOKUP, d_out_packed: int = 0,
+                           d_ids: int = 0, first_id: int = 0, d_out_errs: int = 0, err_cap: int = 0,
+                           d_out_n_errs: int = 0, stream: Optional[int] = None,
+                           requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                           contexts: Optional[Sequence] = None) -> int:
+        """gck_filter_list_device: check_list_device, then the checks whose Permissionship `select`
+        (SELECT_*) names, in request order: their ids, positions and Permissionships into the device
+        arrays, their number into *d_out_n. A per-item error does not fail the call (it is counted in
+        *d_out_n_errs and never survives). Returns the evaluated revision."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        sel = Select(select, 0, d_out_ids or None, d_out_pos or None, d_out_perm or None, cap, d_out_n or None)
+        rev = C.c_uint64(0)
+        _check(self._lib.gck_filter_list_device(self._h, C.byref(cs), C.byref(hdr), fixed_id, vary, d_ids or None,
+                                                first_id, n, *tail[:4], C.byref(sel), *tail[4:], stream,
+                                                C.byref(rev)))
+        return rev.value
+
+    def submit_filter_list_device(self, header, fixed_id: int, vary: int, n: int, d_out_n: int, cap: int,
+                                  d_out_ids: int = 0, d_out_pos: int = 0, d_out_perm: int = 0,
+                                  select: int = SELECT_LOOKUP, d_out_packed: int = 0, d_ids: int = 0, first_id: int = 0,
+                                  d_out_errs: int = 0, err_cap: int = 0, d_out_n_errs: int = 0,
+                                  stream: Optional[int] = None, engine_stream: bool = False,
+                                  requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                                  contexts: Optional[Sequence] = None) -> "DeviceCompactBatch":
+        """gck_filter_submit_list_device: as submit_list_device, with filter_list_device's outputs."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        sel = Select(select, 0, d_out_ids or None, d_out_pos or None, d_out_perm or None, cap, d_out_n or None)
+        b = DeviceCompactBatch(self, hdr)
+        _check(self._lib.gck_filter_submit_list_device(self._h, C.byref(cs), C.byref(hdr), fixed_id, vary,
+                                                       d_ids or None, first_id, n, *tail[:4], C.byref(sel), *tail[4:],
+                                                       SUBMIT_ENGINE_STREAM if engine_stream else 0, stream,
+                                                       C.byref(b._h)))
+        return b
+
+    def prepare_filter_device(self, headers, fixed, vary: int, ids, first, ns, out_n, cap: int, depth: int,
+                              out_ids=None, out_pos=None, out_perm=None, select: int = SELECT_LOOKUP, packed=None,
+                              errs=None, err_cap: int = 0, n_errs=None, streams=None, engine_streams: bool = True,
+                              now_us: int = 0) -> "PreparedFilterDevice":
+        """The compiled loop over filter requests (gckd_run_filter_device): as prepare_list_device, with
+        request k's survivors into out_ids[k] / out_pos[k] / out_perm[k] (`cap` entries; None: not
+        wanted) and their number into out_n[k], all under the one `select`; packed may be None."""
+        return PreparedFilterDevice(self, headers, fixed, vary, ids, first, ns, select, out_ids, out_pos, out_perm,
+                                    cap, out_n, packed, errs, err_cap, depth, n_errs, streams, engine_streams, now_us)
+
+    def filter_ids(self, header, fixed_id: int, vary: int, ids=None, first_id: int = 0, n: Optional[int] = None,
+                   select: int = SELECT_LOOKUP, want_pos: bool = False, want_perm: bool = False,
+                   requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                   contexts: Optional[Sequence] = None):
+        """The survivors of a filter request as torch tensors: `ids` is a device int32 / uint32 tensor
+        of varying ids (None: the range first_id .. first_id + n - 1 on the engine's device). Runs
+        filter_list_device on the current stream with outputs allocated on the tensor's device, reads
+        the two count words — the call's only copy to the host — and returns the surviving ids (in
+        the tensor's dtype), then their positions (int64-indexable int32) and Permissionships (uint8)
+        when asked for, each sliced to the survivor count. A per-item error raises GckError with the
+        lookups' message."""
+        import torch
+        if ids is not None:
+            if ids.dtype not in (torch.int32, torch.uint32) or not ids.is_cuda:
+                raise GckError(GCK_E_INVALID_ARGUMENT, "filter_ids: ids must be a device int32 / uint32 tensor")
+            ids = ids.contiguous().reshape(-1)
+            n, dev, dtype = ids.numel(), ids.device, ids.dtype
+        else:
+            if n is None:
+                raise GckError(GCK_E_INVALID_ARGUMENT, "filter_ids: a range needs n")
+            dev, dtype = torch.device("cuda", self.device), torch.int32
+        with torch.cuda.device(dev):
+            counts = torch.empty(2, dtype=torch.int32, device=dev)  # [survivors, errors]
+            out_ids = torch.empty(n, dtype=dtype, device=dev)
+            out_pos = torch.empty(n, dtype=torch.int32, device=dev) if want_pos else None
+            out_perm = torch.empty(n, dtype=torch.uint8, device=dev) if want_perm else None
+            err = torch.empty(2, dtype=torch.int32, device=dev)  # the first error record
+            self.filter_list_device(header, fixed_id, vary, n, counts.data_ptr(), n, d_out_ids=out_ids.data_ptr(),
+                                    d_out_pos=out_pos.data_ptr() if want_pos else 0,
+                                    d_out_perm=out_perm.data_ptr() if want_perm else 0, select=select,
+                                    d_ids=ids.data_ptr() if ids is not None and n else 0, first_id=first_id,
+                                    d_out_errs=err.data_ptr(), err_cap=1, d_out_n_errs=counts.data_ptr() + 4,
+                                    stream=torch.cuda.current_stream(dev).cuda_stream, requirement=requirement,
+                                    revision=revision, now_us=now_us, contexts=contexts)
+            total, n_errs = (int(x) & 0xFFFFFFFF for x in counts.tolist())
+            if n_errs:
+                code = int(err[1].item())
+                raise GckError(GCK_E_INVALID_ARGUMENT,
+                               ITEM_ERROR_MESSAGES[ITEM_ERR_MAX_DEPTH] if code == ITEM_ERR_MAX_DEPTH
+                               else f"lookup failed: per-item error {code}")
+        out = (out_ids[:total],)
+        if want_pos:
+            out += (out_pos[:total],)
+        if want_perm:
+            out += (out_perm[:total],)
+        return out[0] if len(out) == 1 else out
+
     def device_compact_stats(self) -> Tuple[int, int]:
         """gck_device_compact_stats: chunks of device requests whose join read and wrote the caller's
         device buffers in place, and chunks expanded to items on the device."""
@@ -1544,6 +1670,21 @@ class PreparedListDevice(_Prepared):
         self._args = (hdrs, u32(fixed), vary, arr(ids), u32(first), arr(ns), arr(packed), arr(errs), err_cap,
                       arr(n_errs or [0] * len(ns)), depth, arr(streams or [0]),
                       SUBMIT_ENGINE_STREAM if engine_streams else 0, now_us)
+
+
+class PreparedFilterDevice(_Prepared):
+    """A compiled submit/wait loop over filter requests (Engine.prepare_filter_device)."""
+
+    def __init__(self, engine, headers, fixed, vary, ids, first, ns, select, out_ids, out_pos, out_perm, cap, out_n,
+                 packed, errs, err_cap, depth, n_errs, streams, engine_streams, now_us):
+        super().__init__(engine, "gckd_run_filter_device", "gck_filter_submit_list_device", len(ns), depth)
+        arr = self._arr
+        u32 = lambda xs: (C.c_uint32 * max(1, len(xs)))(*[int(x) for x in xs])
+        opt = lambda xs: arr(xs or [0] * len(ns))
+        hdrs = (Uniform * max(1, len(headers)))(*[_header(h) for h in headers])
+        self._args = (hdrs, u32(fixed), vary, arr(ids), u32(first), arr(ns), select, opt(out_ids), opt(out_pos),
+                      opt(out_perm), cap, arr(out_n), opt(packed), opt(errs), err_cap, opt(n_errs), depth,
+                      arr(streams or [0]), SUBMIT_ENGINE_STREAM if engine_streams else 0, now_us)
 
 
 class DeviceCompactBatch:

@@ -53,6 +53,10 @@
  *       candidate generator, a PyTorch pipeline): pairs, index bytes and id lists are read from, and
  *       the packed plane and the ascending error list written to, device buffers; nothing per check
  *       crosses PCIe.
+ *   gck_filter_list_device / gck_filter_submit_list_device
+ *       the list device request with its last step on the device too: the checks whose Permissionship
+ *       a mask selects, compacted by a kernel into device arrays of ids, positions and
+ *       Permissionships in the caller's order, and their number.
  *
  * Ownership: all inputs and outputs are caller-allocated; the engine never retains a caller
  * pointer after a call returns, except that gck_check_submit keeps the output pointers (and, for
@@ -616,6 +620,52 @@ int gck_check_submit_list_device(gck_engine* e, const gck_consistency* cs, const
  * on the device (check contexts, profiling, no one-round join, GCK_AQL=0, GCK_FLAG_NO_BUNDLE).
  * gck_shaped_stats, gck_list_stats and gck_cross_stats do not count device requests. */
 int gck_device_compact_stats(gck_engine* e, uint64_t out[2]);
+
+/* ---- filter requests (ABI 13, additive) ----------------------------------------------
+ * gck_check_bulk_list_device / gck_check_submit_list_device with the last step done on the device
+ * too: of the n checks of the list request, the survivors — their varying ids, their positions in
+ * the request and their Permissionships — compacted by a kernel into the caller's device arrays, in
+ * the caller's order. The check itself is the list device call's, unchanged: the id list or range,
+ * `vary`, consistency, the chunking of the synchronous form, stream ordering, `flags`, lifetimes,
+ * the error records and the request errors.
+ * Check i survives iff it has no per-item error and (sel->mask >> perm_i) & 1. Survivors are written
+ * in ascending i, an id as often as the list repeats it: the first min(total, cap) of them to each
+ * output array that is not NULL, entries beyond that untouched. *d_out_n = the survivors of the whole
+ * request — always written, for 0 survivors and for n == 0 too.
+ * A check with an error never survives; it is reported through d_out_errs / *d_out_n_errs as the list
+ * device call reports it. Unlike gck_lookup_resources_among, the device form does NOT fail the call
+ * on a per-item error: the caller holds the count word and decides.
+ * d_out_packed may be NULL: the plane then stays in a device buffer of the workspace (allocated with
+ * it; no check allocates). When given, it is written exactly as gck_check_bulk_list_device writes it.
+ * `sel` is copied by the call (the submit call included). GCK_E_INVALID_ARGUMENT, nothing launched,
+ * for sel == NULL, mask == 0, mask & 1 (GCK_PERM_UNSPECIFIED cannot be selected), mask above 0xE,
+ * reserved != 0, d_out_n == NULL, cap > 0 with all three output arrays NULL, a d_out_ids, d_out_pos
+ * or d_out_n that is not 4-byte aligned, and everything the list device call refuses.
+ * gck_device_compact_stats counts a filter request's chunks as a list device request's. */
+#define GCK_SELECT_NO          (1u << GCK_PERM_NO)
+#define GCK_SELECT_HAS         (1u << GCK_PERM_HAS)
+#define GCK_SELECT_CONDITIONAL (1u << GCK_PERM_CONDITIONAL)
+#define GCK_SELECT_LOOKUP      (GCK_SELECT_HAS | GCK_SELECT_CONDITIONAL)   /* LookupResources' rule */
+typedef struct gck_select {
+  uint32_t mask;        /* which Permissionships survive; bit GCK_PERM_UNSPECIFIED must be 0, mask != 0 */
+  uint32_t reserved;    /* 0 */
+  uint32_t* d_out_ids;  /* device, cap entries: the surviving check's varying id (ids[i] or first_id + i); may be NULL */
+  uint32_t* d_out_pos;  /* device, cap entries: its position i in the request; may be NULL */
+  uint8_t*  d_out_perm; /* device, cap entries: its GCK_PERM_*; may be NULL */
+  size_t    cap;
+  uint32_t* d_out_n;    /* device, required: the number of survivors of the whole request */
+} gck_select;
+int gck_filter_list_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                           uint32_t vary, const uint32_t* d_ids, uint32_t first_id, size_t n,
+                           const char* const* contexts, const size_t* context_lens, size_t n_contexts, int64_t now_us,
+                           const gck_select* sel, uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                           uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision);
+int gck_filter_submit_list_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                                  uint32_t vary, const uint32_t* d_ids, uint32_t first_id, size_t n,
+                                  const char* const* contexts, const size_t* context_lens, size_t n_contexts,
+                                  int64_t now_us, const gck_select* sel, uint64_t* d_out_packed,
+                                  gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, uint32_t flags,
+                                  void* stream, gck_batch** out);
 
 /* ---- lookups (Client.LookupResources / LookupSubjects, client/client.go:508-599) -------- */
 /* Ids of the `resource_type` objects on which the subject has `permission` — HAS or CONDITIONAL,
