@@ -470,6 +470,40 @@ class Client:
             return None, e
         return self._filter_device(ctx, "FilterSubjectsDevice", candidates, run)
 
+    def CheckCrossDevice(self, ctx: Optional[Context], cs: Optional[Strategy], permission: str, resources,
+                         subject_type: str, subjects):
+        """``CheckCross`` for id lists in device memory — a batch of users against a page of
+        candidates: ``resources`` are interned ids (``Engine.intern``) of ``permission``'s type
+        ("document#view"), ``subjects`` of ``subject_type`` ("user", or "team#member"), both device
+        int32 / uint32 tensors. Returns ``(plane, err)``: the len(subjects) x ceil(len(resources) / 32)
+        int64 device tensor of 2-bit Permissionships (``unpack_cross``'s layout; (s, r) HAS iff its
+        two bits are PERM_HAS), written by the kernels where it lies (Engine.check_cross_ids); only
+        the error count comes back to the host, and a per-item error is ``err`` with no plane."""
+        self.checkOverlap(ctx)
+        try:
+            import torch
+            obj_type, obj_rel = _rel.ParseTypedRelation(permission)
+            stype, srel_name, _ = _rel._cut(subject_type, "#")
+            for what, t in (("resources", resources), ("subjects", subjects)):
+                if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.uint32) or not t.is_cuda:
+                    raise InvalidArgument(f"CheckCrossDevice: the {what} must be a device int32 / uint32 tensor of "
+                                          "interned ids")
+            requirement, revision = _requirement(cs)
+            eng = self.engine
+
+            def run():
+                # resolved per attempt, as CheckCross does
+                rt, st = eng.type_id(obj_type), eng.type_id(stype)
+                perm = eng.relation_id(rt, obj_rel)
+                srel = ELLIPSIS if srel_name in ("", "...") else eng.relation_id(st, srel_name)
+                if TYPE_INVALID in (rt, st) or REL_INVALID in (perm, srel):
+                    raise GckError(GCK_E_NOT_FOUND, "object definition or relation not found")
+                return eng.check_cross_ids((rt, perm, st, srel), subjects, resources, requirement=requirement,
+                                           revision=revision)
+            return retryRetriableErrors(ctx or Background, run), None
+        except Exception as e:  # noqa: BLE001 — Go returns (nil, err)
+            return None, e
+
     # ---- snapshot plumbing (ReadSchema + ExportRelationships at its revision) -------------
     def LoadSnapshot(self, schema: str, revision: int, relationships: Iterable) -> None:
         """Ingest the output of ``ReadSchema`` (client/client.go:416-422) and

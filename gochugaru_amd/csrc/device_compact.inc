@@ -20,6 +20,14 @@
 //
 // A filter request (gck_filter_list_device) adds k_dc_select behind them, for every batch: the
 // survivors of the finished plane, in the caller's order, at their ranks in the request.
+//
+// A cross request (gck_check_bulk_cross_device) in place is cut into full-width tiles — `rows`
+// subjects by all R resources — so a tile's dense words are the run of the caller's plane that begins
+// at its first row, and its padded check order is the request's s * R + r order: the join writes the
+// caller's plane, after k_dc_cross_ids has put the tile's ids into the workspace's id block (or reads
+// the caller's own buffer when that is in block layout already), and k_dc_emit maps a padded index to
+// the request's. Expanded, its chunks of the row-major sequence end inside plane words, so the plane
+// is cleared once and k_dc_cross_pack ORs each result into its word.
 
 // The shapes of a request, by value in the kernarg segment (a uniform or list request: one entry).
 struct DcShapes {
@@ -34,6 +42,10 @@ struct DcExpand {
   uint32_t n, n_shapes;
   uint32_t vary;            // 0: pairs; GCK_VARY_RESOURCE / GCK_VARY_SUBJECT: a list chunk
   uint32_t fixed_id, first_id;
+  // a cross request's chunk (R != 0): `ids` is the whole resource list, `subs` the whole subject list,
+  // and check i of the chunk is check pos + i of the request (pos + n <= S * R < 2^32)
+  const uint32_t* subs;
+  uint32_t R, pos;
 };
 
 // compact_expand on the device: check i of the chunk as a 20-B item. A check whose index byte is
@@ -48,7 +60,11 @@ __global__ void k_dc_expand(DcExpand a, DcShapes t) {
   }
   const gck_uniform h = t.s[s];
   uint32_t res, sub;
-  if (a.vary) {
+  if (a.R) {
+    const uint32_t g = a.pos + i;
+    res = a.ids[g % a.R];
+    sub = a.subs[g / a.R];
+  } else if (a.vary) {
     const uint32_t v = a.ids ? a.ids[i] : a.first_id + i;
     res = a.vary == GCK_VARY_SUBJECT ? a.fixed_id : v;
     sub = a.vary == GCK_VARY_SUBJECT ? v : a.fixed_id;
@@ -89,6 +105,40 @@ __global__ void k_dc_pack(const uint8_t* perm, const int32_t* err, uint32_t n, u
   }
 }
 
+// A cross tile's ids into the workspace's id block, in the layout its join reads (closure.inc
+// cross_ids): the R resource ids at word 0, the tile's `rows` subject ids from word cross_sub_off(R).
+// One thread per id; the host has checked cross_sub_off(R) + rows against the block. `zero`: the
+// request's count word, cleared here when the batch's emit follows this kernel on its stream (null:
+// cleared elsewhere).
+__global__ void k_dc_cross_ids(const uint32_t* resources, uint32_t R, const uint32_t* subjects, uint32_t rows,
+                               uint32_t* block, uint32_t* zero) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t == 0 && zero) *zero = 0u;
+  if (t < R) block[t] = resources[t];
+  else if (t - R < rows) block[cross_sub_off(R) + (t - R)] = subjects[t - R];
+}
+
+// An expanded cross chunk's results into the row-padded plane, and its error bits: check i of the
+// chunk is check g = pos + i of the request, subject g / R against resource g % R. The plane was
+// cleared before the request's first chunk, and a word may be shared by two chunks (a chunk ends
+// inside a row), so each non-zero result is OR-ed into its word. The bitmap is k_dc_pack's: one bit
+// per check of the chunk, a ballot per half-wave, every one of its ceil(n / 32) words written.
+__global__ void k_dc_cross_pack(const uint8_t* perm, const int32_t* err, uint32_t n, uint32_t pos, uint32_t R,
+                                uint32_t stride, unsigned long long* plane, uint32_t* bitmap) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = i < n;
+  const bool bad = in && err[i] != 0;
+  const uint32_t v = in && !bad ? (uint32_t)perm[i] & 3u : 0u;
+  if (v) {
+    const uint32_t g = pos + i, s = g / R, r = g - s * R;  // (g < S * R: s < S, and r / 32 < stride)
+    atomicOr(&plane[(size_t)s * stride + (r >> 5)], (unsigned long long)v << (2u * (r & 31u)));
+  }
+  const unsigned long long bits = __ballot(bad);
+  const uint32_t word = i >> 5, words = (n + 31u) / 32u;
+  if ((threadIdx.x & 31u) == 0u && word < words)
+    bitmap[word] = (threadIdx.x & 32u) ? (uint32_t)(bits >> 32) : (uint32_t)bits;
+}
+
 // The checks the join of an in-place chunk left (its deferred list, n_left entries), answered by the
 // bundle stages into perm / err: an error sets the check's bit of the bitmap, a result is OR-ed
 // into the plane — the join wrote 0 there, and two such checks may share a word.
@@ -109,8 +159,11 @@ __global__ void k_dc_patch(const uint32_t* left, uint32_t n_left, uint32_t n, co
 // The bitmap's `words` words as ascending (index, code) records: one block, a tile of blockDim words
 // at a time. Record r of the request (r counts from *count, the chunks before this one) is written
 // while r < cap; *count becomes the request's count so far. Clears the bitmap.
+// The index of check i of the chunk in its request is pos + i — or, for a cross tile read in place
+// (row_len != 0: the padded checks of a tile row, 32 * ceil(R / 32); pos = row0 * R), pos +
+// (i / row_len) * R + i % row_len: below S * R < 2^32, since a padding lane sets no bit.
 __global__ void k_dc_emit(uint32_t* bitmap, uint32_t words, const int32_t* err, uint32_t pos, gck_item_error* out,
-                          uint32_t cap, uint32_t* count) {
+                          uint32_t cap, uint32_t* count, uint32_t row_len = 0u, uint32_t R = 0u) {
   __shared__ uint32_t wave_tot[kWaves];
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t base = *count;
@@ -141,7 +194,8 @@ __global__ void k_dc_emit(uint32_t* bitmap, uint32_t words, const int32_t* err, 
       const uint32_t b = (uint32_t)__ffs((int)word) - 1u;
       word &= word - 1u;
       const uint32_t i = t * 32u + b;
-      if (rank < cap) out[rank] = gck_item_error{pos + i, err[i]};
+      const uint32_t at = row_len ? (i / row_len) * R + i % row_len : i;
+      if (rank < cap) out[rank] = gck_item_error{pos + at, err[i]};
       ++rank;
     }
     run += tot;
@@ -229,7 +283,12 @@ static void dc_expand(Workspace& w, const CompactReq& q, size_t pos, uint32_t le
   DcExpand a{};
   DcShapes t{};
   std::memcpy(t.s, q.shapes, (size_t)q.n_shapes * sizeof(gck_uniform));
-  a.ids = q.list() ? (q.ids ? q.ids + pos : nullptr) : q.pairs + 2 * pos;
+  a.ids = q.cross() ? q.resources : q.list() ? (q.ids ? q.ids + pos : nullptr) : q.pairs + 2 * pos;
+  if (q.cross()) {
+    a.subs = q.subjects;
+    a.R = (uint32_t)q.R;
+    a.pos = (uint32_t)pos;
+  }
   a.shape_of = q.shape_of ? q.shape_of + pos : nullptr;
   a.items = w.d_items;
   a.bad = w.dc_aux + 1;
@@ -271,14 +330,20 @@ static void device_collect(Engine& e, Workspace& w) {
       HIP_OK(hipStreamSynchronize(st));
       if (bad != 0xFFFFFFFFu) shape_index_error(c.pos + bad, dc_shape_byte(c, bad), c.n_shapes);
     }
-    hipLaunchKernelGGL(k_dc_pack, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, w.d_perm, w.d_err, n, c.packed,
-                       w.dc_bitmap);
+    if (c.cross)  // (c.out: the request's whole plane, cleared before its first chunk)
+      hipLaunchKernelGGL(k_dc_cross_pack, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, w.d_perm, w.d_err, n,
+                         (uint32_t)c.pos, (uint32_t)c.R, (uint32_t)((c.R + 31u) / 32u), c.out, w.dc_bitmap);
+    else
+      hipLaunchKernelGGL(k_dc_pack, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, w.d_perm, w.d_err, n, c.packed,
+                         w.dc_bitmap);
     HIP_OK(hipGetLastError());
     launched = true;
   }
   if (launched) {
+    // (a cross tile in place: c.pos is its first row's first check, and a padded index is mapped)
+    const uint32_t row_len = c.grid() ? ((c.cols + 31u) / 32u) * 32u : 0u;
     hipLaunchKernelGGL(k_dc_emit, dim3(1), dim3(kBlock), 0, st, w.dc_bitmap, words, w.d_err, (uint32_t)c.pos, c.errs, cap,
-                       c.d_cnt);
+                       c.d_cnt, row_len, (uint32_t)c.R);
     HIP_OK(hipGetLastError());
     if (c.d_cnt == w.dc_aux) w.dc_cnt_dirty = true;
   }

@@ -33,6 +33,9 @@ using submit_list_device_fn = int (*)(gck_engine*, const gck_consistency*, const
                                       const uint32_t*, uint32_t, size_t, const char* const*, const size_t*, size_t,
                                       int64_t, uint64_t*, gck_item_error*, size_t, uint32_t*, uint32_t, void*,
                                       gck_batch**);
+using submit_cross_device_fn = int (*)(gck_engine*, const gck_consistency*, const gck_uniform*, const uint32_t*, size_t,
+                                       const uint32_t*, size_t, const char* const*, const size_t*, size_t, int64_t,
+                                       uint64_t*, gck_item_error*, size_t, uint32_t*, uint32_t, void*, gck_batch**);
 using submit_filter_device_fn = int (*)(gck_engine*, const gck_consistency*, const gck_uniform*, uint32_t, uint32_t,
                                         const uint32_t*, uint32_t, size_t, const char* const*, const size_t*, size_t,
                                         int64_t, const gck_select*, uint64_t*, gck_item_error*, size_t, uint32_t*,
@@ -203,6 +206,22 @@ int gckd_run_list_device(submit_list_device_fn submit, wait_fn wait, gck_engine*
                   nullptr, nullptr, 0, now_us, reinterpret_cast<uint64_t*>(packed[k]),
                   reinterpret_cast<gck_item_error*>(errs[k]), err_cap, reinterpret_cast<uint32_t*>(n_errs[k]), flags,
                   reinterpret_cast<void*>(streams[k % depth]), b);
+  });
+}
+
+// ... and the cross loop (gck_check_submit_cross_device): subjects[k] and resources[k] are device id
+// lists (one buffer in block layout, or two), packed[k] the row-padded plane in device memory.
+int gckd_run_cross_device(submit_cross_device_fn submit, wait_fn wait, gck_engine* e, const gck_consistency* cs,
+                          size_t n_batches, const gck_uniform* hdrs, const uint64_t* subjects, const uint64_t* n_subjects,
+                          const uint64_t* resources, const uint64_t* n_resources, const uint64_t* packed,
+                          const uint64_t* errs, size_t err_cap, const uint64_t* n_errs, uint32_t depth,
+                          const uint64_t* streams, uint32_t flags, int64_t now_us, double* seconds) {
+  if (depth == 0) depth = 1;
+  return run_loop(n_batches, depth, wait, e, seconds, [&](size_t k, gck_batch** b) {
+    return submit(e, cs, hdrs + k, reinterpret_cast<const uint32_t*>(subjects[k]), (size_t)n_subjects[k],
+                  reinterpret_cast<const uint32_t*>(resources[k]), (size_t)n_resources[k], nullptr, nullptr, 0, now_us,
+                  reinterpret_cast<uint64_t*>(packed[k]), reinterpret_cast<gck_item_error*>(errs[k]), err_cap,
+                  reinterpret_cast<uint32_t*>(n_errs[k]), flags, reinterpret_cast<void*>(streams[k % depth]), b);
   });
 }
 

@@ -235,6 +235,7 @@ struct CompactRun {
   uint32_t* d_cnt = nullptr;
   bool zero_cnt = false;  // ... which this batch still has to clear (the join's block 0 does: dc_steal_clear; else a memset)
   bool cnt_memset = false;  // ... cleared by a memset on the batch's stream
+  bool no_aql = false;      // an engine-stream batch whose join must follow a kernel on its stream: the HIP launch, not the HSA queue
   // a filter request's chunk (CompactReq::sel): the survivors of the finished plane go to the caller's
   // arrays (k_dc_select). sel_ids / sel_first: the chunk's varying ids (a device list, or null and the
   // chunk's first id); sel_prev: the word that holds the request's count before this chunk (null: the
@@ -299,6 +300,7 @@ struct Workspace {
   uint32_t* dc_aux = nullptr;     // ... [0] the errors so far of a request that gives no count word, [1] an expanded chunk's bad index,
                                   // [2], [3] a filter request's survivors so far, by chunk parity (k_dc_select)
   unsigned long long* dc_plane = nullptr;  // ... the plane of a filter request that gives none (max_batch / 32 words)
+  uint32_t* dc_ids = nullptr;     // ... the id block a cross device tile's join reads (kAqlIdsBytes; written by k_dc_cross_ids)
   bool dc_cnt_dirty = false;      // ... dc_aux[0] may be non-zero
   uint32_t pair_dirty = 0;        // one of the two alternating deferred-list counters (aql_summaries) may be non-zero:
                                   // the next so many dispatched joins must clear the other one themselves
@@ -2095,6 +2097,7 @@ static Workspace* create_workspace(Engine& e) {
     w->dc_bitmap = dalloc<uint32_t>(w->allocs, w->max_batch / 32 + 1, &w->bytes);
     w->dc_aux = dalloc<uint32_t>(w->allocs, 4, &w->bytes);
     w->dc_plane = dalloc<unsigned long long>(w->allocs, w->max_batch / 32 + 1, &w->bytes);
+    w->dc_ids = dalloc<uint32_t>(w->allocs, kAqlIdsBytes / 4, &w->bytes);
     HIP_OK(hipMemsetAsync(w->dc_bitmap, 0, (w->max_batch / 32 + 1) * sizeof(uint32_t), nullptr));
     HIP_OK(hipMemsetAsync(w->dc_aux, 0, 4 * sizeof(uint32_t), nullptr));
     w->d_ctx = reinterpret_cast<Ctx*>(dalloc<unsigned char>(w->allocs, sizeof(Ctx), &w->bytes));
@@ -2760,7 +2763,7 @@ static Route stage_a_route(Engine& e, Workspace& w) {
   // kernarg block and which clears the checks' caveat flags itself — nothing on the HIP stream)
   r.aql_ok = w.b_own_stream && !r.host_out && !r.chained && r.ctr_clean && e.aql && w.aql_kernarg &&
              (!w.cav_on || (r.lj && ds.lj.cav)) && (r.lj || r.cj) && ((aql_timed && e.aql->tick_hz) || !r.timed) &&
-             aql_build_done(e);
+             !w.cb.no_aql && aql_build_done(e);
   // (GCK_DEBUG_HIP_SELFPUB: an engine-stream batch launched through HIP publishes itself from its
   // last block as an AQL-dispatched one does — the dispatch-span attribution of tools/aql_span.sh;
   // its results are not written back before the publication, so only device readers may use them)
@@ -3740,6 +3743,19 @@ static bool cross_plan(const Engine& e, const Workspace* w0, const Workspace* w1
   q.tile_cols = cols;
   return true;
 }
+// ... of a cross request over device buffers: the same condition without the host id block, and a
+// full-width tile from the device tiling rule.
+static bool cross_plan_device(const Engine& e, const Workspace* w0, const Workspace* w1, const CavCall& cav,
+                              CompactReq& q) {
+  q.tile_rows = q.tile_cols = 0;
+  for (const Workspace* w : {w0, w1})
+    if (w && !(zero_copy_with(e, *w, cav.n_ctx > 0) && w->dc_ids)) return false;
+  uint32_t rows = 0;
+  if (!gck_cross_tile_device(q.S, q.R, w0->max_batch, &rows)) return false;
+  q.tile_rows = rows;
+  q.tile_cols = (uint32_t)q.R;
+  return true;
+}
 static size_t cross_tiles(const CompactReq& q) {
   return ((q.S + q.tile_rows - 1) / q.tile_rows) * ((q.R + q.tile_cols - 1) / q.tile_cols);
 }
@@ -3781,6 +3797,46 @@ static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t 
     c.ss = (uint32_t)h.subject_type | (uint32_t)h.subject_relation << 16;
     c.ctx = h.context_slot;
   };
+  if (c.cross && q.device && q.tile_rows) {
+    // a full-width tile (band `pos`) of a cross request over device buffers: its words are the run of
+    // the caller's plane from its first row, which the join writes; its ids go into the workspace's
+    // device id block by one kernel — unless the request is one tile whose lists lie in block layout
+    // already, which the join reads where they are
+    const size_t wpr = (q.R + 31u) / 32u;
+    c.row0 = (uint32_t)pos * q.tile_rows;
+    c.rows = (uint32_t)std::min<size_t>(q.tile_rows, q.S - c.row0);
+    c.cols = (uint32_t)q.R;
+    c.pos = (size_t)c.row0 * q.R;  // (the request index of the tile's first check: k_dc_emit)
+    const uint32_t padded = c.rows * (uint32_t)wpr * 32u;
+    if (padded > w.max_batch || cross_sub_off(c.cols) + c.rows > kAqlIdsBytes / 4)
+      throw Error(GCK_E_DEVICE, "engine invariant violated: cross device tile above max_batch or the id block");
+    c.pad = padded - c.rows * c.cols;
+    c.mode = CompactRun::kInPlace;
+    c.out = reinterpret_cast<unsigned long long*>(q.packed) + (size_t)c.row0 * wpr;
+    c.packed = c.out;
+    header();
+    const bool own = q.engine_stream;
+    const hipStream_t st = own ? w.stream : (hipStream_t)q.stream;
+    if (c.rows == q.S && q.subjects == q.resources + cross_sub_off(c.cols)) {
+      c.pairs = q.resources;
+    } else {
+      // the join follows the gather on st: an engine-stream batch's too, through the HIP launch and
+      // not the engine's HSA queue, which does not see the stream's order — published by k_publish
+      // after its end, no host wait in between (waiting for the gather and then dispatching measured
+      // 2.5 G checks/s against 6.8-7.4 G: DESIGN 3.6). The gather's thread 0 clears the count word
+      uint32_t* zero = c.zero_cnt ? c.d_cnt : nullptr;
+      hipLaunchKernelGGL(k_dc_cross_ids, dim3((c.cols + c.rows + kBlock - 1) / kBlock), dim3(kBlock), 0, st, q.resources,
+                         c.cols, q.subjects + c.row0, c.rows, w.dc_ids, zero);
+      HIP_OK(hipGetLastError());
+      c.pairs = w.dc_ids;
+      c.zero_cnt = false;
+      c.no_aql = own;
+    }
+    submit_batch(e, w, w.d_items, padded, now_us, w.d_perm, w.d_err, st,
+                 own ? BatchMem::kEngineStream : BatchMem::kCallerStream, c);
+    e.dev_in_place.fetch_add(1, std::memory_order_relaxed);
+    return;
+  }
   if (c.cross && q.tile_rows) {
     // the tile's ids into the workspace's id block; its join writes the tile's words densely into
     // the pinned result staging (wave w word w, as a uniform batch's)
@@ -3944,8 +4000,12 @@ void device_submit_compact(Engine& e, Workspace* w, const CompactReq& req, int64
   CompactReq q = req;
   // (a submitted cross request is one tile by the tiling rule — checked by the entry point — so
   // in place it is tile 0 and expanded it is one chunk: S * R <= its padded size <= max_batch)
-  if (q.cross()) cross_plan(e, w, nullptr, cav, q);
+  if (q.cross() && q.device) cross_plan_device(e, w, nullptr, cav, q);
+  else if (q.cross()) cross_plan(e, w, nullptr, cav, q);
   const hipStream_t st = (q.device && !q.engine_stream) ? (hipStream_t)q.stream : w->stream;
+  // (an expanded cross chunk ORs its results into the plane: cleared first, on the batch's stream)
+  if (q.cross() && q.device && !q.tile_rows)
+    HIP_OK(hipMemsetAsync(q.packed, 0, q.S * ((q.R + 31u) / 32u) * sizeof(uint64_t), st));
   q.zero_cnt = q.device && q.d_n_errs;  // (cleared by the batch: its dispatched join, or the memset below)
   stage_caveats(*w, std::move(cav), st);
   if (now_us == 0) now_us = wall_now_us();
@@ -3992,6 +4052,23 @@ void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const Compact
                           const CavCall& cav) {
   HIP_OK(hipSetDevice(e.device));
   if (now_us == 0) now_us = wall_now_us();
+  if (req.cross() && req.device) {
+    // in place: one batch per full-width band, each writing its rows of the caller's plane; else
+    // row-major chunks of whole words' worth of checks, expanded on the device into a plane cleared
+    // here. The bands' and the chunks' error lists accumulate in order, as compact_chunks' do
+    CompactReq q = req;
+    const bool tiled = cross_plan_device(e, w0, w1, cav, q);
+    const size_t mb = w0->max_batch >= 32 ? (w0->max_batch & ~(size_t)31) : w0->max_batch;
+    HIP_OK(hipStreamSynchronize((hipStream_t)q.stream));
+    uint32_t* d_cnt = dc_count_begin(*w0, q, w0->stream, true);
+    if (!tiled) HIP_OK(hipMemsetAsync(q.packed, 0, q.S * ((q.R + 31u) / 32u) * sizeof(uint64_t), w0->stream));
+    HIP_OK(hipStreamSynchronize(w0->stream));
+    run_chunks(
+        e, w0, w1, tiled ? cross_tiles(q) : q.n, tiled ? 1 : mb, cav,
+        [&](Workspace& w, size_t pos, uint32_t len) { submit_compact(e, w, q, pos, len, now_us, d_cnt); },
+        [&](Workspace& w) { device_collect(e, w); });
+    return;
+  }
   if (req.cross()) {
     // in place: one batch per tile; else chunks of max_batch checks of the row-major sequence,
     // expanded to items (a chunk need not end on a word: uniform_collect places each result)

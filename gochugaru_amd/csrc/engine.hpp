@@ -438,10 +438,12 @@ struct CompactReq {
   uint32_t fixed_id = 0, first_id = 0;
   const uint32_t* ids = nullptr;
   bool list() const { return vary != 0; }
-  // a request over device buffers (gck_check_bulk_uniform_device ...; never a cross request):
-  // shape_of, pairs, ids, packed and errs are device memory, n_errs is null and the count goes to
-  // *d_n_errs (device memory; may be null). The synchronous form completes `stream` and runs on the
-  // workspaces' streams; a submitted batch runs on the workspace's stream (engine_stream) or on `stream`
+  // a request over device buffers (gck_check_bulk_uniform_device ..., gck_check_bulk_cross_device):
+  // shape_of, pairs, ids, subjects, resources, packed and errs are device memory — no host path may
+  // read them — n_errs is null and the count goes to *d_n_errs (device memory; may be null). The
+  // synchronous form completes `stream` and runs on the workspaces' streams; a submitted batch runs on
+  // the workspace's stream (engine_stream) or on `stream`. A cross request over device buffers is cut
+  // into full-width tiles (tile_cols = R, tile_rows from gck_cross_tile_device), one band each
   bool device = false;
   bool engine_stream = true;
   void* stream = nullptr;
@@ -455,7 +457,7 @@ struct CompactReq {
 // *d_n_errs = 0 for an empty device request (synchronous on `stream`; a null pointer: nothing).
 void device_zero_count(Engine& e, uint32_t* d_n_errs, void* stream);
 // Synchronous: chunks of max_batch & ~31 checks over w0 and w1 (as device_check_host); a cross
-// request in place: its tiles, one batch each.
+// request in place: its tiles, one batch each (over device buffers: its full-width bands).
 void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const CompactReq& req, int64_t now_us,
                           const CavCall& cav);
 void device_submit_compact(Engine& e, Workspace* w, const CompactReq& req, int64_t now_us, CavCall cav);

@@ -1498,6 +1498,80 @@ int gck_check_submit_list_device(gck_engine* ge, const gck_consistency* cs, cons
   });
 }
 
+// ---- cross requests over device buffers (include/gck.h gck_check_bulk_cross_device) -----------
+
+int gck_cross_tile_device(size_t S, size_t R, size_t max_batch, uint32_t* rows) {
+  if (rows) *rows = 0;
+  if (S == 0 || R == 0 || R >= GCK_CROSS_IDS) return 0;
+  const size_t padded = 32 * ((R + 31) / 32);  // a row's checks, padding included
+  if (padded > max_batch) return 0;
+  const size_t r = std::min({S, max_batch / padded, (size_t)GCK_CROSS_IDS - R});
+  if (r == 0) return 0;
+  // gck_cross_tile's thin rule: more checks than the tile, and the tile is small
+  if (S > r && r * R < max_batch / 4) return 0;
+  if (rows) *rows = (uint32_t)r;
+  return 1;
+}
+
+// The host cross call's argument checks over the device pointers (none reads a buffer), then the
+// device forms' own.
+static CompactReq cross_device_request(const gck_uniform* hdr, const uint32_t* d_subjects, size_t S,
+                                       const uint32_t* d_resources, size_t R, size_t n_contexts, uint64_t* d_out_packed,
+                                       gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, void* stream,
+                                       bool engine_stream) {
+  const auto aligned = [](const void* p) { return ((uintptr_t)p & 3u) == 0; };
+  const CompactReq q =
+      cross_request(hdr, d_subjects, S, d_resources, R, n_contexts, d_out_packed, d_out_errs, err_cap, nullptr);
+  REQUIRE(aligned(d_subjects), GCK_E_INVALID_ARGUMENT, "device request: d_subjects is not 4-byte aligned");
+  REQUIRE(aligned(d_resources), GCK_E_INVALID_ARGUMENT, "device request: d_resources is not 4-byte aligned");
+  return device_request(q, d_out_errs, d_out_n_errs, stream, engine_stream);
+}
+
+int gck_check_bulk_cross_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr,
+                                const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                                size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                                size_t n_contexts, int64_t now_us, uint64_t* d_out_packed, gck_item_error* d_out_errs,
+                                size_t err_cap, uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision) {
+  return guard([&] {
+    Engine& e = need(ge);
+    const CompactReq req = cross_device_request(hdr, d_subjects, n_subjects, d_resources, n_resources, n_contexts,
+                                                d_out_packed, d_out_errs, err_cap, d_out_n_errs, stream, true);
+    const CallCtx c{cs, contexts, context_lens, n_contexts};
+    if (req.n == 0) return check_device_sync(e, c, req, now_us, out_revision);
+    // two workspaces when the request is more than one batch either way: more than one tile, or
+    // (expanded) more than a chunk
+    uint32_t rows = 0;
+    const size_t mb = max_batch_of(e);
+    const size_t one = gck_cross_tile_device(n_subjects, n_resources, mb, &rows) ? (size_t)rows * n_resources
+                                                                                 : (mb & ~(size_t)31);
+    check_sync(e, c, req.n, one, out_revision,
+               [&](Workspace* w0, Workspace* w1, const CavCall& cav) { device_check_compact(e, w0, w1, req, now_us, cav); });
+  });
+}
+
+int gck_check_submit_cross_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr,
+                                  const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                                  size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                                  size_t n_contexts, int64_t now_us, uint64_t* d_out_packed,
+                                  gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, uint32_t flags,
+                                  void* stream, gck_batch** out) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    check_submit_flags(flags);
+    const CompactReq req =
+        cross_device_request(hdr, d_subjects, n_subjects, d_resources, n_resources, n_contexts, d_out_packed, d_out_errs,
+                             err_cap, d_out_n_errs, stream, (flags & GCK_SUBMIT_ENGINE_STREAM) != 0);
+    uint32_t rows = 0;
+    REQUIRE(req.n == 0 || (gck_cross_tile_device(n_subjects, n_resources, max_batch_of(e), &rows) && rows == n_subjects),
+            GCK_E_INVALID_ARGUMENT,
+            "submitted cross device request of " + std::to_string(n_subjects) + " x " + std::to_string(n_resources) +
+                " is not one tile (gck_cross_tile_device)");
+    *out = submit_device(e, {cs, contexts, context_lens, n_contexts}, req, now_us);
+  });
+}
+
 // ---- filter requests (include/gck.h gck_filter_list_device) -----------------------------------
 
 // A filter request's selection against the call, before anything is launched; then the list device

@@ -190,6 +190,34 @@ def cross_tile(S: int, R: int, max_batch: int = 65536) -> Optional[Tuple[int, in
     return (rows.value, cols.value) if ok else None
 
 
+def cross_tile_device(S: int, R: int, max_batch: int = 65536) -> int:
+    """gck_cross_tile_device: the subjects of a full-width tile (rows x all R resources) a cross
+    request over device buffers is cut into in place, or 0 when the request is expanded to items."""
+    rows = C.c_uint32(0)
+    ok = load_library().gck_cross_tile_device(S, R, max_batch, C.byref(rows))
+    return rows.value if ok else 0
+
+
+def cross_sub_off(R: int) -> int:
+    """The word at which a cross id block's subject ids begin: R rounded up to a multiple of four."""
+    return (R + 3) & ~3
+
+
+def cross_id_block(subjects, resources):
+    """One tensor in the block layout a cross device request of one tile is read from in place — the
+    R resource ids, padding (0) to a multiple of four words, then the S subject ids — and the two
+    views into it: (block, subjects_view, resources_view). The views are what check_cross_device /
+    submit_cross_device take as d_subjects / d_resources. Tensors of any device, int32 or uint32."""
+    import torch
+    resources = resources.reshape(-1)
+    subjects = subjects.reshape(-1).to(device=resources.device, dtype=resources.dtype)
+    R, S, off = resources.numel(), subjects.numel(), cross_sub_off(resources.numel())
+    block = torch.zeros(off + S, dtype=resources.dtype, device=resources.device)
+    block[:R] = resources
+    block[off:] = subjects
+    return block, block[off:off + S], block[:R]
+
+
 MAX_SHAPES = 64  # GCK_MAX_SHAPES
 _SHAPE_FIELDS = ("resource_type", "permission", "subject_type", "subject_relation", "context_slot")
 
@@ -340,6 +368,13 @@ _SIGS = {
                                                C.POINTER(C.c_size_t), C.c_size_t, C.c_int64, _P, _P, C.c_size_t, _P,
                                                C.c_uint32, _P, C.POINTER(_P)]),
     "gck_device_compact_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "gck_check_bulk_cross_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), _P, C.c_size_t, _P,
+                                              C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t,
+                                              C.c_int64, _P, _P, C.c_size_t, _P, _P, C.POINTER(C.c_uint64)]),
+    "gck_check_submit_cross_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), _P, C.c_size_t, _P,
+                                                C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t,
+                                                C.c_int64, _P, _P, C.c_size_t, _P, C.c_uint32, _P, C.POINTER(_P)]),
+    "gck_cross_tile_device": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32)]),
     "gck_filter_list_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), C.c_uint32, C.c_uint32, _P,
                                          C.c_uint32, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
                                          C.c_size_t, C.c_int64, C.POINTER(Select), _P, _P, C.c_size_t, _P, _P,
@@ -470,6 +505,11 @@ def _driver():
                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int64,
                                            C.POINTER(C.c_double)]
+        d.gckd_run_cross_device.restype = C.c_int
+        d.gckd_run_cross_device.argtypes = [C.c_void_p, C.c_void_p, _P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int64,
+                                            C.POINTER(C.c_double)]
         d.gckd_run_filter_device.restype = C.c_int
         d.gckd_run_filter_device.argtypes = [C.c_void_p, C.c_void_p, _P, C.c_void_p, C.c_size_t, C.c_void_p,
                                              C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -1147,6 +1187,79 @@ class Engine:
         return PreparedListDevice(self, headers, fixed, vary, ids, first, ns, packed, errs, err_cap, depth, n_errs,
                                   streams, engine_streams, now_us)
 
+    # ---- cross requests over device buffers (gck_check_bulk_cross_device): d_subjects (S) and
+    # d_resources (R) u32 id lists, d_out_packed the row-padded plane of S * ceil(R / 32) u64. The
+    # lists are read where they are (never copied): unchanged until the call or the wait returns.
+    def check_cross_device(self, header, d_subjects: int, n_subjects: int, d_resources: int, n_resources: int,
+                           d_out_packed: int, d_out_errs: int = 0, err_cap: int = 0, d_out_n_errs: int = 0,
+                           stream: Optional[int] = None, requirement: int = CONSISTENCY_MIN_LATENCY,
+                           revision: int = 0, now_us: int = 0, contexts: Optional[Sequence] = None) -> int:
+        """gck_check_bulk_cross_device: check_cross over two device id lists; the plane and the error
+        records (index = s * R + r) on the device. Returns the evaluated revision."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        rev = C.c_uint64(0)
+        _check(self._lib.gck_check_bulk_cross_device(self._h, C.byref(cs), C.byref(hdr), d_subjects or None,
+                                                     n_subjects, d_resources or None, n_resources, *tail, stream,
+                                                     C.byref(rev)))
+        return rev.value
+
+    def submit_cross_device(self, header, d_subjects: int, n_subjects: int, d_resources: int, n_resources: int,
+                            d_out_packed: int, d_out_errs: int = 0, err_cap: int = 0, d_out_n_errs: int = 0,
+                            stream: Optional[int] = None, engine_stream: bool = False,
+                            requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                            contexts: Optional[Sequence] = None) -> "DeviceCompactBatch":
+        """gck_check_submit_cross_device (one device tile: cross_tile_device(S, R, max_batch) == S): as
+        submit_uniform_device."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        b = DeviceCompactBatch(self, hdr)
+        _check(self._lib.gck_check_submit_cross_device(self._h, C.byref(cs), C.byref(hdr), d_subjects or None,
+                                                       n_subjects, d_resources or None, n_resources, *tail,
+                                                       SUBMIT_ENGINE_STREAM if engine_stream else 0, stream,
+                                                       C.byref(b._h)))
+        return b
+
+    def prepare_cross_device(self, headers, subjects, n_subjects, resources, n_resources, packed, errs, err_cap: int,
+                             depth: int, n_errs=None, streams=None, engine_streams: bool = True,
+                             now_us: int = 0) -> "PreparedCrossDevice":
+        """The compiled loop over cross device requests (gckd_run_cross_device): as prepare_cross with
+        device pointers; n_errs[k] is request k's device count word (None: none)."""
+        return PreparedCrossDevice(self, headers, subjects, n_subjects, resources, n_resources, packed, errs, err_cap,
+                                   depth, n_errs, streams, engine_streams, now_us)
+
+    def check_cross_ids(self, header, subjects, resources, requirement: int = CONSISTENCY_MIN_LATENCY,
+                        revision: int = 0, now_us: int = 0, contexts: Optional[Sequence] = None):
+        """The permission plane of `subjects` x `resources` — device int32 / uint32 tensors of ids —
+        as an int64 [S, ceil(R / 32)] device tensor (2 bits per check, unpack_cross's layout). Runs
+        check_cross_device on the current stream, reads back only the error count — the call's only
+        copy to the host — and raises GckError, with the lookups' message, when it is not 0."""
+        import torch
+        for name, t in (("subjects", subjects), ("resources", resources)):
+            if t.dtype not in (torch.int32, torch.uint32) or not t.is_cuda:
+                raise GckError(GCK_E_INVALID_ARGUMENT, f"check_cross_ids: {name} must be a device int32 / uint32 tensor")
+        if subjects.device != resources.device:
+            raise GckError(GCK_E_INVALID_ARGUMENT, "check_cross_ids: the two lists are on different devices")
+        subjects, resources = subjects.contiguous().reshape(-1), resources.contiguous().reshape(-1)
+        S, R, dev = subjects.numel(), resources.numel(), subjects.device
+        with torch.cuda.device(dev):
+            plane = torch.empty((S, (R + 31) // 32), dtype=torch.int64, device=dev)
+            count = torch.empty(1, dtype=torch.int32, device=dev)
+            err = torch.empty(2, dtype=torch.int32, device=dev)  # the first error record
+            self.check_cross_device(header, subjects.data_ptr() if S * R else 0, S, resources.data_ptr() if S * R else 0,
+                                    R, plane.data_ptr() if S * R else 0, d_out_errs=err.data_ptr(), err_cap=1,
+                                    d_out_n_errs=count.data_ptr(),
+                                    stream=torch.cuda.current_stream(dev).cuda_stream, requirement=requirement,
+                                    revision=revision, now_us=now_us, contexts=contexts)
+            if int(count.item()) & 0xFFFFFFFF:
+                code = int(err[1].item())
+                raise GckError(GCK_E_INVALID_ARGUMENT,
+                               ITEM_ERROR_MESSAGES[ITEM_ERR_MAX_DEPTH] if code == ITEM_ERR_MAX_DEPTH
+                               else f"lookup failed: per-item error {code}")
+        return plane
+
     # ---- filter requests (gck_filter_list_device): the list device request, its survivors compacted
     # on the device. d_out_n: one u32 (required); d_out_ids / d_out_pos (u32) and d_out_perm (u8): `cap`
     # entries each, 0: not wanted; d_out_packed may be 0 (the plane stays in the engine).
@@ -1670,6 +1783,19 @@ class PreparedListDevice(_Prepared):
         self._args = (hdrs, u32(fixed), vary, arr(ids), u32(first), arr(ns), arr(packed), arr(errs), err_cap,
                       arr(n_errs or [0] * len(ns)), depth, arr(streams or [0]),
                       SUBMIT_ENGINE_STREAM if engine_streams else 0, now_us)
+
+
+class PreparedCrossDevice(_Prepared):
+    """A compiled submit/wait loop over cross device requests (Engine.prepare_cross_device)."""
+
+    def __init__(self, engine, headers, subjects, n_subjects, resources, n_resources, packed, errs, err_cap, depth,
+                 n_errs, streams, engine_streams, now_us):
+        super().__init__(engine, "gckd_run_cross_device", "gck_check_submit_cross_device", len(subjects), depth)
+        arr = self._arr
+        hdrs = (Uniform * max(1, len(headers)))(*[_header(h) for h in headers])
+        self._args = (hdrs, arr(subjects), arr(n_subjects), arr(resources), arr(n_resources), arr(packed),
+                      arr(errs or [0] * len(subjects)), err_cap, arr(n_errs or [0] * len(subjects)), depth,
+                      arr(streams or [0]), SUBMIT_ENGINE_STREAM if engine_streams else 0, now_us)
 
 
 class PreparedFilterDevice(_Prepared):

@@ -618,8 +618,52 @@ int gck_check_submit_list_device(gck_engine* e, const gck_consistency* cs, const
 /* Since the engine was created: out[0] = chunks (of max_batch checks) of device requests whose join
  * read the request and wrote the words in place in device memory, out[1] = chunks expanded to items
  * on the device (check contexts, profiling, no one-round join, GCK_AQL=0, GCK_FLAG_NO_BUNDLE).
- * gck_shaped_stats, gck_list_stats and gck_cross_stats do not count device requests. */
+ * gck_shaped_stats, gck_list_stats and gck_cross_stats do not count device requests. A cross device
+ * request (below) counts here too: out[0] its tiles read in place, out[1] its chunks expanded. */
 int gck_device_compact_stats(gck_engine* e, uint64_t out[2]);
+
+/* ---- cross requests over device buffers (ABI 13, additive) ---------------------------
+ * gck_check_bulk_cross / gck_check_submit_cross for id lists that live in device memory — a batch of
+ * user ids and a page of candidate ids as two tensors: d_subjects, d_resources, d_out_packed,
+ * d_out_errs and d_out_n_errs (a uint32_t) are device memory on the engine's device. Check (s, r), the
+ * row-padded plane (stride = ceil(R / 32) words, padding bits 0, every one of the S * stride words
+ * written, an errored check 0) and the records (index = s * R + r, ascending) are the host cross
+ * call's; the err_cap / *d_out_n_errs protocol, stream ordering, GCK_SUBMIT_ENGINE_STREAM,
+ * consistency, the evaluated revision and buffer lifetimes are the device compact calls' above. Unlike
+ * the host cross call the two lists are NOT copied: they stay valid and unchanged until the
+ * synchronous call or the wait returns.
+ * In place the request is cut into full-width tiles, gck_cross_tile_device(S, R, max_batch) subjects
+ * by all R resources, band after band from the top: a tile's words are a contiguous run of the
+ * caller's plane, which the join writes directly, after one small kernel has put the tile's ids into
+ * the workspace's id block. A layout a caller may use to spare even that: one buffer of the R resource
+ * ids, padding to a multiple of four words, then the S subject ids (d_subjects == d_resources +
+ * ((R + 3) & ~3), in words) — when the request is one tile the join reads that buffer where it is.
+ * Otherwise (check contexts, profiling, no one-round join, GCK_AQL=0, GCK_FLAG_NO_BUNDLE, or a 0 from
+ * the tiling rule — R >= GCK_CROSS_IDS among them) the request is expanded to items on the device in
+ * row-major chunks of max_batch checks.
+ * GCK_E_INVALID_ARGUMENT, nothing launched, for everything the host cross call refuses (`reserved`,
+ * the context slot, S * R >= 2^32, null lists with S * R > 0), a d_out_packed that is not 8-byte
+ * aligned, and a d_subjects, d_resources, d_out_errs or d_out_n_errs that is not 4-byte aligned.
+ * S == 0 or R == 0 succeeds and writes only the count word. The submit form takes a request that is
+ * one device tile (gck_cross_tile_device returns S), else GCK_E_INVALID_ARGUMENT.
+ * gck_device_compact_stats counts these requests' tiles and chunks; gck_cross_stats does not. */
+int gck_check_bulk_cross_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr,
+                                const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                                size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                                size_t n_contexts, int64_t now_us, uint64_t* d_out_packed, gck_item_error* d_out_errs,
+                                size_t err_cap, uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision);
+int gck_check_submit_cross_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr,
+                                  const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                                  size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                                  size_t n_contexts, int64_t now_us, uint64_t* d_out_packed,
+                                  gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, uint32_t flags,
+                                  void* stream, gck_batch** out);
+/* The device tiling rule (pure, as gck_cross_tile): *rows = the subjects of a full-width tile,
+ * min(S, max_batch / (32 * ceil(R / 32)), GCK_CROSS_IDS - R), and 1 returned; or 0 (*rows = 0: the
+ * request is expanded) when that is 0, R >= GCK_CROSS_IDS, 32 * ceil(R / 32) > max_batch, or the
+ * request has more checks than the tile and the tile holds fewer than max_batch / 4 (gck_cross_tile's
+ * thin rule). */
+int gck_cross_tile_device(size_t n_subjects, size_t n_resources, size_t max_batch, uint32_t* rows);
 
 /* ---- filter requests (ABI 13, additive) ----------------------------------------------
  * gck_check_bulk_list_device / gck_check_submit_list_device with the last step done on the device
