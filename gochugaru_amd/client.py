@@ -504,6 +504,41 @@ class Client:
         except Exception as e:  # noqa: BLE001 — Go returns (nil, err)
             return None, e
 
+    def FilterCrossDevice(self, ctx: Optional[Context], cs: Optional[Strategy], permission: str, resources,
+                          subject_type: str, subjects, limit: int = 0):
+        """``CheckCrossDevice`` answered as what the caller asked: for each of ``subjects``, which of
+        ``resources`` it may see (HAS or CONDITIONAL) — with ``limit``, the first ``limit`` of them in
+        the page's order. Returns ``((row_off, ids), err)``: ``ids[row_off[s]:row_off[s + 1]]`` are
+        subject s's permitted resource ids, both device tensors, selected and compacted by kernels over
+        the finished plane (Engine.filter_cross_ids); only two count words come back to the host, and
+        a per-item error is ``err``. Parsing and error mapping are ``CheckCrossDevice``'s."""
+        self.checkOverlap(ctx)
+        try:
+            import torch
+            obj_type, obj_rel = _rel.ParseTypedRelation(permission)
+            stype, srel_name, _ = _rel._cut(subject_type, "#")
+            for what, t in (("resources", resources), ("subjects", subjects)):
+                if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.uint32) or not t.is_cuda:
+                    raise InvalidArgument(f"FilterCrossDevice: the {what} must be a device int32 / uint32 tensor of "
+                                          "interned ids")
+            if limit < 0:
+                raise InvalidArgument("FilterCrossDevice: the limit must not be negative")
+            requirement, revision = _requirement(cs)
+            eng = self.engine
+
+            def run():
+                # resolved per attempt, as CheckCross does
+                rt, st = eng.type_id(obj_type), eng.type_id(stype)
+                perm = eng.relation_id(rt, obj_rel)
+                srel = ELLIPSIS if srel_name in ("", "...") else eng.relation_id(st, srel_name)
+                if TYPE_INVALID in (rt, st) or REL_INVALID in (perm, srel):
+                    raise GckError(GCK_E_NOT_FOUND, "object definition or relation not found")
+                return eng.filter_cross_ids((rt, perm, st, srel), subjects, resources, row_limit=limit,
+                                            requirement=requirement, revision=revision)
+            return retryRetriableErrors(ctx or Background, run), None
+        except Exception as e:  # noqa: BLE001 — Go returns (nil, err)
+            return None, e
+
     # ---- snapshot plumbing (ReadSchema + ExportRelationships at its revision) -------------
     def LoadSnapshot(self, schema: str, revision: int, relationships: Iterable) -> None:
         """Ingest the output of ``ReadSchema`` (client/client.go:416-422) and

@@ -258,6 +258,147 @@ __global__ void __launch_bounds__(kBlock) k_dc_select(DcSelect a) {
   }
 }
 
+// A cross filter request (include/gck.h gck_filter_cross_device): the row-segmented selection over
+// the finished row-padded plane, a request-level step behind the last tile or chunk — three kernels
+// with nothing between them but the kernel boundary. k_dc_rows_count: what each row keeps, into
+// row_off[s + 1] (and its survivors into row_n[s]); k_dc_rows_scan: one block turns those into the
+// inclusive prefix in place; k_dc_rows_write: the kept survivors' records at row_off[s] + j.
+// The lane mapping of the count and the write kernel (select_plane.hpp select_row_lanes): a row of
+// `stride` words takes L lanes, L the smallest power of two >= stride within 1 .. 64, one word per
+// lane; a wave carries 64 / L rows. A row of more than 64 words (the expanded path only: an in-place
+// tile has R < GCK_CROSS_IDS) takes the whole wave, 64 words at a time.
+struct DcRows {
+  const unsigned long long* plane;
+  uint32_t S, R, stride, mask, row_limit;
+  uint32_t* row_off;
+  uint32_t* row_n;
+  gck::SelectRowsOut o;
+  uint32_t* out_n;
+};
+
+static_assert(gck::kRowPiece == 64u, "a piece of a row is one word per lane of a wave");
+
+// This lane's row and its word within a piece of it. Every lane of a wave stays in the kernel (the
+// shuffles below take the whole wave): a lane beyond S or beyond the row holds an empty word.
+__device__ inline void dc_row_lane(uint32_t stride, uint32_t& L, uint32_t& row, uint32_t& j) {
+  L = gck::select_row_lanes(stride);
+  const uint32_t lane = threadIdx.x & 63u, gw = blockIdx.x * (uint32_t)kWaves + (threadIdx.x >> 6);
+  row = gw * (64u / L) + lane / L;
+  j = lane & (L - 1u);
+}
+
+// Word t of `row` as its survivor mask (`word` gets the plane word); a padding lane of the row's
+// last word never survives, whatever the plane holds there, so a survivor's column is below R.
+__device__ inline uint64_t dc_row_word(const DcRows& a, uint32_t row, uint32_t t, uint64_t& word) {
+  word = row < a.S && t < a.stride ? reinterpret_cast<const uint64_t*>(a.plane)[(size_t)row * a.stride + t] : 0ull;
+  return gck::select_row_mask(word, a.mask, t, a.R);
+}
+
+__global__ void __launch_bounds__(kBlock) k_dc_rows_count(DcRows a) {
+  uint32_t L, row, j;
+  dc_row_lane(a.stride, L, row, j);
+  uint32_t sum = 0;
+  for (uint32_t p0 = 0; p0 < a.stride; p0 += gck::kRowPiece) {  // (one pass unless stride > 64; the carried count is `sum`)
+    uint64_t word;
+    sum += gck::select_count(dc_row_word(a, row, p0 + j, word));
+  }
+  for (uint32_t d = L >> 1; d >= 1u; d >>= 1) sum += (uint32_t)__shfl_xor((int)sum, (int)d, 64);  // (d < L: inside the row's lanes)
+  if (j == 0u && row < a.S) {
+    a.row_off[row + 1u] = gck::select_row_kept(sum, a.row_limit);
+    if (a.row_n) a.row_n[row] = sum;
+  }
+}
+
+// row_off[1 .. S] (each row's kept count) into the inclusive prefix, in place: one block, a tile of
+// blockDim entries at a time with a running base, as k_dc_emit scans. row_off[0] = 0 and *out_n =
+// the total (below 2^32: at most S * R).
+__global__ void __launch_bounds__(kBlock) k_dc_rows_scan(uint32_t* row_off, uint32_t S, uint32_t* out_n) {
+  __shared__ uint32_t wave_tot[kWaves];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t run = 0;
+  for (uint32_t t0 = 0; t0 < S; t0 += blockDim.x) {
+    const uint32_t t = t0 + threadIdx.x;
+    uint32_t incl = t < S ? row_off[t + 1u] : 0u;
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
+      if (lane >= (uint32_t)d) incl += up;
+    }
+    if (lane == 63u) wave_tot[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, tot = 0;
+    for (uint32_t k = 0; k < (uint32_t)kWaves; ++k) {
+      if (k < wave) before += wave_tot[k];
+      tot += wave_tot[k];
+    }
+    if (t < S) row_off[t + 1u] = run + before + incl;
+    run += tot;
+    __syncthreads();  // (wave_tot is rewritten by the next tile)
+  }
+  if (threadIdx.x == 0) {
+    row_off[0] = 0u;
+    *out_n = run;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_dc_rows_write(DcRows a) {
+  uint32_t L, row, j;
+  dc_row_lane(a.stride, L, row, j);
+  const uint32_t row_base = row < a.S ? a.row_off[row] : 0u;
+  uint32_t carry = 0;  // the row's survivors in the pieces before this one (the same in every lane of the row)
+  for (uint32_t p0 = 0; p0 < a.stride; p0 += gck::kRowPiece) {
+    const uint32_t t = p0 + j;
+    uint64_t word;
+    const uint64_t m = dc_row_word(a, row, t, word);
+    const uint32_t pc = gck::select_count(m);
+    uint32_t incl = pc;
+    for (uint32_t d = 1; d < L; d <<= 1) {
+      const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
+      if (j >= d) incl += up;  // (lane - d is inside the row's lanes)
+    }
+    gck::select_write_row(word, m, t * 32u, carry + incl - pc, row_base, a.row_limit, a.o);
+    if (a.stride <= gck::kRowPiece) break;
+    carry += (uint32_t)__shfl((int)incl, 63, 64);  // (L == 64: the wave is one row)
+    if (a.row_limit && carry >= a.row_limit) break;  // (wave-uniform)
+  }
+}
+
+// The three kernels on `st`; the caller waits. S == 0 writes row_off[0] and *out_n alone; R == 0
+// (stride 0, no plane read) writes S + 1 zeros and S zero row counts.
+static void dc_select_rows(const gck_select_rows& sel, const unsigned long long* plane, size_t S, size_t R,
+                           const uint32_t* resources, hipStream_t st) {
+  DcRows a{};
+  a.plane = plane;
+  a.S = (uint32_t)S;
+  a.R = (uint32_t)R;
+  a.stride = (uint32_t)((R + 31u) / 32u);
+  a.mask = sel.mask;
+  a.row_limit = sel.row_limit;
+  a.row_off = sel.d_out_row_off;
+  a.row_n = sel.d_out_row_n;
+  a.o = gck::SelectRowsOut{sel.d_out_ids, sel.d_out_col, sel.d_out_perm, (uint32_t)std::min<size_t>(sel.cap, 0xFFFFFFFFu),
+                           resources};
+  a.out_n = sel.d_out_n;
+  const uint32_t per_block = (uint32_t)kWaves * (64u / gck::select_row_lanes(a.stride));
+  const dim3 grid((a.S + per_block - 1u) / per_block), block(kBlock);
+  if (a.S) {
+    hipLaunchKernelGGL(k_dc_rows_count, grid, block, 0, st, a);
+    HIP_OK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_dc_rows_scan, dim3(1), block, 0, st, a.row_off, a.S, a.out_n);
+  HIP_OK(hipGetLastError());
+  if (a.S && a.stride && a.o.cap) {
+    hipLaunchKernelGGL(k_dc_rows_write, grid, block, 0, st, a);
+    HIP_OK(hipGetLastError());
+  }
+}
+
+// An empty cross filter request (S == 0 or R == 0: no workspace, no check): its offsets and counts.
+void device_select_rows_empty(Engine& e, const gck_select_rows& sel, size_t S, void* stream) {
+  HIP_OK(hipSetDevice(e.device));
+  dc_select_rows(sel, nullptr, S, 0, nullptr, (hipStream_t)stream);
+  HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+}
+
 // The word a device request counts its errors in, cleared on `st` before the request's first chunk:
 // the caller's, or the workspace's own (which stays 0 until an emit adds to it).
 // (the caller's word of a submitted batch is left to the batch: CompactRun::zero_cnt)
@@ -362,6 +503,12 @@ static void device_collect(Engine& e, Workspace& w) {
     a.out_n = c.sel.d_out_n;
     hipLaunchKernelGGL(k_dc_select, dim3((words + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
     HIP_OK(hipGetLastError());
+    launched = true;
+  }
+  if (c.select_rows) {
+    // a submitted cross filter request: this batch was its one tile or chunk, so the plane is finished
+    // once the kernels above have run on this stream
+    dc_select_rows(c.rsel, c.out, c.rsel_S, c.R, c.rsel_ids, st);
     launched = true;
   }
   // (the count's clear — and the kernels above — are complete when the wait returns; a batch on the

@@ -246,6 +246,12 @@ struct CompactRun {
   uint32_t sel_first = 0;
   const uint32_t* sel_prev = nullptr;
   uint32_t* sel_next = nullptr;
+  // a submitted cross filter request's batch (CompactReq::sel_rows): it is the whole request — one
+  // tile or one chunk — so its collect ends with the row selection over `out` (dc_select_rows)
+  bool select_rows = false;
+  gck_select_rows rsel{};
+  const uint32_t* rsel_ids = nullptr;  // the request's resource list
+  size_t rsel_S = 0;
   bool in_place() const { return mode == kInPlace; }
   bool table_join() const { return mode == kInPlace && indexed; }  // the join reads index bytes and a shape table
 };
@@ -4015,6 +4021,13 @@ void device_submit_compact(Engine& e, Workspace* w, const CompactReq& req, int64
     w->cb.zero_cnt = false;
     w->cb.cnt_memset = true;
   }
+  if (q.sel_rows) {  // (the batch is the whole request: its collect selects the rows)
+    w->cb.select_rows = true;
+    w->cb.rsel = *q.sel_rows;
+    w->cb.rsel_ids = q.resources;
+    w->cb.rsel_S = q.S;
+    w->cb.out = reinterpret_cast<unsigned long long*>(q.packed);
+  }
 }
 
 // The chunks of a request that is no cross request: max_batch checks each, rounded down to a multiple
@@ -4067,6 +4080,12 @@ void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const Compact
         e, w0, w1, tiled ? cross_tiles(q) : q.n, tiled ? 1 : mb, cav,
         [&](Workspace& w, size_t pos, uint32_t len) { submit_compact(e, w, q, pos, len, now_us, d_cnt); },
         [&](Workspace& w) { device_collect(e, w); });
+    if (q.sel_rows) {
+      // every band or chunk is collected — its stream completed — so the plane is finished: the row
+      // selection over the whole of it, then the wait
+      dc_select_rows(*q.sel_rows, reinterpret_cast<const unsigned long long*>(q.packed), q.S, q.R, q.resources, w0->stream);
+      HIP_OK(hipStreamSynchronize(w0->stream));
+    }
     return;
   }
   if (req.cross()) {

@@ -453,7 +453,13 @@ struct CompactReq {
   // each chunk's finished plane go to *sel's arrays, their number to *sel->d_out_n (copied per chunk).
   // `packed` may then be null: the plane stays in the workspace
   const gck_select* sel = nullptr;
+  // a cross filter request (gck_filter_cross_device; a cross request over device buffers): once the
+  // whole plane is finished, each row's kept survivors go to *sel_rows' arrays as a CSR (copied by
+  // the submit; device_compact.inc dc_select_rows)
+  const gck_select_rows* sel_rows = nullptr;
 };
+// The outputs of an empty cross filter request (S == 0 or R == 0), synchronous on `stream`.
+void device_select_rows_empty(Engine& e, const gck_select_rows& sel, size_t S, void* stream);
 // *d_n_errs = 0 for an empty device request (synchronous on `stream`; a null pointer: nothing).
 void device_zero_count(Engine& e, uint32_t* d_n_errs, void* stream);
 // Synchronous: chunks of max_batch & ~31 checks over w0 and w1 (as device_check_host); a cross

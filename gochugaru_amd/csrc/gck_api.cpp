@@ -1625,6 +1625,97 @@ int gck_filter_submit_list_device(gck_engine* ge, const gck_consistency* cs, con
   });
 }
 
+// ---- cross filter requests (include/gck.h gck_filter_cross_device) ----------------------------
+
+// The selection's own argument rules, shared with the host hook (gck_test_select_rows): null when
+// the selection is good, else what is wrong with it.
+static const char* select_rows_fault(const gck_select_rows* sel) {
+  const auto aligned = [](const void* p) { return ((uintptr_t)p & 3u) == 0; };
+  if (!sel) return "cross filter request: null gck_select_rows";
+  if (sel->mask == 0 || (sel->mask & ~0xEu))
+    return "cross filter request: mask must select among GCK_SELECT_NO, GCK_SELECT_HAS and GCK_SELECT_CONDITIONAL";
+  if (!sel->d_out_row_off) return "cross filter request: null d_out_row_off";
+  if (!sel->d_out_n) return "cross filter request: null d_out_n";
+  if (sel->cap != 0 && !sel->d_out_ids && !sel->d_out_col && !sel->d_out_perm)
+    return "cross filter request: cap > 0 without an output array";
+  if (!aligned(sel->d_out_row_off) || !aligned(sel->d_out_row_n) || !aligned(sel->d_out_ids) ||
+      !aligned(sel->d_out_col) || !aligned(sel->d_out_n))
+    return "cross filter request: d_out_row_off, d_out_row_n, d_out_ids, d_out_col or d_out_n is not 4-byte aligned";
+  return nullptr;
+}
+
+// A cross filter request's selection against the call, before anything is launched or written; then
+// the cross device request with it (`sel` is the caller's: the engine copies it before the call returns).
+static CompactReq filter_cross_request(const gck_select_rows* sel, const gck_uniform* hdr, const uint32_t* d_subjects,
+                                       size_t S, const uint32_t* d_resources, size_t R, size_t n_contexts,
+                                       uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                       uint32_t* d_out_n_errs, void* stream, bool engine_stream) {
+  const char* fault = select_rows_fault(sel);
+  REQUIRE(!fault, GCK_E_INVALID_ARGUMENT, fault ? fault : "");
+  REQUIRE(d_out_packed, GCK_E_INVALID_ARGUMENT, "cross filter request: null d_out_packed");
+  CompactReq q = cross_device_request(hdr, d_subjects, S, d_resources, R, n_contexts, d_out_packed, d_out_errs, err_cap,
+                                      d_out_n_errs, stream, engine_stream);
+  q.sel_rows = sel;
+  return q;
+}
+
+int gck_filter_cross_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr,
+                            const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                            size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                            size_t n_contexts, int64_t now_us, const gck_select_rows* sel, uint64_t* d_out_packed,
+                            gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, void* stream,
+                            uint64_t* out_revision) {
+  return guard([&] {
+    Engine& e = need(ge);
+    const CompactReq req = filter_cross_request(sel, hdr, d_subjects, n_subjects, d_resources, n_resources, n_contexts,
+                                                d_out_packed, d_out_errs, err_cap, d_out_n_errs, stream, true);
+    const CallCtx c{cs, contexts, context_lens, n_contexts};
+    if (req.n == 0) {  // (no check runs: the count word, then the offsets and counts of S empty rows)
+      check_device_sync(e, c, req, now_us, out_revision);
+      return device_select_rows_empty(e, *sel, n_subjects, stream);
+    }
+    // (the workspaces of gck_check_bulk_cross_device)
+    uint32_t rows = 0;
+    const size_t mb = max_batch_of(e);
+    const size_t one = gck_cross_tile_device(n_subjects, n_resources, mb, &rows) ? (size_t)rows * n_resources
+                                                                                 : (mb & ~(size_t)31);
+    check_sync(e, c, req.n, one, out_revision,
+               [&](Workspace* w0, Workspace* w1, const CavCall& cav) { device_check_compact(e, w0, w1, req, now_us, cav); });
+  });
+}
+
+int gck_filter_submit_cross_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr,
+                                   const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                                   size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                                   size_t n_contexts, int64_t now_us, const gck_select_rows* sel,
+                                   uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                   uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    check_submit_flags(flags);
+    const bool own = (flags & GCK_SUBMIT_ENGINE_STREAM) != 0;
+    const CompactReq req = filter_cross_request(sel, hdr, d_subjects, n_subjects, d_resources, n_resources, n_contexts,
+                                                d_out_packed, d_out_errs, err_cap, d_out_n_errs, stream, own);
+    uint32_t rows = 0;
+    REQUIRE(req.n == 0 || (gck_cross_tile_device(n_subjects, n_resources, max_batch_of(e), &rows) && rows == n_subjects),
+            GCK_E_INVALID_ARGUMENT,
+            "submitted cross filter request of " + std::to_string(n_subjects) + " x " + std::to_string(n_resources) +
+                " is not one tile (gck_cross_tile_device)");
+    gck_batch* b = submit_device(e, {cs, contexts, context_lens, n_contexts}, req, now_us);
+    if (req.n == 0) {
+      try {
+        device_select_rows_empty(e, *sel, n_subjects, own ? nullptr : stream);
+      } catch (...) {
+        delete b;
+        throw;
+      }
+    }
+    *out = b;
+  });
+}
+
 int gck_device_compact_stats(gck_engine* ge, uint64_t out[2]) {
   return guard([&] {
     Engine& e = need(ge);
@@ -2000,6 +2091,58 @@ int gck_test_select_plane(const uint64_t* words, uint32_t n_words, uint32_t mask
     total = rank;
   }
   *out_n = total;
+  return 0;
+}
+
+// gck_test_select_rows: the row-segmented selection of a cross filter request (select_plane.hpp;
+// k_dc_rows_count, k_dc_rows_scan and k_dc_rows_write in device_compact.inc) over a row-padded plane
+// of S rows of ceil(R / 32) words on the host, with the same functions, row by row and piece by piece
+// of kRowPiece words as the kernels walk them: the counts, their prefix, then each word's survivors
+// from the in-row rank the words before it give. Outputs and NULL rules are gck_select_rows' (src_ids:
+// the resource list, needed with out_ids). -1 for the selection's argument errors. What this pins is
+// the per-word functions and the protocol; the kernels' lane scans inside a wave are covered only by
+// the GPU tests.
+int gck_test_select_rows(const uint64_t* words, uint32_t S, uint32_t R, uint32_t mask, uint32_t row_limit, size_t cap,
+                         const uint32_t* src_ids, uint32_t* out_row_off, uint32_t* out_row_n, uint32_t* out_ids,
+                         uint32_t* out_col, uint8_t* out_perm, uint32_t* out_n) {
+  gck_select_rows sel{mask, row_limit, out_row_off, out_row_n, out_ids, out_col, out_perm, cap, out_n};
+  if (select_rows_fault(&sel)) return -1;
+  const uint32_t stride = (R + 31u) / 32u;
+  if ((!words && S && stride) || (out_ids && !src_ids && R)) return -1;
+  if (S && R && S > 0xFFFFFFFFu / R) return -1;
+  const gck::SelectRowsOut o{out_ids, out_col, out_perm, (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu), src_ids};
+  const auto row_word = [&](uint32_t s, uint32_t t, uint64_t& word) {
+    word = words[(size_t)s * stride + t];
+    return gck::select_row_mask(word, mask, t, R);
+  };
+  for (uint32_t s = 0; s < S; ++s) {  // k_dc_rows_count
+    uint32_t sum = 0;
+    for (uint32_t p0 = 0; p0 < stride; p0 += gck::kRowPiece)
+      for (uint32_t t = p0; t < stride && t < p0 + gck::kRowPiece; ++t) {
+        uint64_t word;
+        sum += gck::select_count(row_word(s, t, word));
+      }
+    out_row_off[s + 1u] = gck::select_row_kept(sum, row_limit);
+    if (out_row_n) out_row_n[s] = sum;
+  }
+  uint32_t run = 0;  // k_dc_rows_scan
+  for (uint32_t s = 0; s < S; ++s) out_row_off[s + 1u] = run += out_row_off[s + 1u];
+  out_row_off[0] = 0u;
+  *out_n = run;
+  for (uint32_t s = 0; s < S && o.cap; ++s) {  // k_dc_rows_write
+    uint32_t carry = 0;
+    for (uint32_t p0 = 0; p0 < stride; p0 += gck::kRowPiece) {
+      uint32_t rank = carry;
+      for (uint32_t t = p0; t < stride && t < p0 + gck::kRowPiece; ++t) {
+        uint64_t word;
+        const uint64_t m = row_word(s, t, word);
+        gck::select_write_row(word, m, t * 32u, rank, out_row_off[s], row_limit, o);
+        rank += gck::select_count(m);
+      }
+      carry = rank;
+      if (row_limit && carry >= row_limit) break;
+    }
+  }
   return 0;
 }
 

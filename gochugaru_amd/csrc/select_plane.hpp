@@ -2,7 +2,9 @@
 // gck_filter_list_device): which checks of a 64-bit word survive a mask of Permissionships, how many
 // survive in a run of words, and the records of a word's survivors at their ranks. Plain C++ that
 // host code compiles as well as the device (k_dc_select in device_compact.inc calls it; gck_api.cpp
-// exports it for the tests as gck_test_select_plane).
+// exports it for the tests as gck_test_select_plane). Below them, the row-segmented form over a cross
+// request's row-padded plane (gck_filter_cross_device; k_dc_rows_count / k_dc_rows_write, and
+// gck_test_select_rows on the host).
 //
 // A word holds 32 checks, check b in bits 2b .. 2b + 1 (GCK_PERM_*: 0 unspecified — an errored check
 // and a tail lane alike —, 1 NO, 2 HAS, 3 CONDITIONAL). `mask` has bit v set when value v survives
@@ -67,6 +69,66 @@ GCK_SEL_HD inline void select_write(uint64_t word, uint64_t m, uint32_t t, uint3
     if (o.ids) o.ids[rank] = o.src_ids ? o.src_ids[i] : o.first_id + i;
     if (o.pos) o.pos[rank] = o.pos0 + i;
     if (o.perm) o.perm[rank] = (uint8_t)((word >> bit) & 3u);
+    ++rank;
+  }
+}
+
+// ---- the row-segmented selection over a cross plane (include/gck.h gck_filter_cross_device) ----
+// The plane is S rows of `stride` = ceil(R / 32) words; row s keeps its first kept_s survivors, at
+// ranks row_off[s] + j of the request. The kernels (k_dc_rows_count, k_dc_rows_write) and the host
+// hook (gck_test_select_rows) walk a row in pieces of kRowPiece words, one word per lane of a wave.
+
+constexpr uint32_t kRowPiece = 64;  // words of a row a wave takes at once
+
+// The lanes of a wave that one row of `stride` words takes: the smallest power of two >= stride,
+// within 1 .. 64 (a wave carries 64 / L rows; a longer row takes the whole wave, piece after piece).
+GCK_SEL_HD inline uint32_t select_row_lanes(uint32_t stride) {
+  uint32_t l = 1;
+  while (l < stride && l < kRowPiece) l <<= 1;
+  return l;
+}
+
+// What a row keeps of its surv survivors under row_limit (0: all of them).
+GCK_SEL_HD inline uint32_t select_row_kept(uint32_t surv, uint32_t row_limit) {
+  return row_limit && surv > row_limit ? row_limit : surv;
+}
+
+// The survivor mask of word t of a row of R checks: select_mask, with the padding lanes of the row's
+// last word cleared (the engine writes them 0; a survivor's column is below R whatever they hold).
+GCK_SEL_HD inline uint64_t select_row_mask(uint64_t word, uint32_t mask, uint32_t t, uint32_t R) {
+  uint64_t m = select_mask(word, mask);
+  const uint32_t col0 = t * 32u;
+  if (col0 >= R) return 0;
+  if (R - col0 < 32u) m &= (1ull << (2u * (R - col0))) - 1ull;
+  return m;
+}
+
+// Where the kept survivors go: any of the three arrays may be null; `cap` entries each. A
+// survivor's id is src_ids[r], r its column.
+struct SelectRowsOut {
+  uint32_t* ids;
+  uint32_t* col;
+  uint8_t* perm;
+  uint32_t cap;
+  const uint32_t* src_ids;
+};
+
+// The survivors m of one word of a row (word = its plane word, col0 = the column of its check 0), the
+// first of them at in-row rank `rank`; the row's first record is at `row_base` of the request. Each is
+// written while its in-row rank is below `limit` (0: no limit) and its rank in the request below
+// cap. Ascending within the word.
+GCK_SEL_HD inline void select_write_row(uint64_t word, uint64_t m, uint32_t col0, uint32_t rank, uint32_t row_base,
+                                        uint32_t limit, const SelectRowsOut& o) {
+  while (m) {
+    if (limit && rank >= limit) return;
+    const uint32_t at = row_base + rank;
+    if (at >= o.cap) return;
+    const uint32_t bit = (uint32_t)__builtin_ctzll(m);
+    m &= m - 1u;
+    const uint32_t r = col0 + (bit >> 1);
+    if (o.ids) o.ids[at] = o.src_ids[r];
+    if (o.col) o.col[at] = r;
+    if (o.perm) o.perm[at] = (uint8_t)((word >> bit) & 3u);
     ++rank;
   }
 }

@@ -57,6 +57,9 @@
  *       the list device request with its last step on the device too: the checks whose Permissionship
  *       a mask selects, compacted by a kernel into device arrays of ids, positions and
  *       Permissionships in the caller's order, and their number.
+ *   gck_filter_cross_device / gck_filter_submit_cross_device
+ *       the cross device request likewise: each subject's surviving resources, optionally the first K
+ *       of them, compacted by kernels into a CSR (row offsets, ids, columns, Permissionships).
  *
  * Ownership: all inputs and outputs are caller-allocated; the engine never retains a caller
  * pointer after a call returns, except that gck_check_submit keeps the output pointers (and, for
@@ -710,6 +713,62 @@ int gck_filter_submit_list_device(gck_engine* e, const gck_consistency* cs, cons
                                   int64_t now_us, const gck_select* sel, uint64_t* d_out_packed,
                                   gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, uint32_t flags,
                                   void* stream, gck_batch** out);
+
+/* ---- cross filter requests (ABI 13, additive) ----------------------------------------
+ * gck_check_bulk_cross_device / gck_check_submit_cross_device with the last step done on the device
+ * too: "for each of these subjects, which of these resources" — the survivors of every row of the
+ * finished plane, compacted by kernels into a CSR in the caller's device memory. Nothing but the two
+ * count words (*d_out_n, *d_out_n_errs) ever needs to cross PCIe.
+ * The check itself is the cross device call's, unchanged in every respect: the tiling and the block
+ * layout read in place, the expansion on the device (check contexts, R >= GCK_CROSS_IDS, thin requests
+ * and the other fallbacks), stream ordering and `flags`, consistency and the evaluated revision, the
+ * error records (index = s * R + r) and the request errors. d_out_packed is required and is written
+ * exactly as gck_check_bulk_cross_device writes it (a form without a plane is out of scope).
+ * Check (s, r) survives iff it has no per-item error and (sel->mask >> perm) & 1. Row s has surv_s
+ * survivors and keeps kept_s = row_limit ? min(surv_s, row_limit) : surv_s of them, the first in
+ * ascending r (the first K permitted candidates of a ranked page).
+ *   d_out_row_off: row_off[0] = 0, row_off[s + 1] = row_off[s] + kept_s; all S + 1 entries are always
+ *     written, whatever cap is. With S == 0 only row_off[0] and *d_out_n (= 0) are written, besides the
+ *     error count word; with R == 0 all S + 1 entries are 0 (and d_out_row_n, when given, S zeros).
+ *   records: kept survivor j of row s has rank row_off[s] + j; its resource id (d_resources[r]), its
+ *     position r in the resource list and its GCK_PERM_* go to every array that is not NULL iff
+ *     rank < cap. Entries at and beyond min(total, cap) stay untouched.
+ *   d_out_row_n[s] = surv_s (before row_limit) when the array is given; *d_out_n = row_off[S], always
+ *     written.
+ * Ids are reported as often as the resource list repeats them; the selection reads d_resources, which
+ * stays valid until the synchronous call or the wait returns (the cross device call's lifetime rule).
+ * A per-item error does not fail the call, as for the list filter: the errored check never survives
+ * and the caller holds the count word.
+ * `sel` is copied by the call (the submit call included). GCK_E_INVALID_ARGUMENT, nothing launched and
+ * nothing written, for sel == NULL, a bad mask (gck_select's rule: 0, bit 0 set, above 0xE),
+ * d_out_row_off == NULL, d_out_n == NULL, d_out_packed == NULL, cap > 0 with all three record arrays
+ * NULL, a d_out_row_off, d_out_row_n, d_out_ids, d_out_col or d_out_n that is not 4-byte aligned, and
+ * everything the cross device call refuses. gck_device_compact_stats counts the request as a cross
+ * device request.
+ * Out of scope: the mirror — per-resource rows of surviving subjects — would need a transposed plane. */
+typedef struct gck_select_rows {
+  uint32_t mask;           /* GCK_SELECT_*: as gck_select.mask (bit 0 clear, != 0, <= 0xE) */
+  uint32_t row_limit;      /* 0: keep every survivor; else keep at most this many per subject, the first in list order */
+  uint32_t* d_out_row_off; /* device, S + 1 entries, required */
+  uint32_t* d_out_row_n;   /* device, S entries, may be NULL: survivors of row s BEFORE row_limit */
+  uint32_t* d_out_ids;     /* device, cap entries, may be NULL: resources[r] of a kept survivor */
+  uint32_t* d_out_col;     /* device, cap entries, may be NULL: its position r in the resource list */
+  uint8_t*  d_out_perm;    /* device, cap entries, may be NULL: its GCK_PERM_* */
+  size_t    cap;
+  uint32_t* d_out_n;       /* device, required: kept survivors of the whole request (== row_off[S]) */
+} gck_select_rows;         /* 64 bytes */
+int gck_filter_cross_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr,
+                            const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                            size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                            size_t n_contexts, int64_t now_us, const gck_select_rows* sel, uint64_t* d_out_packed,
+                            gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, void* stream,
+                            uint64_t* out_revision);
+int gck_filter_submit_cross_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr,
+                                   const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                                   size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                                   size_t n_contexts, int64_t now_us, const gck_select_rows* sel,
+                                   uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                   uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out);
 
 /* ---- lookups (Client.LookupResources / LookupSubjects, client/client.go:508-599) -------- */
 /* Ids of the `resource_type` objects on which the subject has `permission` — HAS or CONDITIONAL,
