@@ -504,6 +504,10 @@ static uint32_t* slot_alloc(DeviceSnapshot& ds, size_t bytes) {
 struct SlotSet {
   const uint32_t* slots = nullptr;
   const uint32_t* list = nullptr;  // user slots: the cover lists (null: none)
+  // resource slots: their 16-B fronts (slot_pack.hpp), in the slots' own allocation behind the last
+  // slot — built, adopted and freed with them, so a Watch batch that rewrites a resource's slot
+  // (the whole array is rebuilt then) publishes its front with it
+  const uint32_t* fronts(uint32_t n_rows) const { return slots ? slots + (size_t)n_rows * kDSlotWords : nullptr; }
 };
 
 // closure.inc k_user_slots_1p / k_user_slots_ids at the snapshot's entry width, on the null stream.
@@ -654,7 +658,7 @@ static SlotSet slots_for(Engine& e, DeviceSnapshot& ds, std::map<const uint32_t*
   if (kind == SlotKind::kUser)
     if (const SlotSet* d = slots_delta(e, ds, cache, off, nbr, n_rows, closure, n_groups)) return *d;
   PhaseClock pc(kind == SlotKind::kUser ? "user_slots" : "res_slots");
-  const size_t bytes = (size_t)std::max<uint32_t>(n_rows, 1) * words * 4;
+  const size_t bytes = (size_t)std::max<uint32_t>(n_rows, 1) * (words + (kind == SlotKind::kResource ? kFrontWords : 0u)) * 4;
   size_t free_b = 0, total_b = 0;
   HIP_OK(hipMemGetInfo(&free_b, &total_b));
   SlotSet out;
@@ -673,7 +677,7 @@ static SlotSet slots_for(Engine& e, DeviceSnapshot& ds, std::map<const uint32_t*
       out.list = ul.list;
     } else if (n_rows) {
       hipLaunchKernelGGL(k_res_slots, dim3(grid_for(n_rows)), dim3(kBlock), 0, 0, off, nbr, n_rows, closure->lab,
-                         n_groups, s);
+                         n_groups, s, s + (size_t)n_rows * kDSlotWords);
       HIP_OK(hipGetLastError());
       HIP_OK(hipDeviceSynchronize());
       ds.slot_recs.push_back({off, closure->lab, closure->cov_pre, s, nullptr, 0ull, n_rows, (uint8_t)SlotKind::kResource});
@@ -708,11 +712,16 @@ static void build_closure_join(Engine& e, DeviceSnapshot& ds, const std::vector<
     return true;
   };
   const Derived* closure_of = nullptr;
+  bool no_fronts = false;
+  if (const char* f = debug_env("GCK_DEBUG_CJ_FRONT")) no_fronts = atoi(f) == 0;
   std::map<const uint32_t*, SlotSet> slot_cache;  // source CSR offsets -> its slots
   {
     ds.slot_bits = 24u;
     for (const Derived& x : ds.derived)
       if (x.kind == 1 && x.d.n_rows >= (1u << 24) - 1u) ds.slot_bits = 32;  // (all-ones: the unused-entry mark)
+    // (GCK_DEBUG_SLOT_BITS=32: the 32-bit layout and its kernels on a small hierarchy, for the tests)
+    if (const char* b = debug_env("GCK_DEBUG_SLOT_BITS"))
+      if (atoi(b) == 32) ds.slot_bits = 32;
   }
   std::vector<uint16_t> root(nf, 0xFFFFu);
   std::vector<CjMeta> meta;
@@ -774,10 +783,12 @@ static void build_closure_join(Engine& e, DeviceSnapshot& ds, const std::vector<
         const SlotSet us = slots_for(e, ds, slot_cache, E.t_off, E.t_nbr, E.t_rows, SlotKind::kUser, closure_of, M.m_rows);
         E.uslot = us.slots;
         E.ulist = us.list;
-        E.dslot = E.uslot ? slots_for(e, ds, slot_cache, E.v_off, E.v_nbr, E.v_rows, SlotKind::kResource, closure_of,
-                                      M.m_rows).slots
-                          : nullptr;
+        const SlotSet rs = E.uslot ? slots_for(e, ds, slot_cache, E.v_off, E.v_nbr, E.v_rows, SlotKind::kResource, closure_of, M.m_rows)
+                                   : SlotSet{};
+        E.dslot = rs.slots;
         if (!E.dslot) E.uslot = E.ulist = nullptr;
+        // the fronts' starts are 24 bits wide: 24-bit snapshots only (GCK_DEBUG_CJ_FRONT=0: the join without them)
+        else if (ds.slot_bits == 24u && !no_fronts) E.dfront = rs.fronts(E.v_rows);
       }
       ents.push_back(E);
     }

@@ -49,6 +49,7 @@ constexpr uint32_t kDSlotWords = 16;   // 64 B per resource: count, (pre, end) p
 // entries), the rest of a resource slot zero (empty intervals).
 template <int BITS> constexpr uint32_t slot_half_cap() { return BITS == 24 ? 9u : 7u; }
 constexpr uint32_t kSlotHalfV = 3;
+static_assert(kFrontV == kSlotHalfV, "a front holds what half a resource slot holds");
 
 struct CjEntry {  // one (eligible root, subject type): everything a check needs, flat (64 B)
   const uint32_t* v_off;   // R's groups (null: V(R) = {R})
@@ -62,8 +63,10 @@ struct CjEntry {  // one (eligible root, subject type): everything a check needs
   const uint32_t* uslot;   // slot fast path (null: none): kUSlotWords per subject (t_rows)
   const uint32_t* dslot;   // kDSlotWords per resource (v_rows)
   const uint32_t* ulist;   // the cover lists of users whose covers exceed a slot (null: none)
+  const uint32_t* dfront;  // kFrontWords per resource: the slots' 16-B fronts (slot_pack.hpp; null: none — a
+                           // 32-bit snapshot, GCK_DEBUG_CJ_FRONT=0)
 };
-static_assert(sizeof(CjEntry) == 88, "CjEntry layout");
+static_assert(sizeof(CjEntry) == 96, "CjEntry layout");
 
 struct CjMeta {  // per eligible root
   uint16_t mtype, mrel;   // the self-recursive relation m
@@ -350,8 +353,8 @@ __device__ __forceinline__ void block_summary_cold(const A& a, uint32_t deferred
 }
 
 // per wave: {start, table staged, round 1 done, tasks done, end, tasks, probes, checks taken,
-// items staged, slots and lists decided, slots decided}
-constexpr int kCjTimingWords = 11;
+// items staged, slots and lists decided, slots decided, checks whose front said "read the slot"}
+constexpr int kCjTimingWords = 12;
 
 __device__ __forceinline__ void sig_bits(uint32_t v, uint32_t& b0, uint32_t& b1, uint32_t& b2) {
   const uint64_t h = mix64(0x9E3779B97F4A7C15ull ^ v);
@@ -620,10 +623,10 @@ __global__ void __launch_bounds__(kBlock) k_slot_scatter(uint32_t* __restrict__ 
   for (uint32_t j = 0; j < kUSlotWords / 4; ++j) dst[j] = src[j];
 }
 
-// One thread per resource: the interval of each of its groups.
+// One thread per resource: the interval of each of its groups, and the slot's front (slot_pack.hpp).
 __global__ void __launch_bounds__(kBlock) k_res_slots(const uint32_t* __restrict__ v_off, const uint32_t* __restrict__ v_nbr,
                                                       uint32_t n_res, const uint32_t* __restrict__ lab, uint32_t n_groups,
-                                                      uint32_t* __restrict__ slots) {
+                                                      uint32_t* __restrict__ slots, uint32_t* __restrict__ fronts) {
   const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
   if (r >= n_res) return;
   const uint32_t b = v_off[r], n = v_off[r + 1] - b;
@@ -646,6 +649,9 @@ __global__ void __launch_bounds__(kBlock) k_res_slots(const uint32_t* __restrict
   uint4* out = reinterpret_cast<uint4*>(slots + (size_t)r * kDSlotWords);
 #pragma unroll
   for (uint32_t j = 0; j < kDSlotWords / 4; ++j) out[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
+  uint32_t f[kFrontWords];
+  front_pack(w, f);
+  *reinterpret_cast<uint4*>(fronts + (size_t)r * kFrontWords) = make_uint4(f[0], f[1], f[2], f[3]);
 }
 
 template <int BITS, int K = 0>
@@ -941,7 +947,7 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
     bad_w = check_slots(cold->bad_slot, cold->slot_limit, active, it, w0, lane);
   }
   // ---- round 1: both slots of every check the slots can take, line by line ---------------------
-  unsigned long long ua = 0, da = 0, lbase = 0;
+  unsigned long long ua = 0, da = 0, fa = 0, lbase = 0;  // (fa: the resource slot's front, half slots only)
   if (active && it.permission < a.n_fwd && it.subject_id != kWildcard && it.subject_relation == kEllipsis) {
     const uint32_t d = root[it.permission];
     if (d != 0xFFFFu && it.resource_type == meta[d].rtype && it.subject_type < a.n_types) {
@@ -950,6 +956,7 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
         ua = (unsigned long long)(uintptr_t)(E.uslot + (size_t)it.subject_id * kUSlotWords);
         da = (unsigned long long)(uintptr_t)(E.dslot + (size_t)it.resource_id * kDSlotWords);
         lbase = (unsigned long long)(uintptr_t)E.ulist;
+        if (HALF && E.dfront) fa = (unsigned long long)(uintptr_t)(E.dfront + (size_t)it.resource_id * kFrontWords);
       }
     }
   }
@@ -959,6 +966,7 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
   s_da[lane] = da;
   const bool any_slots = __ballot(ua != 0) != 0;
   uint32_t dd[kDSlotWords];  // this lane's resource slot (the list round stages it again)
+  uint32_t n_flag = 0;       // the wave's checks whose front said "read the slot" (timing builds record it)
   if (HALF && any_slots) {
     // the whole user slot (four lanes per 64-B line) and the first 32 B of the resource slot
     // (two lanes per half line) of every check: three loads per lane. The first half of a
@@ -967,13 +975,23 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
     // 43.6 vs 25.6 G random reads/s); the lanes whose resource slot goes on read its second half
     // themselves below. (Half user slots too — users with <= 9 covers — measured slower: most
     // waves then had a lane with more covers, and so a second dependent round.)
+    //
+    // With fronts (CjEntry::dfront, 24-bit snapshots) the resource read is the check's own 16-B front
+    // instead, one lane each, in the same round: four fronts share a 64-B line, so a quarter as many
+    // lines carry the resources and more of the reads are Infinity Cache hits — which takes a
+    // temporal load (tools/gather_probe --two-table: nontemporal, the layout changes nothing;
+    // temporal, 16-B records read 2.9 % more checks/s than today's half slots). A flagged front
+    // (slot_pack.hpp), or a check whose entry has none, reads its whole slot below.
+    const bool fronts = __ballot(fa != 0) != 0;  // (wave-uniform: a scalar branch)
     u32x4 y[3];
 #pragma unroll
     for (uint32_t r = 0; r < 2u; ++r) {  // user line of check 16 r + lane / 4, chunk lane % 4
       const unsigned long long b = s_ua[16u * r + ((uint32_t)lane >> 2)];
       y[r] = b ? slot_load((const GCK_GLOBAL u32x4*)(b + ((uint32_t)lane & 3u) * 16u)) : u32x4{0u, 0u, 0u, 0u};
     }
-    {  // resource half line of check lane / 2, chunk lane % 2
+    if (fronts) {  // the check's own front (no front: flagged)
+      y[2] = fa ? *(const GCK_GLOBAL u32x4*)fa : u32x4{kFrontReadSlot, kFrontReadSlot, kFrontReadSlot, kFrontReadSlot};
+    } else {  // resource half line of check lane / 2, chunk lane % 2
       const unsigned long long b = s_da[(uint32_t)lane >> 1];
       y[2] = b ? slot_load((const GCK_GLOBAL u32x4*)(b + ((uint32_t)lane & 1u) * 16u)) : u32x4{0u, 0u, 0u, 0u};
     }
@@ -983,7 +1001,8 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
       const uint32_t chk = 16u * r + ((uint32_t)lane >> 2);
       *reinterpret_cast<u32x4*>(&s_slot_w[chk * kCheckWords + ((uint32_t)lane & 3u) * 4u]) = y[r];
     }
-    *reinterpret_cast<u32x4*>(&s_slot_w[((uint32_t)lane >> 1) * kCheckWords + kUSlotWords + ((uint32_t)lane & 1u) * 4u]) = y[2];
+    if (!fronts)
+      *reinterpret_cast<u32x4*>(&s_slot_w[((uint32_t)lane >> 1) * kCheckWords + kUSlotWords + ((uint32_t)lane & 1u) * 4u]) = y[2];
     lds_wave_fence();
     uint32_t w[kUSlotWords];
     if ((uint32_t)lane < CPW) {
@@ -993,16 +1012,38 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
         const u32x4 v = *reinterpret_cast<const u32x4*>(&src[q]);
         w[q] = v.x, w[q + 1] = v.y, w[q + 2] = v.z, w[q + 3] = v.w;
       }
+      if (!fronts) {
 #pragma unroll
-      for (uint32_t q = 0; q < 8u; q += 4) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(&src[kUSlotWords + q]);
-        dd[q] = v.x, dd[q + 1] = v.y, dd[q + 2] = v.z, dd[q + 3] = v.w;
+        for (uint32_t q = 0; q < 8u; q += 4) {
+          const u32x4 v = *reinterpret_cast<const u32x4*>(&src[kUSlotWords + q]);
+          dd[q] = v.x, dd[q + 1] = v.y, dd[q + 2] = v.z, dd[q + 3] = v.w;
+        }
+      }
+    }
+    // a flagged front's lane reads its slot itself (rare: the slots with more
+    // than 3 intervals, long intervals, overflow slots); the others unpack theirs into the same words
+    bool read_d = false;
+    if (fronts) {
+      const uint32_t f[kFrontWords] = {y[2].x, y[2].y, y[2].z, y[2].w};
+      read_d = ua && (uint32_t)lane < CPW && front_flagged(f);
+      front_unpack(f, dd);
+      if (!ua || (uint32_t)lane >= CPW || read_d) {
+#pragma unroll
+        for (uint32_t q = 0; q < 8u; ++q) dd[q] = 0u;
       }
     }
 #pragma unroll
     for (uint32_t q = 8; q < kDSlotWords; ++q) dd[q] = 0u;  // (empty intervals, as a fitting slot has them)
+    n_flag = (uint32_t)__popcll(__ballot(read_d));
+    if (__builtin_expect(n_flag != 0u, 0) && read_d) {  // (the whole slot: one round, not two)
+#pragma unroll
+      for (uint32_t q = 0; q < kDSlotWords; q += 4) {
+        const u32x4 h = slot_load((const GCK_GLOBAL u32x4*)(da + 4u * q));
+        dd[q] = h.x, dd[q + 1] = h.y, dd[q + 2] = h.z, dd[q + 3] = h.w;
+      }
+    }
     // second halves of the resource slots with more intervals (each lane its own check's)
-    const bool more_d = ua && !(dd[0] & kSlotOverflow) && dd[0] > kSlotHalfV;
+    const bool more_d = ua && !read_d && !(dd[0] & kSlotOverflow) && dd[0] > kSlotHalfV;
     if (__builtin_expect(__ballot(more_d) != 0, 0) && more_d) {
       const u32x4 h0 = slot_load((const GCK_GLOBAL u32x4*)(da + 32u));
       const u32x4 h1 = slot_load((const GCK_GLOBAL u32x4*)(da + 48u));
@@ -1378,6 +1419,7 @@ __device__ __forceinline__ uint32_t cj_block(const A& ax, const uint32_t blk, co
       t[8] = t_items;
       t[9] = t_slots;
       t[10] = t_slot1;
+      t[11] = n_flag;
     }
   }
   return blk_deferred;

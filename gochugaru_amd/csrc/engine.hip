@@ -2516,6 +2516,10 @@ static void publish_and_collect(Engine& e, Workspace& w) {
   w.ctr_clean = true;
 }
 
+// The closure join's per-wave timing records of an n-check batch: every wave of every block writes
+// one (closure.inc cj_block), and the variant with the most waves has 32 checks per wave, 4 waves per block.
+static size_t cj_timing_words(uint32_t n) { return (size_t)kCjTimingWords * kWaves * ((size_t)n / (32u * kWaves) + 1); }
+
 static BundleArgs bundle_args(Engine& e, Workspace& w, const gck_item* d_items, uint32_t n, uint8_t* d_perm,
                               int32_t* d_err) {
   BundleArgs a{};
@@ -2543,7 +2547,7 @@ static BundleArgs bundle_args(Engine& e, Workspace& w, const gck_item* d_items, 
   static const char* timing_env = debug_env("GCK_DEBUG_TIMING");
   // bundle records of stages A and B, then the closure join's per-wave records
   const size_t timing_words = (size_t)kTimingWords * (n + 1) * 2 +
-                              std::max((size_t)kCjTimingWords * (n / 64 + 1), (size_t)kLjTimingWords * (n / 16 + 1));
+                              std::max(cj_timing_words(n), (size_t)kLjTimingWords * (n / 16 + 1));
   if (timing_env && w.timing_cap < timing_words) {
     if (w.timing) (void)hipFree(w.timing);
     w.timing = nullptr;
@@ -3181,7 +3185,7 @@ static void debug_dump(Engine& e, Workspace& w, uint32_t n) {
   if (timing_env && w.timing) {
     HIP_OK(hipDeviceSynchronize());  // (a closure join publishes its batch before its last waves end)
     const size_t timing_words = (size_t)kTimingWords * (n + 1) * 2;
-    const size_t cj_words = std::max((size_t)kCjTimingWords * (n / 64 + 1), (size_t)kLjTimingWords * (n / 16 + 1));
+    const size_t cj_words = std::max(cj_timing_words(n), (size_t)kLjTimingWords * (n / 16 + 1));
     std::vector<unsigned long long> h(timing_words + cj_words);
     HIP_OK(hipMemcpy(h.data(), w.timing, (timing_words + cj_words) * 8, hipMemcpyDeviceToHost));
     std::string path = std::string(timing_env) + ".bin";

@@ -2070,6 +2070,16 @@ int gck_test_slot_pack(uint32_t bits, const uint32_t* raw, uint32_t n, uint32_t 
   return (int)m;
 }
 
+// gck_test_front_pack: the 16-B front (slot_pack.hpp) of the 16-word resource slot `slot`, as the
+// slot-build kernel writes it, into front[4]; when it packed, the 8 slot words it stands for into
+// unpacked[8] (untouched otherwise). Returns 1 packed, 0 flagged "read the slot", -1 bad arguments.
+int gck_test_front_pack(const uint32_t* slot, uint32_t* front, uint32_t* unpacked) {
+  if (!slot || !front || !unpacked) return -1;
+  if (!gck::front_pack(slot, front)) return 0;
+  gck::front_unpack(front, unpacked);
+  return 1;
+}
+
 // gck_test_select_plane: the ordered selection of k_dc_select (select_plane.hpp) over a chunk's plane
 // of n_words words on the host, tile by tile as the kernel's blocks take it: a tile's first rank is
 // `base` (the request's count before the chunk) plus a recount of the words before the tile, ranks

@@ -118,4 +118,60 @@ GCK_SLOT_HD inline void slot_pack_plain_list(uint32_t bits, uint32_t count, uint
   w[kUSlotWords - 1] = list_at;
 }
 
+// ---- the 16-B front of a resource slot (24-bit snapshots) ----------------------------------------
+// A resource slot (closure.inc kDSlotWords: word 0 the interval count or kSlotOverflow, word 1 zero,
+// words 2 + 2k, 3 + 2k interval k as [start, end)) is read at random once per check; four fronts
+// share the 64-B line that one slot fills, so more of them stay in the Infinity Cache between two
+// uses. A front holds what the first half of a slot holds, in 128 bits:
+//   word k (k < 3)  bits 0-23 start of interval k, bits 24-31 the low 8 bits of its length
+//   word 3          bits 10k .. 10k+9 the high 10 bits of the length of interval k; bits 30-31 the count
+// Lengths are kFrontLenBits (18) bits, starts 24, counts 0-3; unused intervals are zero. A resource
+// whose slot does not fit — more than 3 intervals, an overflow slot, a nonzero word 1, a start of
+// 2^24 or more, a length of 0 or above 2^18 - 1 (an end below its start wraps to one) — has the
+// all-ones front kFrontReadSlot instead (the "read the slot" flag: in band, 2 + 3 x 42 bits leave
+// none over), and so has a slot whose packed form would be all ones. The join then decides the
+// check from its 64-B slot exactly as without fronts.
+constexpr uint32_t kFrontWords = 4;
+constexpr uint32_t kFrontV = 3;         // intervals of a front (= closure.inc kSlotHalfV)
+constexpr uint32_t kFrontLenBits = 18;  // + 24 bits of start = 42 per interval
+constexpr uint32_t kFrontLenMax = (1u << kFrontLenBits) - 1u;
+constexpr uint32_t kFrontReadSlot = 0xFFFFFFFFu;  // every word of a flagged front
+
+GCK_SLOT_HD inline bool front_flagged(const uint32_t* f) { return (f[0] & f[1] & f[2] & f[3]) == kFrontReadSlot; }
+
+// The front of the slot d (16 words); returns whether it packed (false: flagged).
+GCK_SLOT_HD inline bool front_pack(const uint32_t* d, uint32_t* f) {
+  bool ok = !(d[0] & kSlotOverflow) && d[0] <= kFrontV && d[1] == 0u;
+  for (uint32_t k = 0; k < kFrontWords; ++k) f[k] = 0u;
+  for (uint32_t k = 0; k < kFrontV && ok; ++k) {
+    const uint32_t lo = d[2 + 2 * k], len = d[3 + 2 * k] - lo;
+    if (k >= d[0]) {
+      ok = lo == 0u && d[3 + 2 * k] == 0u;  // (an unused interval is empty in the slot too)
+      continue;
+    }
+    if (lo >> 24 || len == 0u || len > kFrontLenMax) {
+      ok = false;
+      continue;
+    }
+    f[k] = lo | (len & 255u) << 24;
+    f[3] |= (len >> 8) << (10u * k);
+  }
+  for (uint32_t k = 2 + 2 * kFrontV; k < 16u && ok; ++k) ok = d[k] == 0u;  // (the slot's second half: empty)
+  if (ok) f[3] |= d[0] << 30;
+  if (!ok || front_flagged(f))
+    for (uint32_t k = 0; k < kFrontWords; ++k) f[k] = kFrontReadSlot;
+  return !front_flagged(f);
+}
+
+// Words 0-7 of the slot a packed (not flagged) front stands for; the slot's words 8-15 are zero.
+GCK_SLOT_HD inline void front_unpack(const uint32_t* f, uint32_t* d) {
+  d[0] = f[3] >> 30;
+  d[1] = 0u;
+  for (uint32_t k = 0; k < kFrontV; ++k) {
+    const uint32_t lo = f[k] & 0xFFFFFFu, len = f[k] >> 24 | (f[3] >> (10u * k) & 1023u) << 8;
+    d[2 + 2 * k] = lo;
+    d[3 + 2 * k] = lo + len;
+  }
+}
+
 }  // namespace gck

@@ -5,7 +5,7 @@ import sys
 import numpy as np
 
 TICK_US = 0.01
-W = 11  # closure.inc kCjTimingWords
+W = 12  # closure.inc kCjTimingWords
 
 
 def launches(path):
@@ -35,6 +35,14 @@ def list_round(recs):
     return (float(with_l.mean()), float(n_list.sum() / max(1, n_take.sum())), med(with_l), med(~with_l))
 
 
+def front_flags(recs):
+    """Word 11 of a wave's record: its checks whose 16-B resource front said "read the slot" (0
+    without fronts). Returns (share of waves with such a check, share of checks)."""
+    a = np.concatenate(recs)
+    n_take, n_flag = a[:, 7] & 0xFFFFFFFF, a[:, 11]
+    return float((n_flag > 0).mean()), float(n_flag.sum() / max(1, n_take.sum()))
+
+
 def main(path):
     spans, recs, raw = [], [], []
     for r in launches(path):
@@ -59,6 +67,8 @@ def main(path):
     w_share, c_share, med_with, med_without = list_round(raw)
     print(f"list round (1b): {100 * w_share:.1f} % of waves, {100 * c_share:.2f} % of checks; "
           f"median lists phase {med_with:.2f} us with one, {med_without:.2f} us without")
+    fw, fc = front_flags(raw)
+    print(f"flagged fronts (slot read instead): {100 * fw:.1f} % of waves, {100 * fc:.2f} % of checks")
 
 
 if __name__ == "__main__":

@@ -11,7 +11,10 @@ layouts of a user slot are counted (gochugaru_amd/csrc/slot_pack.hpp):
   dedup    ... with more sorted unique entries than a slot holds
   window   ... and neither an inline entry nor the omitted window decides the check
 The timing build's phase dump (tools/analyze_cj.py, "list round (1b)") reports the same two
-shares from the device. torch's CPU and GPU generators give different graphs from one seed, and
+shares from the device. Beside them, `front_flag`: the checks whose document's 16-B front (slot_pack.hpp
+front_pack) says "read the slot" — more than 3 viewer groups, or a group whose interval is longer
+than 2^18 - 1 labels or starts at 2^24 or later — and the waves that hold one (analyze_cj.py,
+"flagged fronts"). torch's CPU and GPU generators give different graphs from one seed, and
 the heavy tail of the group sizes moves the shares from instance to instance (raw: 5.2 % of the
 checks at 2e7 tuples, 3.4 % at 1e8, 4.1 % at 4e8, 4.2 % at 1e9, all on the CPU), so a prediction
 for the graph the device runs is made with --device cuda: the graph and the checks are generated
@@ -28,6 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CAP = {24: 20, 32: 15}
 SORT_MAX = 64
 CPW = 32  # checks per wave of the flagship variant
+FRONT_V, FRONT_LEN_MAX, FRONT_START_END = 3, (1 << 18) - 1, 1 << 24  # slot_pack.hpp kFrontV, kFrontLenMax, 24-bit starts
 
 
 def labels_and_covers(n_groups, g_off, g_nbr):
@@ -99,7 +103,8 @@ def main():
     group_of = np.repeat(np.arange(G.n_groups, dtype=np.int32), np.diff(u_off))[order]
     del order
     cap, n_in = CAP[a.bits], CAP[a.bits] - 2
-    tot = {k: [0, 0] for k in ("raw", "dedup", "window")}  # listed checks, waves with one
+    tot = {k: [0, 0] for k in ("raw", "dedup", "window", "front_flag")}  # listed / flagged checks, waves with one
+    unfit = np.concatenate([[0], np.cumsum(((end - pre > FRONT_LEN_MAX) | (pre >= FRONT_START_END))[v_nbr])])
     n_checks = n_waves = 0
     raw_sizes = []
     for seed in a.seeds:
@@ -107,6 +112,7 @@ def main():
         docs, users = items[:, 1].astype(np.int64), items[:, 3].astype(np.int64)
         b, e_ = np.searchsorted(sorted_users, users, "left"), np.searchsorted(sorted_users, users, "right")
         flags = {k: np.zeros(len(users), dtype=bool) for k in tot}
+        flags["front_flag"] = (v_off[docs + 1] - v_off[docs] > FRONT_V) | (unfit[v_off[docs + 1]] - unfit[v_off[docs]] > 0)
         for i in range(len(users)):
             gs = group_of[b[i]:e_[i]]
             raw = [int(pre[c]) for g in gs for c in cover[g]]

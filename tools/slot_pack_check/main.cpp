@@ -8,6 +8,7 @@
 // Random entry sets of 1-64 raw entries (duplicates, dense blocks, both ends of the range) at both
 // entry widths: the packed slot's inline entries and omitted run together are the sorted unique
 // set, the run's open range is the narrowest, and every omitted entry lies strictly inside it.
+// Then the 16-B resource fronts: what packs, what is flagged, and the round trip.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -92,6 +93,36 @@ int main() {
     REQUIRE((w[0] & (kSlotLoOpen | kSlotHiOpen)) == (kSlotLoOpen | kSlotHiOpen) && slot_list_off(w) == 7u);
     for (uint32_t k = 0; k < n_in; ++k) REQUIRE(entry(bits, w, k) == unused);
   }
-  std::printf("slot_pack ok: %ld listed, %ld inline\n", listed, fits);
-  return listed > 5000 && fits > 5000 ? 0 : 1;
+  // resource fronts: random slots of 0-7 intervals with lengths around the 18-bit edge; a front
+  // packs exactly when the slot has at most 3 intervals that all fit, and then unpacks to the
+  // slot's first eight words
+  long packed = 0, flagged = 0;
+  for (int it = 0; it < 40000; ++it) {
+    uint32_t d[16] = {}, f[kFrontWords], u[8];
+    const uint32_t n = (uint32_t)(rng() % 8);
+    bool fit = n <= kFrontV;
+    d[0] = n;
+    for (uint32_t k = 0; k < n && k < 7; ++k) {
+      const uint32_t lo = (uint32_t)(rng() % (1u << 24)) + ((rng() % 16 == 0) ? 1u << 24 : 0u);
+      const uint32_t edge[] = {0u, 1u, 255u, 256u, kFrontLenMax - 1, kFrontLenMax, kFrontLenMax + 1, 1u << 20};
+      const uint32_t len = rng() % 2 ? edge[rng() % 8] : 1u + (uint32_t)(rng() % kFrontLenMax);
+      d[2 + 2 * k] = lo, d[3 + 2 * k] = lo + len;
+      fit = fit && lo < (1u << 24) && len >= 1 && len <= kFrontLenMax;
+    }
+    if (it % 50 == 0) d[0] = kSlotOverflow, fit = false;
+    const bool ok = front_pack(d, f);
+    REQUIRE(ok == !front_flagged(f));
+    bool all_ones = n == 3;  // (the one packed form that reads as the flag)
+    for (uint32_t k = 0; k < 3 && all_ones; ++k) all_ones = d[2 + 2 * k] == 0xFFFFFFu && d[3 + 2 * k] - d[2 + 2 * k] == kFrontLenMax;
+    REQUIRE(ok == (fit && !all_ones));
+    if (!ok) {
+      ++flagged;
+      continue;
+    }
+    ++packed;
+    front_unpack(f, u);
+    for (uint32_t k = 0; k < 8; ++k) REQUIRE(u[k] == d[k]);
+  }
+  std::printf("slot_pack ok: %ld listed, %ld inline; fronts: %ld packed, %ld flagged\n", listed, fits, packed, flagged);
+  return listed > 5000 && fits > 5000 && packed > 2000 && flagged > 5000 ? 0 : 1;
 }
