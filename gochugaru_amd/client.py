@@ -539,6 +539,42 @@ class Client:
         except Exception as e:  # noqa: BLE001 — Go returns (nil, err)
             return None, e
 
+    def FilterCrossSubjectsDevice(self, ctx: Optional[Context], cs: Optional[Strategy], resource_permission: str,
+                                  resources, subject_type: str, subjects, limit: int = 0):
+        """``FilterCrossDevice`` by resource — an access review, a share dialog, a notification fan-out:
+        for each of ``resources``, which of ``subjects`` may see it (HAS or CONDITIONAL) — with
+        ``limit``, the first ``limit`` of them in the subject list's order. Returns
+        ``((col_off, ids), err)``: ``ids[col_off[r]:col_off[r + 1]]`` are the subject ids that may see
+        resource r, both device tensors, selected and compacted by kernels over the finished plane
+        (Engine.filter_cross_cols_ids); only two count words come back to the host, and a per-item
+        error is ``err``. Parsing and error mapping are ``FilterCrossDevice``'s."""
+        self.checkOverlap(ctx)
+        try:
+            import torch
+            obj_type, obj_rel = _rel.ParseTypedRelation(resource_permission)
+            stype, srel_name, _ = _rel._cut(subject_type, "#")
+            for what, t in (("resources", resources), ("subjects", subjects)):
+                if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.uint32) or not t.is_cuda:
+                    raise InvalidArgument(f"FilterCrossSubjectsDevice: the {what} must be a device int32 / uint32 "
+                                          "tensor of interned ids")
+            if limit < 0:
+                raise InvalidArgument("FilterCrossSubjectsDevice: the limit must not be negative")
+            requirement, revision = _requirement(cs)
+            eng = self.engine
+
+            def run():
+                # resolved per attempt, as CheckCross does
+                rt, st = eng.type_id(obj_type), eng.type_id(stype)
+                perm = eng.relation_id(rt, obj_rel)
+                srel = ELLIPSIS if srel_name in ("", "...") else eng.relation_id(st, srel_name)
+                if TYPE_INVALID in (rt, st) or REL_INVALID in (perm, srel):
+                    raise GckError(GCK_E_NOT_FOUND, "object definition or relation not found")
+                return eng.filter_cross_cols_ids((rt, perm, st, srel), subjects, resources, col_limit=limit,
+                                                 requirement=requirement, revision=revision)
+            return retryRetriableErrors(ctx or Background, run), None
+        except Exception as e:  # noqa: BLE001 — Go returns (nil, err)
+            return None, e
+
     # ---- snapshot plumbing (ReadSchema + ExportRelationships at its revision) -------------
     def LoadSnapshot(self, schema: str, revision: int, relationships: Iterable) -> None:
         """Ingest the output of ``ReadSchema`` (client/client.go:416-422) and

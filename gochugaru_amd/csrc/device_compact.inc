@@ -399,6 +399,140 @@ void device_select_rows_empty(Engine& e, const gck_select_rows& sel, size_t S, v
   HIP_OK(hipStreamSynchronize((hipStream_t)stream));
 }
 
+// A cross filter request by resource (include/gck.h gck_filter_cross_cols_device): the mirror of the
+// step above, a column-segmented selection over the same finished row-padded plane, in the same two
+// places. k_dc_cols_count: what each column keeps, into col_off[r + 1] (and its survivors into
+// col_n[r]); k_dc_rows_scan, as it is, over (col_off, R, out_n); k_dc_cols_write: the kept survivors'
+// records at col_off[r] + j, j ascending with s.
+// The mapping (select_plane.hpp): a block is kColGroup = 64 columns — the plane's word-columns
+// 2 * blockIdx and 2 * blockIdx + 1 — by kColChunks = 16 waves. It takes the S rows in tiles of
+// kColTile = 2,048: the tile's two words per row go to LDS by one coalesced read, all of it in
+// flight at once, and every later look at the plane is an LDS read. Lane l of wave k has column
+// 64 * blockIdx + l and rows [k * n, (k + 1) * n) of the tile, n = ceil(rows of the tile / 16). A
+// thread counts its column in its chunk; the 16 counts of a column meet in LDS, and the chunks before
+// a thread's own (and the tiles before, a running count) are its carried in-column rank. One block
+// walks all S rows of its 64 columns: a plane of millions of subjects by a handful of resources (the
+// expanded path only; an in-place plane is one tile) selects slowly but correctly.
+struct DcCols {
+  const unsigned long long* plane;
+  uint32_t S, R, stride, mask, col_limit;
+  uint32_t* col_off;
+  uint32_t* col_n;
+  gck::SelectColsOut o;
+};
+
+constexpr int kColBlock = (int)(gck::kColGroup * gck::kColChunks);
+static_assert(gck::kColGroup == 64u && kColBlock <= 1024, "a column per lane, a chunk per wave, one block");
+
+struct DcColsLds {
+  uint64_t tile[gck::kColTile][2];                  // the block's two word-columns of the tile's rows
+  uint32_t part[gck::kColChunks][gck::kColGroup];  // a column's survivors per chunk
+};
+
+// Rows [t0, t0 + T) of the block's two word-columns into lds.tile; a word-column beyond the row
+// (stride odd, the last block) is staged as 0, which never survives. The caller's barrier follows.
+__device__ inline void dc_cols_stage(const DcCols& a, DcColsLds& lds, uint32_t t0, uint32_t T) {
+  const uint64_t* plane = reinterpret_cast<const uint64_t*>(a.plane);
+  const uint32_t w0 = 2u * blockIdx.x;
+#pragma unroll 4
+  for (uint32_t i = threadIdx.x; i < 2u * T; i += (uint32_t)kColBlock) {
+    const uint32_t row = i >> 1, t = w0 + (i & 1u);
+    lds.tile[row][i & 1u] = t < a.stride ? plane[(size_t)(t0 + row) * a.stride + t] : 0ull;
+  }
+}
+
+// This thread's chunk of a staged tile of T rows: its first row in the tile and its number of rows.
+__device__ inline void dc_cols_chunk(uint32_t T, uint32_t& r0, uint32_t& n) {
+  const uint32_t per = gck::select_col_chunk_rows(T);
+  r0 = min(T, (threadIdx.x >> 6) * per);
+  n = min(per, T - r0);
+}
+
+// Every thread of the block reaches every barrier below: a thread whose column is beyond R stages
+// words as the others do, counts 0 and writes nothing.
+__global__ void __launch_bounds__(kColBlock) k_dc_cols_count(DcCols a) {
+  __shared__ DcColsLds lds;
+  const uint32_t lane = threadIdx.x & 63u, chunk = threadIdx.x >> 6, c = blockIdx.x * gck::kColGroup + lane;
+  uint32_t met = 0;
+  for (uint32_t t0 = 0; t0 < a.S; t0 += min(gck::kColTile, a.S - t0)) {  // (t0 never wraps)
+    const uint32_t T = min(gck::kColTile, a.S - t0);
+    dc_cols_stage(a, lds, t0, T);
+    __syncthreads();
+    uint32_t r0, n;
+    dc_cols_chunk(T, r0, n);
+    met += gck::select_col_walk(&lds.tile[r0][lane >> 5], 2, a.R, a.mask, c, t0 + r0, n, nullptr, 0u, 0u, 0u);
+    __syncthreads();  // (the tile is restaged)
+  }
+  lds.part[chunk][lane] = met;
+  __syncthreads();
+  if (chunk != 0u || c >= a.R) return;
+  uint32_t surv = 0;
+  for (uint32_t k = 0; k < gck::kColChunks; ++k) surv += lds.part[k][lane];
+  a.col_off[c + 1u] = gck::select_row_kept(surv, a.col_limit);
+  if (a.col_n) a.col_n[c] = surv;
+}
+
+__global__ void __launch_bounds__(kColBlock) k_dc_cols_write(DcCols a) {
+  __shared__ DcColsLds lds;
+  const uint32_t lane = threadIdx.x & 63u, chunk = threadIdx.x >> 6, c = blockIdx.x * gck::kColGroup + lane;
+  // (read beside the first tile's words, not behind them)
+  const uint32_t base = c < a.R ? a.col_off[c] : 0u, kept = c < a.R ? a.col_off[c + 1u] - base : 0u;  // (the scan's: min(surv, col_limit))
+  uint32_t carry = 0;  // the column's survivors in the tiles before this one
+  for (uint32_t t0 = 0; t0 < a.S; t0 += min(gck::kColTile, a.S - t0)) {
+    const uint32_t T = min(gck::kColTile, a.S - t0);
+    dc_cols_stage(a, lds, t0, T);
+    __syncthreads();
+    uint32_t r0, n;
+    dc_cols_chunk(T, r0, n);
+    const uint64_t* mine = &lds.tile[r0][lane >> 5];
+    lds.part[chunk][lane] = gck::select_col_walk(mine, 2, a.R, a.mask, c, t0 + r0, n, nullptr, 0u, 0u, 0u);
+    __syncthreads();
+    uint32_t rank = carry;
+    for (uint32_t k = 0; k < gck::kColChunks; ++k) {
+      const uint32_t p = lds.part[k][lane];
+      if (k < chunk) rank += p;
+      carry += p;
+    }
+    if (rank < kept && base + rank < a.o.cap) gck::select_col_walk(mine, 2, a.R, a.mask, c, t0 + r0, n, &a.o, rank, base, kept);
+    __syncthreads();  // (the tile and the counts are rewritten)
+  }
+}
+
+// The three kernels on `st`; the caller waits. R == 0 writes col_off[0] and *out_n alone; S == 0 (no
+// plane read) writes R + 1 zeros and R zero column counts.
+static void dc_select_cols(const gck_select_cols& sel, const unsigned long long* plane, size_t S, size_t R,
+                           const uint32_t* subjects, hipStream_t st) {
+  DcCols a{};
+  a.plane = plane;
+  a.S = (uint32_t)S;
+  a.R = (uint32_t)R;
+  a.stride = (uint32_t)((R + 31u) / 32u);
+  a.mask = sel.mask;
+  a.col_limit = sel.col_limit;
+  a.col_off = sel.d_out_col_off;
+  a.col_n = sel.d_out_col_n;
+  a.o = gck::SelectColsOut{sel.d_out_ids, sel.d_out_row, sel.d_out_perm, (uint32_t)std::min<size_t>(sel.cap, 0xFFFFFFFFu),
+                           subjects};
+  const dim3 grid((a.R + gck::kColGroup - 1u) / gck::kColGroup), block(kColBlock);
+  if (a.R) {
+    hipLaunchKernelGGL(k_dc_cols_count, grid, block, 0, st, a);
+    HIP_OK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_dc_rows_scan, dim3(1), dim3(kBlock), 0, st, a.col_off, a.R, sel.d_out_n);
+  HIP_OK(hipGetLastError());
+  if (a.S && a.R && a.o.cap) {
+    hipLaunchKernelGGL(k_dc_cols_write, grid, block, 0, st, a);
+    HIP_OK(hipGetLastError());
+  }
+}
+
+// An empty cross filter request by resource (S == 0 or R == 0: no workspace, no check).
+void device_select_cols_empty(Engine& e, const gck_select_cols& sel, size_t R, void* stream) {
+  HIP_OK(hipSetDevice(e.device));
+  dc_select_cols(sel, nullptr, 0, R, nullptr, (hipStream_t)stream);
+  HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+}
+
 // The word a device request counts its errors in, cleared on `st` before the request's first chunk:
 // the caller's, or the workspace's own (which stays 0 until an emit adds to it).
 // (the caller's word of a submitted batch is left to the batch: CompactRun::zero_cnt)
@@ -509,6 +643,10 @@ static void device_collect(Engine& e, Workspace& w) {
     // a submitted cross filter request: this batch was its one tile or chunk, so the plane is finished
     // once the kernels above have run on this stream
     dc_select_rows(c.rsel, c.out, c.rsel_S, c.R, c.rsel_ids, st);
+    launched = true;
+  }
+  if (c.select_cols) {  // (its twin by resource: the same finished plane, by column)
+    dc_select_cols(c.csel, c.out, c.csel_S, c.R, c.csel_ids, st);
     launched = true;
   }
   // (the count's clear — and the kernels above — are complete when the wait returns; a batch on the

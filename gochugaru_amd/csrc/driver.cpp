@@ -44,6 +44,10 @@ using submit_filter_cross_device_fn = int (*)(gck_engine*, const gck_consistency
                                               size_t, const uint32_t*, size_t, const char* const*, const size_t*, size_t,
                                               int64_t, const gck_select_rows*, uint64_t*, gck_item_error*, size_t,
                                               uint32_t*, uint32_t, void*, gck_batch**);
+using submit_filter_cross_cols_device_fn = int (*)(gck_engine*, const gck_consistency*, const gck_uniform*,
+                                                   const uint32_t*, size_t, const uint32_t*, size_t, const char* const*,
+                                                   const size_t*, size_t, int64_t, const gck_select_cols*, uint64_t*,
+                                                   gck_item_error*, size_t, uint32_t*, uint32_t, void*, gck_batch**);
 
 // Optional per-batch timeline of the next loops (gckd_set_trace): for batch k, the seconds after
 // the loop's start at which its submit and its wait returned (stamps[2k], stamps[2k + 1]).
@@ -276,6 +280,37 @@ int gckd_run_filter_cross_device(submit_filter_cross_device_fn submit, wait_fn w
     sel.d_out_row_n = reinterpret_cast<uint32_t*>(row_n[k]);
     sel.d_out_ids = reinterpret_cast<uint32_t*>(out_ids[k]);
     sel.d_out_col = reinterpret_cast<uint32_t*>(out_col[k]);
+    sel.d_out_perm = reinterpret_cast<uint8_t*>(out_perm[k]);
+    sel.cap = cap;
+    sel.d_out_n = reinterpret_cast<uint32_t*>(out_n[k]);
+    return submit(e, cs, hdrs + k, reinterpret_cast<const uint32_t*>(subjects[k]), (size_t)n_subjects[k],
+                  reinterpret_cast<const uint32_t*>(resources[k]), (size_t)n_resources[k], nullptr, nullptr, 0, now_us,
+                  &sel, reinterpret_cast<uint64_t*>(packed[k]), reinterpret_cast<gck_item_error*>(errs[k]), err_cap,
+                  reinterpret_cast<uint32_t*>(n_errs[k]), flags, reinterpret_cast<void*>(streams[k % depth]), b);
+  });
+}
+
+// Its twin by resource (gck_filter_submit_cross_cols_device): request k's CSR is col_off[k]
+// (n_resources[k] + 1 entries), col_n[k], out_ids[k], out_row[k], out_perm[k] (cap entries each; 0: not
+// wanted) and the count word out_n[k], under the one mask and column limit.
+int gckd_run_filter_cross_cols_device(submit_filter_cross_cols_device_fn submit, wait_fn wait, gck_engine* e,
+                                      const gck_consistency* cs, size_t n_batches, const gck_uniform* hdrs,
+                                      const uint64_t* subjects, const uint64_t* n_subjects, const uint64_t* resources,
+                                      const uint64_t* n_resources, uint32_t mask, uint32_t col_limit,
+                                      const uint64_t* col_off, const uint64_t* col_n, const uint64_t* out_ids,
+                                      const uint64_t* out_row, const uint64_t* out_perm, size_t cap, const uint64_t* out_n,
+                                      const uint64_t* packed, const uint64_t* errs, size_t err_cap, const uint64_t* n_errs,
+                                      uint32_t depth, const uint64_t* streams, uint32_t flags, int64_t now_us,
+                                      double* seconds) {
+  if (depth == 0) depth = 1;
+  return run_loop(n_batches, depth, wait, e, seconds, [&](size_t k, gck_batch** b) {
+    gck_select_cols sel{};  // (copied by the call)
+    sel.mask = mask;
+    sel.col_limit = col_limit;
+    sel.d_out_col_off = reinterpret_cast<uint32_t*>(col_off[k]);
+    sel.d_out_col_n = reinterpret_cast<uint32_t*>(col_n[k]);
+    sel.d_out_ids = reinterpret_cast<uint32_t*>(out_ids[k]);
+    sel.d_out_row = reinterpret_cast<uint32_t*>(out_row[k]);
     sel.d_out_perm = reinterpret_cast<uint8_t*>(out_perm[k]);
     sel.cap = cap;
     sel.d_out_n = reinterpret_cast<uint32_t*>(out_n[k]);

@@ -252,6 +252,11 @@ struct CompactRun {
   gck_select_rows rsel{};
   const uint32_t* rsel_ids = nullptr;  // the request's resource list
   size_t rsel_S = 0;
+  // its twin by resource (CompactReq::sel_cols; dc_select_cols): the request's subject list and S
+  bool select_cols = false;
+  gck_select_cols csel{};
+  const uint32_t* csel_ids = nullptr;
+  size_t csel_S = 0;
   bool in_place() const { return mode == kInPlace; }
   bool table_join() const { return mode == kInPlace && indexed; }  // the join reads index bytes and a shape table
 };
@@ -4032,6 +4037,13 @@ void device_submit_compact(Engine& e, Workspace* w, const CompactReq& req, int64
     w->cb.rsel_S = q.S;
     w->cb.out = reinterpret_cast<unsigned long long*>(q.packed);
   }
+  if (q.sel_cols) {  // (likewise: its collect selects the columns)
+    w->cb.select_cols = true;
+    w->cb.csel = *q.sel_cols;
+    w->cb.csel_ids = q.subjects;
+    w->cb.csel_S = q.S;
+    w->cb.out = reinterpret_cast<unsigned long long*>(q.packed);
+  }
 }
 
 // The chunks of a request that is no cross request: max_batch checks each, rounded down to a multiple
@@ -4088,6 +4100,10 @@ void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const Compact
       // every band or chunk is collected — its stream completed — so the plane is finished: the row
       // selection over the whole of it, then the wait
       dc_select_rows(*q.sel_rows, reinterpret_cast<const unsigned long long*>(q.packed), q.S, q.R, q.resources, w0->stream);
+      HIP_OK(hipStreamSynchronize(w0->stream));
+    }
+    if (q.sel_cols) {  // (the same place, for the selection by resource)
+      dc_select_cols(*q.sel_cols, reinterpret_cast<const unsigned long long*>(q.packed), q.S, q.R, q.subjects, w0->stream);
       HIP_OK(hipStreamSynchronize(w0->stream));
     }
     return;

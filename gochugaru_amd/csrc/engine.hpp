@@ -457,9 +457,14 @@ struct CompactReq {
   // whole plane is finished, each row's kept survivors go to *sel_rows' arrays as a CSR (copied by
   // the submit; device_compact.inc dc_select_rows)
   const gck_select_rows* sel_rows = nullptr;
+  // a cross filter request by resource (gck_filter_cross_cols_device): sel_rows' twin — each column's
+  // kept survivors, as a CSR by resource (device_compact.inc dc_select_cols). At most one of the two
+  const gck_select_cols* sel_cols = nullptr;
 };
 // The outputs of an empty cross filter request (S == 0 or R == 0), synchronous on `stream`.
 void device_select_rows_empty(Engine& e, const gck_select_rows& sel, size_t S, void* stream);
+// Likewise by resource: col_off[0] and the count alone for R == 0, else R + 1 zero offsets.
+void device_select_cols_empty(Engine& e, const gck_select_cols& sel, size_t R, void* stream);
 // *d_n_errs = 0 for an empty device request (synchronous on `stream`; a null pointer: nothing).
 void device_zero_count(Engine& e, uint32_t* d_n_errs, void* stream);
 // Synchronous: chunks of max_batch & ~31 checks over w0 and w1 (as device_check_host); a cross

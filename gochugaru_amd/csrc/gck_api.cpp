@@ -1716,6 +1716,101 @@ int gck_filter_submit_cross_device(gck_engine* ge, const gck_consistency* cs, co
   });
 }
 
+// ---- cross filter requests by resource (include/gck.h gck_filter_cross_cols_device) -----------
+
+// The selection's own argument rules, shared with the host hook (gck_test_select_cols): null when
+// the selection is good, else what is wrong with it.
+static const char* select_cols_fault(const gck_select_cols* sel) {
+  const auto aligned = [](const void* p) { return ((uintptr_t)p & 3u) == 0; };
+  if (!sel) return "cross filter request by resource: null gck_select_cols";
+  if (sel->mask == 0 || (sel->mask & ~0xEu))
+    return "cross filter request by resource: mask must select among GCK_SELECT_NO, GCK_SELECT_HAS and "
+           "GCK_SELECT_CONDITIONAL";
+  if (!sel->d_out_col_off) return "cross filter request by resource: null d_out_col_off";
+  if (!sel->d_out_n) return "cross filter request by resource: null d_out_n";
+  if (sel->cap != 0 && !sel->d_out_ids && !sel->d_out_row && !sel->d_out_perm)
+    return "cross filter request by resource: cap > 0 without an output array";
+  if (!aligned(sel->d_out_col_off) || !aligned(sel->d_out_col_n) || !aligned(sel->d_out_ids) ||
+      !aligned(sel->d_out_row) || !aligned(sel->d_out_n))
+    return "cross filter request by resource: d_out_col_off, d_out_col_n, d_out_ids, d_out_row or d_out_n is not "
+           "4-byte aligned";
+  return nullptr;
+}
+
+// filter_cross_request's twin: the selection against the call, before anything is launched or
+// written; then the cross device request with it (`sel` is the caller's: the engine copies it).
+static CompactReq filter_cross_cols_request(const gck_select_cols* sel, const gck_uniform* hdr, const uint32_t* d_subjects,
+                                            size_t S, const uint32_t* d_resources, size_t R, size_t n_contexts,
+                                            uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                            uint32_t* d_out_n_errs, void* stream, bool engine_stream) {
+  const char* fault = select_cols_fault(sel);
+  REQUIRE(!fault, GCK_E_INVALID_ARGUMENT, fault ? fault : "");
+  REQUIRE(d_out_packed, GCK_E_INVALID_ARGUMENT, "cross filter request by resource: null d_out_packed");
+  CompactReq q = cross_device_request(hdr, d_subjects, S, d_resources, R, n_contexts, d_out_packed, d_out_errs, err_cap,
+                                      d_out_n_errs, stream, engine_stream);
+  q.sel_cols = sel;
+  return q;
+}
+
+int gck_filter_cross_cols_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr,
+                                 const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                                 size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                                 size_t n_contexts, int64_t now_us, const gck_select_cols* sel,
+                                 uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                 uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision) {
+  return guard([&] {
+    Engine& e = need(ge);
+    const CompactReq req = filter_cross_cols_request(sel, hdr, d_subjects, n_subjects, d_resources, n_resources,
+                                                     n_contexts, d_out_packed, d_out_errs, err_cap, d_out_n_errs, stream,
+                                                     true);
+    const CallCtx c{cs, contexts, context_lens, n_contexts};
+    if (req.n == 0) {  // (no check runs: the count word, then the offsets and counts of R empty columns)
+      check_device_sync(e, c, req, now_us, out_revision);
+      return device_select_cols_empty(e, *sel, n_resources, stream);
+    }
+    // (the workspaces of gck_check_bulk_cross_device)
+    uint32_t rows = 0;
+    const size_t mb = max_batch_of(e);
+    const size_t one = gck_cross_tile_device(n_subjects, n_resources, mb, &rows) ? (size_t)rows * n_resources
+                                                                                 : (mb & ~(size_t)31);
+    check_sync(e, c, req.n, one, out_revision,
+               [&](Workspace* w0, Workspace* w1, const CavCall& cav) { device_check_compact(e, w0, w1, req, now_us, cav); });
+  });
+}
+
+int gck_filter_submit_cross_cols_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr,
+                                        const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                                        size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                                        size_t n_contexts, int64_t now_us, const gck_select_cols* sel,
+                                        uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                        uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    check_submit_flags(flags);
+    const bool own = (flags & GCK_SUBMIT_ENGINE_STREAM) != 0;
+    const CompactReq req = filter_cross_cols_request(sel, hdr, d_subjects, n_subjects, d_resources, n_resources,
+                                                     n_contexts, d_out_packed, d_out_errs, err_cap, d_out_n_errs, stream,
+                                                     own);
+    uint32_t rows = 0;
+    REQUIRE(req.n == 0 || (gck_cross_tile_device(n_subjects, n_resources, max_batch_of(e), &rows) && rows == n_subjects),
+            GCK_E_INVALID_ARGUMENT,
+            "submitted cross filter request by resource of " + std::to_string(n_subjects) + " x " +
+                std::to_string(n_resources) + " is not one tile (gck_cross_tile_device)");
+    gck_batch* b = submit_device(e, {cs, contexts, context_lens, n_contexts}, req, now_us);
+    if (req.n == 0) {
+      try {
+        device_select_cols_empty(e, *sel, n_resources, own ? nullptr : stream);
+      } catch (...) {
+        delete b;
+        throw;
+      }
+    }
+    *out = b;
+  });
+}
+
 int gck_device_compact_stats(gck_engine* ge, uint64_t out[2]) {
   return guard([&] {
     Engine& e = need(ge);
@@ -2151,6 +2246,80 @@ int gck_test_select_rows(const uint64_t* words, uint32_t S, uint32_t R, uint32_t
       }
       carry = rank;
       if (row_limit && carry >= row_limit) break;
+    }
+  }
+  return 0;
+}
+
+// gck_test_select_cols: the column-segmented selection of a cross filter request by resource
+// (select_plane.hpp; k_dc_cols_count, k_dc_rows_scan and k_dc_cols_write in device_compact.inc) over a
+// row-padded plane of S rows of ceil(R / 32) words on the host, with the same functions and the same
+// walk: blocks of kColGroup columns, the rows in tiles of kColTile, each tile's rows of a column in
+// kColChunks chunks counted one by one (select_col_walk, in its batches of words) into a block's
+// table, the prefix, then each chunk written from the rank the chunks and the tiles before it carry.
+// Only the staging differs: the kernels read a tile's words from LDS, this reads them from the plane.
+// Outputs and NULL rules are gck_select_cols' (src_ids: the subject list, needed with out_ids). -1 for
+// the selection's argument errors. What this does not pin is the staging and the barriers between a
+// block's waves: the GPU tests' ground.
+int gck_test_select_cols(const uint64_t* words, uint32_t S, uint32_t R, uint32_t mask, uint32_t col_limit, size_t cap,
+                         const uint32_t* src_ids, uint32_t* out_col_off, uint32_t* out_col_n, uint32_t* out_ids,
+                         uint32_t* out_row, uint8_t* out_perm, uint32_t* out_n) {
+  gck_select_cols sel{mask, col_limit, out_col_off, out_col_n, out_ids, out_row, out_perm, cap, out_n};
+  if (select_cols_fault(&sel)) return -1;
+  const uint32_t stride = (R + 31u) / 32u;
+  if ((!words && S && stride) || (out_ids && !src_ids && S)) return -1;
+  if (S && R && S > 0xFFFFFFFFu / R) return -1;
+  const gck::SelectColsOut o{out_ids, out_row, out_perm, (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu), src_ids};
+  const uint32_t blocks = (R + gck::kColGroup - 1u) / gck::kColGroup;
+  // part[chunk][lane] of a block's tile, as the kernels' LDS table; walk: one thread's chunk of the tile at row t0
+  uint32_t part[gck::kColChunks][gck::kColGroup];
+  const auto walk = [&](uint32_t blk, uint32_t t0, uint32_t T, uint32_t chunk, uint32_t lane, const gck::SelectColsOut* out,
+                        uint32_t rank, uint32_t base, uint32_t kept) -> uint32_t {
+    const uint32_t c = blk * gck::kColGroup + lane, per = gck::select_col_chunk_rows(T);
+    const uint32_t r0 = std::min(T, chunk * per), n = std::min(per, T - r0);
+    if (c >= R) return 0u;  // (the kernels stage a zero word for it)
+    return gck::select_col_walk(words + (size_t)(t0 + r0) * stride + (c >> 5), stride, R, mask, c, t0 + r0, n, out, rank,
+                                base, kept);
+  };
+  const auto count_tile = [&](uint32_t blk, uint32_t t0, uint32_t T) {
+    for (uint32_t chunk = 0; chunk < gck::kColChunks; ++chunk)
+      for (uint32_t lane = 0; lane < gck::kColGroup; ++lane)
+        part[chunk][lane] = walk(blk, t0, T, chunk, lane, nullptr, 0u, 0u, 0u);
+  };
+  for (uint32_t blk = 0; blk < blocks; ++blk) {  // k_dc_cols_count
+    uint32_t surv[gck::kColGroup] = {};
+    for (uint32_t t0 = 0; t0 < S; t0 += std::min(gck::kColTile, S - t0)) {
+      count_tile(blk, t0, std::min(gck::kColTile, S - t0));
+      for (uint32_t chunk = 0; chunk < gck::kColChunks; ++chunk)
+        for (uint32_t lane = 0; lane < gck::kColGroup; ++lane) surv[lane] += part[chunk][lane];
+    }
+    for (uint32_t lane = 0; lane < gck::kColGroup; ++lane) {
+      const uint32_t c = blk * gck::kColGroup + lane;
+      if (c >= R) continue;
+      out_col_off[c + 1u] = gck::select_row_kept(surv[lane], col_limit);
+      if (out_col_n) out_col_n[c] = surv[lane];
+    }
+  }
+  uint32_t run = 0;  // k_dc_rows_scan
+  for (uint32_t r = 0; r < R; ++r) out_col_off[r + 1u] = run += out_col_off[r + 1u];
+  out_col_off[0] = 0u;
+  *out_n = run;
+  for (uint32_t blk = 0; blk < blocks && S && o.cap; ++blk) {  // k_dc_cols_write
+    uint32_t carry[gck::kColGroup] = {};
+    for (uint32_t t0 = 0; t0 < S; t0 += std::min(gck::kColTile, S - t0)) {
+      const uint32_t T = std::min(gck::kColTile, S - t0);
+      count_tile(blk, t0, T);
+      for (uint32_t chunk = 0; chunk < gck::kColChunks; ++chunk)
+        for (uint32_t lane = 0; lane < gck::kColGroup; ++lane) {
+          const uint32_t c = blk * gck::kColGroup + lane;
+          if (c >= R) continue;
+          uint32_t rank = carry[lane];
+          for (uint32_t k = 0; k < chunk; ++k) rank += part[k][lane];
+          const uint32_t base = out_col_off[c], kept = out_col_off[c + 1u] - base;
+          if (rank < kept && base + rank < o.cap) walk(blk, t0, T, chunk, lane, &o, rank, base, kept);
+        }
+      for (uint32_t chunk = 0; chunk < gck::kColChunks; ++chunk)
+        for (uint32_t lane = 0; lane < gck::kColGroup; ++lane) carry[lane] += part[chunk][lane];
     }
   }
   return 0;

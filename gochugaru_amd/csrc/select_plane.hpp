@@ -4,7 +4,8 @@
 // host code compiles as well as the device (k_dc_select in device_compact.inc calls it; gck_api.cpp
 // exports it for the tests as gck_test_select_plane). Below them, the row-segmented form over a cross
 // request's row-padded plane (gck_filter_cross_device; k_dc_rows_count / k_dc_rows_write, and
-// gck_test_select_rows on the host).
+// gck_test_select_rows on the host), and its mirror, the column-segmented form
+// (gck_filter_cross_cols_device; k_dc_cols_count / k_dc_cols_write, gck_test_select_cols).
 //
 // A word holds 32 checks, check b in bits 2b .. 2b + 1 (GCK_PERM_*: 0 unspecified — an errored check
 // and a tail lane alike —, 1 NO, 2 HAS, 3 CONDITIONAL). `mask` has bit v set when value v survives
@@ -131,6 +132,78 @@ GCK_SEL_HD inline void select_write_row(uint64_t word, uint64_t m, uint32_t col0
     if (o.perm) o.perm[at] = (uint8_t)((word >> bit) & 3u);
     ++rank;
   }
+}
+
+// ---- the column-segmented selection over a cross plane (include/gck.h gck_filter_cross_cols_device) ----
+// The mirror: column r of the same row-padded plane keeps its first kept_r survivors in ascending s,
+// at ranks col_off[r] + j of the request. The kernels (k_dc_cols_count, k_dc_cols_write) and the host
+// hook (gck_test_select_cols) give a column to a thread. A block has kColGroup columns — two
+// word-columns of the plane — and takes the S rows in tiles of kColTile rows, whose two words per row
+// it stages in LDS with one coalesced read; a tile is cut into kColChunks chunks of consecutive rows,
+// one per wave. A thread counts its column in its chunk; the chunks before it (summed through LDS) and
+// the tiles before (a running count) are its carried in-column rank, and it then walks its chunk
+// downward writing records — ordered by construction, no atomics and no lane exchange.
+
+constexpr uint32_t kColGroup = 64;    // columns of a block: one per lane of a wave (two word-columns)
+constexpr uint32_t kColChunks = 16;   // row chunks of a tile: one per wave
+constexpr uint32_t kColTile = 2048;   // rows of a tile (an in-place plane, at most 2,048 words, is one tile)
+constexpr uint32_t kColBatch = 8;     // words a thread reads before it looks at them
+
+// The rows of one chunk of a tile of T rows: the chunks are [k * n, min(T, (k + 1) * n)), the last
+// ones empty when T is small.
+GCK_SEL_HD inline uint32_t select_col_chunk_rows(uint32_t T) { return (T + kColChunks - 1u) / kColChunks; }
+
+// Column c of a row of R checks, `word` the row's word c / 32: its GCK_PERM_* when it survives
+// `mask`, else 0. Agrees with bit 2 (c % 32) of select_row_mask(word, mask, c / 32, R): a padding
+// column of the row's last word (c >= R) never survives, whatever the plane holds there.
+GCK_SEL_HD inline uint32_t select_col_perm(uint64_t word, uint32_t mask, uint32_t c, uint32_t R) {
+  const uint32_t v = (uint32_t)(word >> (2u * (c & 31u))) & 3u;
+  return c < R && ((mask >> v) & 1u) ? v : 0u;
+}
+
+// Where the kept survivors go: any of the three arrays may be null; `cap` entries each. A
+// survivor's id is src_ids[s], s its row.
+struct SelectColsOut {
+  uint32_t* ids;
+  uint32_t* row;
+  uint8_t* perm;
+  uint32_t cap;
+  const uint32_t* src_ids;
+};
+
+// The record of the survivor in row s (perm: its GCK_PERM_*) at rank `at` of the request; at < cap.
+GCK_SEL_HD inline void select_write_col(uint32_t s, uint32_t perm, uint32_t at, const SelectColsOut& o) {
+  if (o.ids) o.ids[at] = o.src_ids[s];
+  if (o.row) o.row[at] = s;
+  if (o.perm) o.perm[at] = (uint8_t)perm;
+}
+
+// One chunk of one column as a thread walks it: rows s0 .. s0 + n - 1, the column's word of row
+// s0 + i at words[i * step] (the staged tile on the device, the plane itself on the host), in batches
+// of kColBatch words read first and looked at after. Returns the survivors met.
+// With `o` the survivors are also written: the first of the chunk has in-column rank `rank`, the
+// column's records start at `base` of the request and it keeps `kept` of its survivors; the walk ends
+// at the first survivor beyond `kept` or beyond cap (ranks ascend, so every later one is beyond too).
+GCK_SEL_HD inline uint32_t select_col_walk(const uint64_t* words, size_t step, uint32_t R, uint32_t mask, uint32_t c,
+                                           uint32_t s0, uint32_t n, const SelectColsOut* o, uint32_t rank, uint32_t base,
+                                           uint32_t kept) {
+  uint32_t met = 0;
+  for (uint32_t i = 0; i < n; i += kColBatch) {  // (n <= kColTile: i never wraps)
+    uint64_t w[kColBatch];
+#pragma unroll
+    for (uint32_t k = 0; k < kColBatch; ++k) w[k] = k < n - i ? words[(size_t)(i + k) * step] : 0ull;  // (0: never survives)
+#pragma unroll
+    for (uint32_t k = 0; k < kColBatch; ++k) {
+      const uint32_t v = select_col_perm(w[k], mask, c, R);
+      if (!v) continue;
+      ++met;
+      if (!o) continue;
+      if (rank >= kept || base + rank >= o->cap) return met;
+      select_write_col(s0 + i + k, v, base + rank, *o);
+      ++rank;
+    }
+  }
+  return met;
 }
 
 }  // namespace gck

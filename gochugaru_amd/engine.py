@@ -171,6 +171,14 @@ class SelectRows(C.Structure):
                 ("d_out_perm", C.c_void_p), ("cap", C.c_size_t), ("d_out_n", C.c_void_p)]
 
 
+class SelectCols(C.Structure):
+    """gck_select_cols (include/gck.h): which Permissionships survive a cross filter request by
+    resource, how many each resource keeps, and the device arrays of the CSR they go to."""
+    _fields_ = [("mask", C.c_uint32), ("col_limit", C.c_uint32), ("d_out_col_off", C.c_void_p),
+                ("d_out_col_n", C.c_void_p), ("d_out_ids", C.c_void_p), ("d_out_row", C.c_void_p),
+                ("d_out_perm", C.c_void_p), ("cap", C.c_size_t), ("d_out_n", C.c_void_p)]
+
+
 SELECT_NO = 1 << PERM_NO                       # GCK_SELECT_NO
 SELECT_HAS = 1 << PERM_HAS                     # GCK_SELECT_HAS
 SELECT_CONDITIONAL = 1 << PERM_CONDITIONAL     # GCK_SELECT_CONDITIONAL
@@ -399,6 +407,14 @@ _SIGS = {
                                                  C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t,
                                                  C.c_int64, C.POINTER(SelectRows), _P, _P, C.c_size_t, _P, C.c_uint32,
                                                  _P, C.POINTER(_P)]),
+    "gck_filter_cross_cols_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), _P, C.c_size_t, _P,
+                                               C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t,
+                                               C.c_int64, C.POINTER(SelectCols), _P, _P, C.c_size_t, _P, _P,
+                                               C.POINTER(C.c_uint64)]),
+    "gck_filter_submit_cross_cols_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), _P, C.c_size_t,
+                                                      _P, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                                      C.c_size_t, C.c_int64, C.POINTER(SelectCols), _P, _P, C.c_size_t,
+                                                      _P, C.c_uint32, _P, C.POINTER(_P)]),
     "gck_lookup_resources_among": (C.c_int, [_P, C.POINTER(_Consistency), C.c_uint16, C.c_uint16, C.c_uint16,
                                              C.c_uint16, C.c_uint32, _P, C.c_size_t, C.c_int64, _P, _P, C.c_size_t,
                                              C.POINTER(C.c_size_t)]),
@@ -539,6 +555,8 @@ def _driver():
                                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                                    C.c_int64, C.POINTER(C.c_double)]
+        d.gckd_run_filter_cross_cols_device.restype = C.c_int
+        d.gckd_run_filter_cross_cols_device.argtypes = list(d.gckd_run_filter_cross_device.argtypes)  # (its twin)
         d.gckd_set_trace.restype = None
         d.gckd_set_trace.argtypes = [C.c_void_p, C.c_size_t]
         _DRIVER = d
@@ -1494,6 +1512,121 @@ class Engine:
             out += (out_perm[:total],)
         return out
 
+    # ---- cross filter requests by resource (gck_filter_cross_cols_device): the mirror — each resource's
+    # surviving subjects as a CSR. d_out_col_off: R + 1 u32 (required); d_out_n: one u32 (required);
+    # d_out_col_n: R u32, 0: not wanted; d_out_ids / d_out_row (u32) and d_out_perm (u8): `cap` entries
+    # each, 0: not wanted; d_out_packed is required.
+    def filter_cross_cols_device(self, header, d_subjects: int, n_subjects: int, d_resources: int, n_resources: int,
+                                 d_out_col_off: int, d_out_n: int, cap: int, d_out_packed: int, d_out_ids: int = 0,
+                                 d_out_row: int = 0, d_out_perm: int = 0, d_out_col_n: int = 0,
+                                 select: int = SELECT_LOOKUP, col_limit: int = 0, d_out_errs: int = 0, err_cap: int = 0,
+                                 d_out_n_errs: int = 0, stream: Optional[int] = None,
+                                 requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                                 contexts: Optional[Sequence] = None) -> int:
+        """gck_filter_cross_cols_device: check_cross_device, then for each resource the subjects whose
+        Permissionship `select` (SELECT_*) names, in the subject list's order and at most `col_limit` of
+        them (0: all): column offsets, ids, rows and Permissionships into the device arrays, their number
+        into *d_out_n. A per-item error does not fail the call. Returns the evaluated revision."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        sel = SelectCols(select, col_limit, d_out_col_off or None, d_out_col_n or None, d_out_ids or None,
+                         d_out_row or None, d_out_perm or None, cap, d_out_n or None)
+        rev = C.c_uint64(0)
+        _check(self._lib.gck_filter_cross_cols_device(self._h, C.byref(cs), C.byref(hdr), d_subjects or None,
+                                                      n_subjects, d_resources or None, n_resources, *tail[:4],
+                                                      C.byref(sel), *tail[4:], stream, C.byref(rev)))
+        return rev.value
+
+    def submit_filter_cross_cols_device(self, header, d_subjects: int, n_subjects: int, d_resources: int,
+                                        n_resources: int, d_out_col_off: int, d_out_n: int, cap: int, d_out_packed: int,
+                                        d_out_ids: int = 0, d_out_row: int = 0, d_out_perm: int = 0,
+                                        d_out_col_n: int = 0, select: int = SELECT_LOOKUP, col_limit: int = 0,
+                                        d_out_errs: int = 0, err_cap: int = 0, d_out_n_errs: int = 0,
+                                        stream: Optional[int] = None, engine_stream: bool = False,
+                                        requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                                        contexts: Optional[Sequence] = None) -> "DeviceCompactBatch":
+        """gck_filter_submit_cross_cols_device (one device tile): as submit_cross_device, with
+        filter_cross_cols_device's outputs."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        sel = SelectCols(select, col_limit, d_out_col_off or None, d_out_col_n or None, d_out_ids or None,
+                         d_out_row or None, d_out_perm or None, cap, d_out_n or None)
+        b = DeviceCompactBatch(self, hdr)
+        _check(self._lib.gck_filter_submit_cross_cols_device(self._h, C.byref(cs), C.byref(hdr), d_subjects or None,
+                                                             n_subjects, d_resources or None, n_resources, *tail[:4],
+                                                             C.byref(sel), *tail[4:],
+                                                             SUBMIT_ENGINE_STREAM if engine_stream else 0, stream,
+                                                             C.byref(b._h)))
+        return b
+
+    def prepare_filter_cross_cols_device(self, headers, subjects, n_subjects, resources, n_resources, col_off, out_n,
+                                         cap: int, packed, depth: int, out_ids=None, out_row=None, out_perm=None,
+                                         col_n=None, select: int = SELECT_LOOKUP, col_limit: int = 0, errs=None,
+                                         err_cap: int = 0, n_errs=None, streams=None, engine_streams: bool = True,
+                                         now_us: int = 0) -> "PreparedFilterCrossColsDevice":
+        """The compiled loop over cross filter requests by resource (gckd_run_filter_cross_cols_device): as
+        prepare_filter_cross_device, with request k's CSR into col_off[k] / out_ids[k] / out_row[k] /
+        out_perm[k] (`cap` entries; None: not wanted), its columns' survivor counts into col_n[k] and the
+        total into out_n[k], all under the one `select` and `col_limit`."""
+        return PreparedFilterCrossColsDevice(self, headers, subjects, n_subjects, resources, n_resources, select,
+                                             col_limit, col_off, col_n, out_ids, out_row, out_perm, cap, out_n, packed,
+                                             errs, err_cap, depth, n_errs, streams, engine_streams, now_us)
+
+    def filter_cross_cols_ids(self, header, subjects, resources, select: int = SELECT_LOOKUP, col_limit: int = 0,
+                              want_row: bool = False, want_perm: bool = False,
+                              requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                              contexts: Optional[Sequence] = None):
+        """For each of `resources` the `subjects` that may see it — device int32 / uint32 tensors of ids —
+        as a CSR of torch tensors: (col_off, ids), col_off an int32 [R + 1] tensor and ids (in the
+        subjects' dtype) the kept survivors of resource r at col_off[r] .. col_off[r + 1], in the subject
+        list's order; then their rows (int32) and Permissionships (uint8) when asked for. `col_limit`:
+        at most so many per resource (0: all). Runs filter_cross_cols_device on the current stream with
+        outputs allocated on the tensors' device (cap = R * (col_limit or S)) and reads the two count
+        words — the call's only copy to the host. A per-item error raises GckError with the lookups'
+        message."""
+        import torch
+        for name, t in (("subjects", subjects), ("resources", resources)):
+            if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.uint32) or not t.is_cuda:
+                raise GckError(GCK_E_INVALID_ARGUMENT,
+                               f"filter_cross_cols_ids: {name} must be a device int32 / uint32 tensor")
+        if subjects.device != resources.device:
+            raise GckError(GCK_E_INVALID_ARGUMENT, "filter_cross_cols_ids: the two lists are on different devices")
+        subjects, resources = subjects.contiguous().reshape(-1), resources.contiguous().reshape(-1)
+        S, R, dev = subjects.numel(), resources.numel(), subjects.device
+        cap = R * (min(col_limit, S) if col_limit else S)
+        with torch.cuda.device(dev):
+            plane = torch.empty(max(1, S * ((R + 31) // 32)), dtype=torch.int64, device=dev)  # (required, also when empty)
+            col_off = torch.empty(R + 1, dtype=torch.int32, device=dev)
+            counts = torch.empty(2, dtype=torch.int32, device=dev)  # [kept survivors, errors]
+            out_ids = torch.empty(cap, dtype=subjects.dtype, device=dev)
+            out_row = torch.empty(cap, dtype=torch.int32, device=dev) if want_row else None
+            out_perm = torch.empty(cap, dtype=torch.uint8, device=dev) if want_perm else None
+            err = torch.empty(2, dtype=torch.int32, device=dev)  # the first error record
+            self.filter_cross_cols_device(header, subjects.data_ptr() if S * R else 0, S,
+                                          resources.data_ptr() if S * R else 0, R, col_off.data_ptr(),
+                                          counts.data_ptr(), cap, plane.data_ptr(),
+                                          d_out_ids=out_ids.data_ptr() if cap else 0,
+                                          d_out_row=out_row.data_ptr() if want_row and cap else 0,
+                                          d_out_perm=out_perm.data_ptr() if want_perm and cap else 0, select=select,
+                                          col_limit=col_limit, d_out_errs=err.data_ptr(), err_cap=1,
+                                          d_out_n_errs=counts.data_ptr() + 4,
+                                          stream=torch.cuda.current_stream(dev).cuda_stream, requirement=requirement,
+                                          revision=revision, now_us=now_us, contexts=contexts)
+            total, n_errs = (int(x) & 0xFFFFFFFF for x in counts.tolist())
+            if n_errs:
+                code = int(err[1].item())
+                raise GckError(GCK_E_INVALID_ARGUMENT,
+                               ITEM_ERROR_MESSAGES[ITEM_ERR_MAX_DEPTH] if code == ITEM_ERR_MAX_DEPTH
+                               else f"lookup failed: per-item error {code}")
+        out = (col_off, out_ids[:total])
+        if want_row:
+            out += (out_row[:total],)
+        if want_perm:
+            out += (out_perm[:total],)
+        return out
+
     def device_compact_stats(self) -> Tuple[int, int]:
         """gck_device_compact_stats: chunks of device requests whose join read and wrote the caller's
         device buffers in place, and chunks expanded to items on the device."""
@@ -1960,6 +2093,24 @@ class PreparedFilterCrossDevice(_Prepared):
         hdrs = (Uniform * max(1, len(headers)))(*[_header(h) for h in headers])
         self._args = (hdrs, arr(subjects), arr(n_subjects), arr(resources), arr(n_resources), select, row_limit,
                       arr(row_off), opt(row_n), opt(out_ids), opt(out_col), opt(out_perm), cap, arr(out_n), arr(packed),
+                      opt(errs), err_cap, opt(n_errs), depth, arr(streams or [0]),
+                      SUBMIT_ENGINE_STREAM if engine_streams else 0, now_us)
+
+
+class PreparedFilterCrossColsDevice(_Prepared):
+    """A compiled submit/wait loop over cross filter requests by resource
+    (Engine.prepare_filter_cross_cols_device)."""
+
+    def __init__(self, engine, headers, subjects, n_subjects, resources, n_resources, select, col_limit, col_off,
+                 col_n, out_ids, out_row, out_perm, cap, out_n, packed, errs, err_cap, depth, n_errs, streams,
+                 engine_streams, now_us):
+        super().__init__(engine, "gckd_run_filter_cross_cols_device", "gck_filter_submit_cross_cols_device",
+                         len(subjects), depth)
+        arr = self._arr
+        opt = lambda xs: arr(xs or [0] * len(subjects))
+        hdrs = (Uniform * max(1, len(headers)))(*[_header(h) for h in headers])
+        self._args = (hdrs, arr(subjects), arr(n_subjects), arr(resources), arr(n_resources), select, col_limit,
+                      arr(col_off), opt(col_n), opt(out_ids), opt(out_row), opt(out_perm), cap, arr(out_n), arr(packed),
                       opt(errs), err_cap, opt(n_errs), depth, arr(streams or [0]),
                       SUBMIT_ENGINE_STREAM if engine_streams else 0, now_us)
 

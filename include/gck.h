@@ -60,6 +60,9 @@
  *   gck_filter_cross_device / gck_filter_submit_cross_device
  *       the cross device request likewise: each subject's surviving resources, optionally the first K
  *       of them, compacted by kernels into a CSR (row offsets, ids, columns, Permissionships).
+ *   gck_filter_cross_cols_device / gck_filter_submit_cross_cols_device
+ *       its mirror: each resource's surviving subjects, optionally the first K of them, as a CSR by
+ *       resource (column offsets, ids, rows, Permissionships).
  *
  * Ownership: all inputs and outputs are caller-allocated; the engine never retains a caller
  * pointer after a call returns, except that gck_check_submit keeps the output pointers (and, for
@@ -745,7 +748,8 @@ int gck_filter_submit_list_device(gck_engine* e, const gck_consistency* cs, cons
  * NULL, a d_out_row_off, d_out_row_n, d_out_ids, d_out_col or d_out_n that is not 4-byte aligned, and
  * everything the cross device call refuses. gck_device_compact_stats counts the request as a cross
  * device request.
- * Out of scope: the mirror — per-resource rows of surviving subjects — would need a transposed plane. */
+ * The mirror — per-resource rows of surviving subjects — is gck_filter_cross_cols_device, below.
+ * Out of scope: a form without a plane; the three kernels of a one-tile plane fused into one launch. */
 typedef struct gck_select_rows {
   uint32_t mask;           /* GCK_SELECT_*: as gck_select.mask (bit 0 clear, != 0, <= 0xE) */
   uint32_t row_limit;      /* 0: keep every survivor; else keep at most this many per subject, the first in list order */
@@ -769,6 +773,67 @@ int gck_filter_submit_cross_device(gck_engine* e, const gck_consistency* cs, con
                                    size_t n_contexts, int64_t now_us, const gck_select_rows* sel,
                                    uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
                                    uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out);
+
+/* ---- cross filter requests by resource (ABI 13, additive) -----------------------------
+ * The mirror of gck_filter_cross_device: "for each of these resources, which of these subjects" — an
+ * access review, a share dialog, a notification fan-out — the survivors of every COLUMN of the same
+ * finished plane, compacted by kernels into a CSR by resource in the caller's device memory. Nothing
+ * but the two count words (*d_out_n, *d_out_n_errs) ever needs to cross PCIe.
+ * The check itself is the cross device call's, unchanged in every respect, exactly as for
+ * gck_filter_cross_device: the tiling and the block layout read in place, the expansion on the device
+ * (check contexts, R >= GCK_CROSS_IDS, thin requests and the other fallbacks), stream ordering and
+ * `flags`, consistency and the evaluated revision, the error records (index = s * R + r), the request
+ * errors and the one-tile rule of the submit form. d_out_packed is required and is written exactly as
+ * gck_check_bulk_cross_device writes it: the plane stays row-padded, S rows of ceil(R / 32) words.
+ * Check (s, r) survives iff it has no per-item error and (sel->mask >> perm) & 1. Column r has surv_r
+ * survivors and keeps kept_r = col_limit ? min(surv_r, col_limit) : surv_r of them, the first in
+ * ascending s (the first K permitted subjects of the subject list's order).
+ *   d_out_col_off: col_off[0] = 0, col_off[r + 1] = col_off[r] + kept_r; all R + 1 entries are always
+ *     written, whatever cap is. With R == 0 only col_off[0] and *d_out_n (= 0) are written, besides the
+ *     error count word; with S == 0 all R + 1 entries are 0 (and d_out_col_n, when given, R zeros).
+ *   records: kept survivor j of column r has rank col_off[r] + j; its subject id (d_subjects[s]), its
+ *     position s in the subject list and its GCK_PERM_* go to every array that is not NULL iff
+ *     rank < cap. Entries at and beyond min(total, cap) stay untouched.
+ *   d_out_col_n[r] = surv_r (before col_limit) when the array is given; *d_out_n = col_off[R], always
+ *     written.
+ * Ids are reported as often as the subject list repeats them; the selection reads d_subjects, which
+ * stays valid until the synchronous call or the wait returns (the cross device call's lifetime rule).
+ * A per-item error does not fail the call: the errored check never survives and the caller holds the
+ * count word. An empty request (S == 0 or R == 0) does not touch gck_device_compact_stats; any other
+ * is counted there as a cross device request.
+ * `sel` is copied by the call (the submit call included). GCK_E_INVALID_ARGUMENT, nothing launched and
+ * nothing written, for sel == NULL, a bad mask (gck_select's rule: 0, bit 0 set, above 0xE),
+ * d_out_col_off == NULL, d_out_n == NULL, d_out_packed == NULL, cap > 0 with all three record arrays
+ * NULL, a d_out_col_off, d_out_col_n, d_out_ids, d_out_row or d_out_n that is not 4-byte aligned, and
+ * everything the cross device call refuses.
+ * Cost: the selection kernels run one block per 64 resources, and each block walks all S rows of its
+ * columns, 16 chunks of rows side by side. An in-place tile has S * ceil(R / 32) <= max_batch / 32 words, so that walk is
+ * short; a huge, thin expanded plane (millions of subjects by a handful of resources) selects slowly
+ * but correctly.
+ * Out of scope: a form without a plane; the three kernels of a one-tile plane fused into one launch. */
+typedef struct gck_select_cols {
+  uint32_t mask;           /* GCK_SELECT_*: as gck_select.mask (bit 0 clear, != 0, <= 0xE) */
+  uint32_t col_limit;      /* 0: keep every survivor; else keep at most this many per resource, the first in subject-list order */
+  uint32_t* d_out_col_off; /* device, R + 1 entries, required */
+  uint32_t* d_out_col_n;   /* device, R entries, may be NULL: survivors of column r BEFORE col_limit */
+  uint32_t* d_out_ids;     /* device, cap entries, may be NULL: d_subjects[s] of a kept survivor */
+  uint32_t* d_out_row;     /* device, cap entries, may be NULL: its position s in the subject list */
+  uint8_t*  d_out_perm;    /* device, cap entries, may be NULL: its GCK_PERM_* */
+  size_t    cap;
+  uint32_t* d_out_n;       /* device, required: kept survivors of the whole request (== col_off[R]) */
+} gck_select_cols;         /* 64 bytes */
+int gck_filter_cross_cols_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr,
+                                 const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                                 size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                                 size_t n_contexts, int64_t now_us, const gck_select_cols* sel,
+                                 uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                 uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision);
+int gck_filter_submit_cross_cols_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr,
+                                        const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                                        size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                                        size_t n_contexts, int64_t now_us, const gck_select_cols* sel,
+                                        uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                        uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out);
 
 /* ---- lookups (Client.LookupResources / LookupSubjects, client/client.go:508-599) -------- */
 /* Ids of the `resource_type` objects on which the subject has `permission` — HAS or CONDITIONAL,
