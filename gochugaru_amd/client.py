@@ -575,6 +575,55 @@ class Client:
         except Exception as e:  # noqa: BLE001 — Go returns (nil, err)
             return None, e
 
+    def _filter_groups(self, name: str, ctx, cs, permission: str, subject_type: str, owners, offsets, candidates,
+                       vary: int, limit: int):
+        self.checkOverlap(ctx)
+        try:
+            import torch
+            obj_type, obj_rel = _rel.ParseTypedRelation(permission)
+            stype, srel_name, _ = _rel._cut(subject_type, "#")
+            for what, t in (("owners", owners), ("offsets", offsets), ("candidates", candidates)):
+                if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.uint32) or not t.is_cuda:
+                    raise InvalidArgument(f"{name}: the {what} must be a device int32 / uint32 tensor")
+            if limit < 0:
+                raise InvalidArgument(f"{name}: the limit must not be negative")
+            requirement, revision = _requirement(cs)
+            eng = self.engine
+
+            def run():
+                # resolved per attempt, as CheckCross does
+                rt, st = eng.type_id(obj_type), eng.type_id(stype)
+                perm = eng.relation_id(rt, obj_rel)
+                srel = ELLIPSIS if srel_name in ("", "...") else eng.relation_id(st, srel_name)
+                if TYPE_INVALID in (rt, st) or REL_INVALID in (perm, srel):
+                    raise GckError(GCK_E_NOT_FOUND, "object definition or relation not found")
+                return eng.filter_groups_ids((rt, perm, st, srel), owners, offsets, candidates, vary=vary,
+                                             group_limit=limit, requirement=requirement, revision=revision)
+            return retryRetriableErrors(ctx or Background, run), None
+        except Exception as e:  # noqa: BLE001 — Go returns (nil, err)
+            return None, e
+
+    def FilterGroupsDevice(self, ctx: Optional[Context], cs: Optional[Strategy], permission: str, candidates, offsets,
+                           subject_type: str, subjects, limit: int = 0):
+        """A candidate list per subject — what a retrieval or ranking step returns, its own top-K for
+        each user: for each of ``subjects``, which of *its own* candidate resources
+        ``candidates[offsets[s]:offsets[s + 1]]`` it may see (HAS or CONDITIONAL) — with ``limit``, the
+        first ``limit`` of them in its candidates' order. Returns ``((row_off, ids), err)``:
+        ``ids[row_off[s]:row_off[s + 1]]`` are subject s's permitted candidates, both device tensors,
+        selected and compacted by kernels over the finished plane (Engine.filter_groups_ids); only two
+        count words come back to the host, and a per-item error — or malformed offsets — is ``err``.
+        Parsing, retry and error mapping are ``FilterCrossDevice``'s."""
+        return self._filter_groups("FilterGroupsDevice", ctx, cs, permission, subject_type, subjects, offsets, candidates,
+                                   VARY_RESOURCE, limit)
+
+    def FilterGroupSubjectsDevice(self, ctx: Optional[Context], cs: Optional[Strategy], resource_permission: str,
+                                  resources, subject_type: str, candidates, offsets, limit: int = 0):
+        """``FilterGroupsDevice``'s mirror: for each of ``resources``, which of *its own* candidate
+        subjects ``candidates[offsets[r]:offsets[r + 1]]`` may see it. Returns ``((row_off, ids), err)``,
+        ``ids[row_off[r]:row_off[r + 1]]`` the permitted candidate subjects of resource r."""
+        return self._filter_groups("FilterGroupSubjectsDevice", ctx, cs, resource_permission, subject_type, resources,
+                                   offsets, candidates, VARY_SUBJECT, limit)
+
     # ---- snapshot plumbing (ReadSchema + ExportRelationships at its revision) -------------
     def LoadSnapshot(self, schema: str, revision: int, relationships: Iterable) -> None:
         """Ingest the output of ``ReadSchema`` (client/client.go:416-422) and

@@ -28,6 +28,10 @@
 // the caller's own buffer when that is in block layout already), and k_dc_emit maps a padded index to
 // the request's. Expanded, its chunks of the row-major sequence end inside plane words, so the plane
 // is cleared once and k_dc_cross_pack ORs each result into its word.
+//
+// A group filter request (gck_filter_groups_device) is a uniform device request whose pairs a kernel
+// writes: k_dc_group_pairs expands each chunk's (owner, candidate) pairs from the caller's CSR into the
+// workspace's dc_pairs, the chunk runs as above, and the group-segmented selection follows the last one.
 
 // The shapes of a request, by value in the kernarg segment (a uniform or list request: one entry).
 struct DcShapes {
@@ -533,6 +537,170 @@ void device_select_cols_empty(Engine& e, const gck_select_cols& sel, size_t R, v
   HIP_OK(hipStreamSynchronize((hipStream_t)stream));
 }
 
+// A group filter request (include/gck.h gck_filter_groups_device): S owners, each with its own run
+// of a flat candidate list, the runs given by S + 1 offsets in device memory. k_dc_group_check
+// validates the offsets once per request (the smallest bad s into a word the host reads at the end);
+// k_dc_group_pairs expands a chunk to the 8-B pairs a uniform device chunk's join reads, into the
+// workspace's dc_pairs; behind the last chunk the segmented selection over the dense plane —
+// k_dc_groups_count, k_dc_rows_scan as it is, k_dc_groups_write.
+// Nothing has validated the offsets when these kernels read them, so each of them stays in bounds
+// whatever they hold (select_plane.hpp select_group_of, select_group_range): a group index is within
+// [0, S - 1], a group's range within [0, n], a record's rank below cap.
+
+// Entry t of the S + 1 offsets against the rule off[0] == 0, off[s] <= off[s + 1], off[S] == n.
+__global__ void __launch_bounds__(kBlock) k_dc_group_check(const uint32_t* off, uint32_t S, uint32_t n, uint32_t* bad) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t > S) return;
+  const uint32_t v = off[t];
+  const bool wrong = (t == 0u && v != 0u) || (t == S && v != n) || (t < S && v > off[t + 1u]);
+  if (wrong) atomicMin(bad, t);
+}
+
+// Check pos + i of the request as a pair at pairs[i]: its group's owner and its own candidate, in
+// the order the joins read a pair (resource id in the low half). The candidate load and the pair
+// store are coalesced; the search reads the offsets, a few lines that stay in L2.
+struct DcGroupPairs {
+  const uint32_t* off;
+  const uint32_t* owners;
+  const uint32_t* candidates;
+  unsigned long long* pairs;
+  uint32_t S, pos, len, vary;
+};
+
+__global__ void __launch_bounds__(kBlock) k_dc_group_pairs(DcGroupPairs a) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.len) return;
+  const uint32_t k = a.pos + i;  // (pos + len <= n < 2^32)
+  const uint32_t own = a.owners[gck::select_group_of(a.off, a.S, k)], cand = a.candidates[k];
+  const uint32_t res = a.vary == GCK_VARY_SUBJECT ? own : cand, sub = a.vary == GCK_VARY_SUBJECT ? cand : own;
+  a.pairs[i] = (unsigned long long)sub << 32 | res;
+}
+
+static void dc_group_pairs(Workspace& w, const CompactReq& q, size_t pos, uint32_t len, hipStream_t st) {
+  DcGroupPairs a{q.group_off, q.owners, q.ids, w.dc_pairs, (uint32_t)q.S, (uint32_t)pos, len, q.vary};
+  if (len > w.max_batch) throw Error(GCK_E_DEVICE, "engine invariant violated: group chunk above max_batch");
+  hipLaunchKernelGGL(k_dc_group_pairs, dim3((len + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+  HIP_OK(hipGetLastError());
+}
+
+// The offsets' check on `st`, once per request and before its chunks: w.dc_aux[4] is 0xFFFFFFFF
+// afterwards, or the smallest s that breaks the rule.
+static void dc_group_check(Workspace& w, const CompactReq& q, hipStream_t st) {
+  HIP_OK(hipMemsetAsync(w.dc_aux + 4, 0xFF, 4, st));
+  hipLaunchKernelGGL(k_dc_group_check, dim3(((uint32_t)q.S + 1u + kBlock - 1) / kBlock), dim3(kBlock), 0, st, q.group_off,
+                     (uint32_t)q.S, (uint32_t)q.n, w.dc_aux + 4);
+  HIP_OK(hipGetLastError());
+}
+
+static void group_offsets_error(uint32_t s, size_t S, size_t n) {
+  throw Error(GCK_E_INVALID_ARGUMENT,
+              "group filter request: bad group offsets at s = " + std::to_string(s) + " (off[0] == 0, off[s] <= off[s + 1] and off[" +
+                  std::to_string(S) + "] == " + std::to_string(n) + " must hold)");
+}
+
+// The lane mapping of the count and the write kernel: a group takes L lanes of a wave (the host's
+// choice, select_group_lanes: a power of two within 1 .. 64), one plane word per lane, and a wave
+// carries 64 / L groups; a group of more than L words is walked in pieces of L words, the count or the
+// rank carried from piece to piece. Every lane stays in the kernel while the shuffles run — a lane
+// beyond S has an empty group — and a wave's loop runs while any of its groups has words left (a
+// ballot: wave-uniform).
+struct DcGroups {
+  const unsigned long long* plane;
+  const uint32_t* off;
+  uint32_t S, n, L, mask, group_limit;
+  uint32_t* row_off;
+  uint32_t* row_n;
+  gck::SelectRowsOut o;  // (src_ids: the candidates; col: a survivor's position k)
+};
+
+// This lane's group s, its lane j within the group, the group's range [lo, hi) and its words
+// [w0, w0 + nw).
+__device__ inline void dc_group_lane(const DcGroups& a, uint32_t& s, uint32_t& j, uint32_t& lo, uint32_t& hi, uint32_t& w0,
+                                     uint32_t& nw) {
+  const uint32_t lane = threadIdx.x & 63u, gw = blockIdx.x * (uint32_t)kWaves + (threadIdx.x >> 6);
+  s = gw * (64u / a.L) + lane / a.L;
+  j = lane & (a.L - 1u);
+  lo = hi = 0;
+  if (s < a.S) gck::select_group_range(a.off, s, a.n, lo, hi);
+  w0 = lo >> 5;
+  nw = hi > lo ? ((hi - 1u) >> 5) - w0 + 1u : 0u;
+}
+
+__global__ void __launch_bounds__(kBlock) k_dc_groups_count(DcGroups a) {
+  uint32_t s, j, lo, hi, w0, nw;
+  dc_group_lane(a, s, j, lo, hi, w0, nw);
+  const uint64_t* plane = reinterpret_cast<const uint64_t*>(a.plane);
+  uint32_t sum = 0;
+  for (uint32_t p0 = 0; __any(p0 < nw); p0 += a.L) {  // (nw <= 2^27: p0 never wraps)
+    const uint32_t t = p0 + j;
+    if (t < nw) sum += gck::select_count(gck::select_group_mask(plane[w0 + t], a.mask, w0 + t, lo, hi));
+  }
+  for (uint32_t d = a.L >> 1; d >= 1u; d >>= 1) sum += (uint32_t)__shfl_xor((int)sum, (int)d, 64);  // (d < L: inside the group's lanes)
+  if (j == 0u && s < a.S) {
+    a.row_off[s + 1u] = gck::select_row_kept(sum, a.group_limit);
+    if (a.row_n) a.row_n[s] = sum;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_dc_groups_write(DcGroups a) {
+  uint32_t s, j, lo, hi, w0, nw;
+  dc_group_lane(a, s, j, lo, hi, w0, nw);
+  const uint64_t* plane = reinterpret_cast<const uint64_t*>(a.plane);
+  const uint32_t lane = threadIdx.x & 63u, last = (lane | (a.L - 1u));  // the group's last lane
+  const uint32_t base = s < a.S ? a.row_off[s] : 0u;
+  uint32_t carry = 0;  // the group's survivors in the pieces before this one (the same in every lane of the group)
+  for (uint32_t p0 = 0; __any(p0 < nw && !(a.group_limit && carry >= a.group_limit)); p0 += a.L) {
+    const uint32_t t = p0 + j;
+    const uint64_t word = t < nw ? plane[w0 + t] : 0ull;
+    const uint64_t m = t < nw ? gck::select_group_mask(word, a.mask, w0 + t, lo, hi) : 0ull;
+    const uint32_t pc = gck::select_count(m);
+    uint32_t incl = pc;
+    for (uint32_t d = 1; d < a.L; d <<= 1) {
+      const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
+      if (j >= d) incl += up;  // (lane - d is inside the group's lanes)
+    }
+    gck::select_write_row(word, m, (w0 + t) * 32u, carry + incl - pc, base, a.group_limit, a.o);
+    carry += (uint32_t)__shfl((int)incl, (int)last, 64);
+  }
+}
+
+// The three kernels on `st`; the caller waits. S == 0 writes row_off[0] and *out_n alone; n == 0
+// reads neither the offsets nor a plane and writes S + 1 zeros and S zero counts.
+static void dc_select_groups(const gck_select_groups& sel, const unsigned long long* plane, const uint32_t* off, size_t S,
+                             size_t n, const uint32_t* candidates, hipStream_t st) {
+  DcGroups a{};
+  a.plane = plane;
+  a.off = off;
+  a.S = (uint32_t)S;
+  a.n = (uint32_t)n;
+  a.L = gck::select_group_lanes(a.n, a.S);
+  a.mask = sel.mask;
+  a.group_limit = sel.group_limit;
+  a.row_off = sel.d_out_row_off;
+  a.row_n = sel.d_out_row_n;
+  a.o = gck::SelectRowsOut{sel.d_out_ids, sel.d_out_pos, sel.d_out_perm, (uint32_t)std::min<size_t>(sel.cap, 0xFFFFFFFFu),
+                           candidates};
+  const uint32_t per_block = (uint32_t)kWaves * (64u / a.L);
+  const dim3 grid((a.S + per_block - 1u) / per_block), block(kBlock);
+  if (a.S) {
+    hipLaunchKernelGGL(k_dc_groups_count, grid, block, 0, st, a);
+    HIP_OK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_dc_rows_scan, dim3(1), block, 0, st, a.row_off, a.S, sel.d_out_n);
+  HIP_OK(hipGetLastError());
+  if (a.S && a.n && a.o.cap) {
+    hipLaunchKernelGGL(k_dc_groups_write, grid, block, 0, st, a);
+    HIP_OK(hipGetLastError());
+  }
+}
+
+// An empty group filter request (n == 0: no workspace, no check, no offset read).
+void device_select_groups_empty(Engine& e, const gck_select_groups& sel, size_t S, void* stream) {
+  HIP_OK(hipSetDevice(e.device));
+  dc_select_groups(sel, nullptr, nullptr, S, 0, nullptr, (hipStream_t)stream);
+  HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+}
+
 // The word a device request counts its errors in, cleared on `st` before the request's first chunk:
 // the caller's, or the workspace's own (which stays 0 until an emit adds to it).
 // (the caller's word of a submitted batch is left to the batch: CompactRun::zero_cnt)
@@ -558,7 +726,10 @@ static void dc_expand(Workspace& w, const CompactReq& q, size_t pos, uint32_t le
   DcExpand a{};
   DcShapes t{};
   std::memcpy(t.s, q.shapes, (size_t)q.n_shapes * sizeof(gck_uniform));
-  a.ids = q.cross() ? q.resources : q.list() ? (q.ids ? q.ids + pos : nullptr) : q.pairs + 2 * pos;
+  a.ids = q.cross() ? q.resources
+          : q.groups() ? reinterpret_cast<const uint32_t*>(w.dc_pairs)  // (a group chunk's pairs: dc_group_pairs, before this)
+          : q.list() ? (q.ids ? q.ids + pos : nullptr)
+                     : q.pairs + 2 * pos;
   if (q.cross()) {
     a.subs = q.subjects;
     a.R = (uint32_t)q.R;
@@ -569,7 +740,7 @@ static void dc_expand(Workspace& w, const CompactReq& q, size_t pos, uint32_t le
   a.bad = w.dc_aux + 1;
   a.n = len;
   a.n_shapes = q.n_shapes;
-  a.vary = q.vary;
+  a.vary = q.list() ? q.vary : 0u;
   a.fixed_id = q.fixed_id;
   a.first_id = q.first_id + (uint32_t)pos;
   if (a.shape_of) HIP_OK(hipMemsetAsync(w.dc_aux + 1, 0xFF, 4, st));
@@ -649,7 +820,16 @@ static void device_collect(Engine& e, Workspace& w) {
     dc_select_cols(c.csel, c.out, c.csel_S, c.R, c.csel_ids, st);
     launched = true;
   }
+  uint32_t bad_group = 0xFFFFFFFFu;
+  if (c.select_groups) {
+    // a submitted group filter request: this batch was its one chunk, so the dense plane is finished;
+    // the offsets' check ran on this stream before the chunk
+    dc_select_groups(c.gsel, c.out, c.gsel_off, c.gsel_S, n, c.gsel_ids, st);
+    HIP_OK(hipMemcpyAsync(&bad_group, w.dc_aux + 4, 4, hipMemcpyDeviceToHost, st));
+    launched = true;
+  }
   // (the count's clear — and the kernels above — are complete when the wait returns; a batch on the
   // caller's stream that launched nothing is ordered by that stream alone)
   if (launched || (w.b_own_stream && c.cnt_memset)) HIP_OK(hipStreamSynchronize(st));
+  if (bad_group != 0xFFFFFFFFu) group_offsets_error(bad_group, c.gsel_S, n);
 }

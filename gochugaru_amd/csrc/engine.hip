@@ -257,6 +257,14 @@ struct CompactRun {
   gck_select_cols csel{};
   const uint32_t* csel_ids = nullptr;
   size_t csel_S = 0;
+  // a submitted group filter request's batch (CompactReq::sel_groups): the whole request too, so its
+  // collect ends with the group selection over `out` (dc_select_groups) and reads the offsets' check
+  // word, which k_dc_group_check wrote on the batch's stream before the chunk
+  bool select_groups = false;
+  gck_select_groups gsel{};
+  const uint32_t* gsel_off = nullptr;  // the request's S + 1 offsets
+  const uint32_t* gsel_ids = nullptr;  // ... and its candidates
+  size_t gsel_S = 0;
   bool in_place() const { return mode == kInPlace; }
   bool table_join() const { return mode == kInPlace && indexed; }  // the join reads index bytes and a shape table
 };
@@ -309,9 +317,11 @@ struct Workspace {
   CompactBatch cb;            // the batch is a compact request's chunk (submit_compact)
   uint32_t* dc_bitmap = nullptr;  // device_compact.inc: one error bit per check of a device request's chunk (zero between batches)
   uint32_t* dc_aux = nullptr;     // ... [0] the errors so far of a request that gives no count word, [1] an expanded chunk's bad index,
-                                  // [2], [3] a filter request's survivors so far, by chunk parity (k_dc_select)
+                                  // [2], [3] a filter request's survivors so far, by chunk parity (k_dc_select),
+                                  // [4] a group filter request's smallest bad offset index (k_dc_group_check); 8 words
   unsigned long long* dc_plane = nullptr;  // ... the plane of a filter request that gives none (max_batch / 32 words)
   uint32_t* dc_ids = nullptr;     // ... the id block a cross device tile's join reads (kAqlIdsBytes; written by k_dc_cross_ids)
+  unsigned long long* dc_pairs = nullptr;  // ... a group filter chunk's pairs (max_batch x 8 B; written by k_dc_group_pairs)
   bool dc_cnt_dirty = false;      // ... dc_aux[0] may be non-zero
   uint32_t pair_dirty = 0;        // one of the two alternating deferred-list counters (aql_summaries) may be non-zero:
                                   // the next so many dispatched joins must clear the other one themselves
@@ -2106,11 +2116,12 @@ static Workspace* create_workspace(Engine& e) {
     w->d_err = dalloc<int32_t>(w->allocs, w->max_batch, &w->bytes);
     w->cav_flag = dalloc<uint8_t>(w->allocs, w->max_batch, &w->bytes);
     w->dc_bitmap = dalloc<uint32_t>(w->allocs, w->max_batch / 32 + 1, &w->bytes);
-    w->dc_aux = dalloc<uint32_t>(w->allocs, 4, &w->bytes);
+    w->dc_aux = dalloc<uint32_t>(w->allocs, 8, &w->bytes);
     w->dc_plane = dalloc<unsigned long long>(w->allocs, w->max_batch / 32 + 1, &w->bytes);
     w->dc_ids = dalloc<uint32_t>(w->allocs, kAqlIdsBytes / 4, &w->bytes);
+    w->dc_pairs = dalloc<unsigned long long>(w->allocs, w->max_batch, &w->bytes);
     HIP_OK(hipMemsetAsync(w->dc_bitmap, 0, (w->max_batch / 32 + 1) * sizeof(uint32_t), nullptr));
-    HIP_OK(hipMemsetAsync(w->dc_aux, 0, 4 * sizeof(uint32_t), nullptr));
+    HIP_OK(hipMemsetAsync(w->dc_aux, 0, 8 * sizeof(uint32_t), nullptr));
     w->d_ctx = reinterpret_cast<Ctx*>(dalloc<unsigned char>(w->allocs, sizeof(Ctx), &w->bytes));
     HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&w->h_ctx), sizeof(Ctx), hipHostMallocDefault));
     HIP_OK(hipHostMalloc(&w->h_ctr, sizeof(DevCounters) + (kBCtrs + 4) * sizeof(unsigned),
@@ -3884,6 +3895,15 @@ static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t 
       c.shape_of = c.indexed ? q.shape_of + pos : nullptr;
       c.packed = c.out;
     }
+    if (q.groups()) {
+      // a group filter chunk: its pairs into the workspace's pair buffer by one kernel, and the join
+      // behind it on the same stream — an engine-stream batch's too, through the HIP launch and not
+      // the engine's HSA queue, as a cross device tile's join follows its gather (above)
+      const bool own = q.engine_stream;
+      dc_group_pairs(w, q, pos, len, own ? w.stream : (hipStream_t)q.stream);
+      c.pairs = reinterpret_cast<const uint32_t*>(w.dc_pairs);
+      c.no_aql = own;
+    }
     if (q.list()) {
       // a list chunk: its ids, 4 B per check; a range's chunk has none, only its own first id
       if (!q.device) compact_stage(e, w, q.ids ? q.ids + pos : nullptr, 4u, nullptr, len, c);
@@ -3904,6 +3924,7 @@ static void submit_compact(Engine& e, Workspace& w, const CompactReq& q, size_t 
     c.packed = c.out;
     c.shape_of = c.indexed ? q.shape_of + pos : nullptr;  // (read for the message of a bad index only)
     const hipStream_t st = q.engine_stream ? w.stream : (hipStream_t)q.stream;
+    if (q.groups()) dc_group_pairs(w, q, pos, len, st);  // (k_dc_expand reads the chunk's pairs from dc_pairs)
     dc_expand(w, q, pos, len, st);
     submit_batch(e, w, w.d_items, len, now_us, w.d_perm, w.d_err, st,
                  q.engine_stream ? BatchMem::kEngineStream : BatchMem::kCallerStream, c);
@@ -4024,6 +4045,7 @@ void device_submit_compact(Engine& e, Workspace* w, const CompactReq& req, int64
   q.zero_cnt = q.device && q.d_n_errs;  // (cleared by the batch: its dispatched join, or the memset below)
   stage_caveats(*w, std::move(cav), st);
   if (now_us == 0) now_us = wall_now_us();
+  if (q.groups()) dc_group_check(*w, q, st);  // (on the batch's stream, before its chunk; the wait reads the word)
   submit_compact(e, *w, q, 0, (uint32_t)q.n, now_us, q.device ? dc_count_begin(*w, q, st, false) : nullptr);
   if (w->cb.zero_cnt) {  // (no dispatched join took the clear of the caller's count word)
     HIP_OK(hipMemsetAsync(w->cb.d_cnt, 0, 4, st));
@@ -4044,6 +4066,14 @@ void device_submit_compact(Engine& e, Workspace* w, const CompactReq& req, int64
     w->cb.csel_S = q.S;
     w->cb.out = reinterpret_cast<unsigned long long*>(q.packed);
   }
+  if (q.groups()) {  // (likewise: its collect selects the groups and reads the offsets' check word)
+    w->cb.select_groups = true;
+    w->cb.gsel = *q.sel_groups;
+    w->cb.gsel_off = q.group_off;
+    w->cb.gsel_ids = q.ids;
+    w->cb.gsel_S = q.S;
+    w->cb.out = reinterpret_cast<unsigned long long*>(q.packed);
+  }
 }
 
 // The chunks of a request that is no cross request: max_batch checks each, rounded down to a multiple
@@ -4061,6 +4091,7 @@ static size_t compact_chunks(Engine& e, Workspace* w0, Workspace* w1, const Comp
     // completes first, and so does the clear of the count the chunks' lists accumulate in
     HIP_OK(hipStreamSynchronize((hipStream_t)req.stream));
     d_cnt = dc_count_begin(*w0, req, w0->stream, true);
+    if (req.groups()) dc_group_check(*w0, req, w0->stream);  // (once, before the chunks; read behind the selection)
     HIP_OK(hipStreamSynchronize(w0->stream));
   }
   run_chunks(
@@ -4123,6 +4154,16 @@ void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const Compact
   }
   std::vector<gck_item_error> errs;
   compact_chunks(e, w0, w1, req, now_us, cav, errs);
+  if (req.groups()) {
+    // every chunk is collected — its stream completed — so the dense plane is finished: the group
+    // selection over the whole of it, the offsets' check word behind it, then the wait
+    dc_select_groups(*req.sel_groups, reinterpret_cast<const unsigned long long*>(req.packed), req.group_off, req.S, req.n,
+                     req.ids, w0->stream);
+    uint32_t bad = 0xFFFFFFFFu;
+    HIP_OK(hipMemcpyAsync(&bad, w0->dc_aux + 4, 4, hipMemcpyDeviceToHost, w0->stream));
+    HIP_OK(hipStreamSynchronize(w0->stream));
+    if (bad != 0xFFFFFFFFu) group_offsets_error(bad, req.S, req.n);
+  }
   if (!req.device) uniform_errors(errs, req.errs, req.err_cap, req.n_errs);
 }
 

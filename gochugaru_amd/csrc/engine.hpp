@@ -437,7 +437,7 @@ struct CompactReq {
   uint32_t vary = 0;
   uint32_t fixed_id = 0, first_id = 0;
   const uint32_t* ids = nullptr;
-  bool list() const { return vary != 0; }
+  bool list() const { return vary != 0 && !sel_groups; }
   // a request over device buffers (gck_check_bulk_uniform_device ..., gck_check_bulk_cross_device):
   // shape_of, pairs, ids, subjects, resources, packed and errs are device memory — no host path may
   // read them — n_errs is null and the count goes to *d_n_errs (device memory; may be null). The
@@ -460,11 +460,24 @@ struct CompactReq {
   // a cross filter request by resource (gck_filter_cross_cols_device): sel_rows' twin — each column's
   // kept survivors, as a CSR by resource (device_compact.inc dc_select_cols). At most one of the two
   const gck_select_cols* sel_cols = nullptr;
+  // a group filter request (gck_filter_groups_device; device buffers only, one header, null pairs):
+  // S owners, owner s with the candidates ids[group_off[s] .. group_off[s + 1]) of the flat list `ids`
+  // (n of them); check k is (shapes[0], ids[k], owners[s]) with `vary` GCK_VARY_RESOURCE, or the
+  // mirror. Each chunk is expanded to pairs in the workspace (k_dc_group_pairs) and runs as a uniform
+  // device chunk; `packed` is the dense plane, and once it is finished each group's kept survivors go
+  // to *sel_groups' arrays as a CSR (copied by the submit; device_compact.inc dc_select_groups)
+  const uint32_t* owners = nullptr;
+  const uint32_t* group_off = nullptr;
+  const gck_select_groups* sel_groups = nullptr;
+  bool groups() const { return sel_groups != nullptr; }
 };
 // The outputs of an empty cross filter request (S == 0 or R == 0), synchronous on `stream`.
 void device_select_rows_empty(Engine& e, const gck_select_rows& sel, size_t S, void* stream);
 // Likewise by resource: col_off[0] and the count alone for R == 0, else R + 1 zero offsets.
 void device_select_cols_empty(Engine& e, const gck_select_cols& sel, size_t R, void* stream);
+// ... of an empty group filter request (n == 0): row_off[0] and the count alone for S == 0, else
+// S + 1 zero offsets and S zero counts; no offset is read.
+void device_select_groups_empty(Engine& e, const gck_select_groups& sel, size_t S, void* stream);
 // *d_n_errs = 0 for an empty device request (synchronous on `stream`; a null pointer: nothing).
 void device_zero_count(Engine& e, uint32_t* d_n_errs, void* stream);
 // Synchronous: chunks of max_batch & ~31 checks over w0 and w1 (as device_check_host); a cross

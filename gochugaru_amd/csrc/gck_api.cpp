@@ -1811,6 +1811,114 @@ int gck_filter_submit_cross_cols_device(gck_engine* ge, const gck_consistency* c
   });
 }
 
+// ---- group filter requests (include/gck.h gck_filter_groups_device) ---------------------------
+
+// The request's argument rules, every one of them, shared with the host hook (gck_test_groups_rule):
+// empty when the request is good, else what is wrong with it. Reads no buffer but *hdr and *sel.
+static std::string groups_fault(const gck_uniform* hdr, uint32_t vary, const uint32_t* d_owners, size_t S,
+                                const uint32_t* d_group_off, const uint32_t* d_candidates, size_t n, size_t n_contexts,
+                                const gck_select_groups* sel, const uint64_t* d_out_packed, const gck_item_error* d_out_errs,
+                                size_t err_cap, const uint32_t* d_out_n_errs) {
+  const auto aligned = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+  const std::string g = "group filter request: ";
+  if (!hdr) return "null header";
+  if (hdr->context_slot > n_contexts)
+    return "uniform header: context_slot " + std::to_string(hdr->context_slot) + " beyond the " + std::to_string(n_contexts) +
+           " contexts given";
+  if (hdr->reserved != 0) return g + "the header's reserved must be 0";
+  if (vary != GCK_VARY_RESOURCE && vary != GCK_VARY_SUBJECT) return g + "vary must be GCK_VARY_RESOURCE or GCK_VARY_SUBJECT";
+  if (!sel) return g + "null gck_select_groups";
+  if (sel->mask == 0 || (sel->mask & ~0xEu))
+    return g + "mask must select among GCK_SELECT_NO, GCK_SELECT_HAS and GCK_SELECT_CONDITIONAL";
+  if (!sel->d_out_row_off) return g + "null d_out_row_off";
+  if (!sel->d_out_n) return g + "null d_out_n";
+  if (!d_out_packed) return g + "null d_out_packed";
+  if (sel->cap != 0 && !sel->d_out_ids && !sel->d_out_pos && !sel->d_out_perm) return g + "cap > 0 without an output array";
+  if (n >= 0x100000000ull) return g + std::to_string(n) + " checks reach 2^32";
+  if (S >= 0x100000000ull) return g + std::to_string(S) + " groups reach 2^32";
+  if (n > 0 && S == 0) return g + std::to_string(n) + " candidates without a group";
+  if (n > 0 && (!d_owners || !d_group_off || !d_candidates)) return g + "null d_owners, d_group_off or d_candidates";
+  if (err_cap != 0 && !d_out_errs) return "null error list";
+  if (!aligned(d_out_packed, 8)) return g + "d_out_packed is not 8-byte aligned";
+  if (!aligned(d_owners, 4) || !aligned(d_group_off, 4) || !aligned(d_candidates, 4))
+    return g + "d_owners, d_group_off or d_candidates is not 4-byte aligned";
+  if (!aligned(d_out_errs, 4) || !aligned(d_out_n_errs, 4)) return g + "d_out_errs or d_out_n_errs is not 4-byte aligned";
+  if (!aligned(sel->d_out_row_off, 4) || !aligned(sel->d_out_row_n, 4) || !aligned(sel->d_out_ids, 4) ||
+      !aligned(sel->d_out_pos, 4) || !aligned(sel->d_out_n, 4))
+    return g + "d_out_row_off, d_out_row_n, d_out_ids, d_out_pos or d_out_n is not 4-byte aligned";
+  return std::string();
+}
+
+// The rules against the call, before anything is launched or written; then the request as the engine
+// takes it (`sel` is the caller's: the engine copies it before the call returns).
+static CompactReq groups_request(const gck_uniform* hdr, uint32_t vary, const uint32_t* d_owners, size_t S,
+                                 const uint32_t* d_group_off, const uint32_t* d_candidates, size_t n, size_t n_contexts,
+                                 const gck_select_groups* sel, uint64_t* d_out_packed, gck_item_error* d_out_errs,
+                                 size_t err_cap, uint32_t* d_out_n_errs, void* stream, bool engine_stream) {
+  const std::string fault = groups_fault(hdr, vary, d_owners, S, d_group_off, d_candidates, n, n_contexts, sel, d_out_packed,
+                                         d_out_errs, err_cap, d_out_n_errs);
+  REQUIRE(fault.empty(), GCK_E_INVALID_ARGUMENT, fault);
+  CompactReq q{hdr, 1u, nullptr, nullptr, n, d_out_packed, d_out_errs, err_cap, nullptr};
+  q.vary = vary;
+  q.ids = d_candidates;
+  q.owners = d_owners;
+  q.group_off = d_group_off;
+  q.S = S;
+  q.sel_groups = sel;
+  q.device = true;
+  q.engine_stream = engine_stream;
+  q.stream = stream;
+  q.d_n_errs = d_out_n_errs;
+  return q;
+}
+
+int gck_filter_groups_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr, uint32_t vary,
+                             const uint32_t* d_owners, size_t n_owners, const uint32_t* d_group_off,
+                             const uint32_t* d_candidates, size_t n_candidates, const char* const* contexts,
+                             const size_t* context_lens, size_t n_contexts, int64_t now_us,
+                             const gck_select_groups* sel, uint64_t* d_out_packed, gck_item_error* d_out_errs,
+                             size_t err_cap, uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision) {
+  return guard([&] {
+    Engine& e = need(ge);
+    const CompactReq req = groups_request(hdr, vary, d_owners, n_owners, d_group_off, d_candidates, n_candidates, n_contexts,
+                                          sel, d_out_packed, d_out_errs, err_cap, d_out_n_errs, stream, true);
+    const CallCtx c{cs, contexts, context_lens, n_contexts};
+    check_device_sync(e, c, req, now_us, out_revision);
+    // (no check ran: the count word above, then the offsets and counts of S empty groups)
+    if (req.n == 0) device_select_groups_empty(e, *sel, n_owners, stream);
+  });
+}
+
+int gck_filter_submit_groups_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr, uint32_t vary,
+                                    const uint32_t* d_owners, size_t n_owners, const uint32_t* d_group_off,
+                                    const uint32_t* d_candidates, size_t n_candidates, const char* const* contexts,
+                                    const size_t* context_lens, size_t n_contexts, int64_t now_us,
+                                    const gck_select_groups* sel, uint64_t* d_out_packed, gck_item_error* d_out_errs,
+                                    size_t err_cap, uint32_t* d_out_n_errs, uint32_t flags, void* stream,
+                                    gck_batch** out) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    check_submit_flags(flags);
+    const bool own = (flags & GCK_SUBMIT_ENGINE_STREAM) != 0;
+    const CompactReq req = groups_request(hdr, vary, d_owners, n_owners, d_group_off, d_candidates, n_candidates, n_contexts,
+                                          sel, d_out_packed, d_out_errs, err_cap, d_out_n_errs, stream, own);
+    REQUIRE(req.n <= max_batch_of(e), GCK_E_INVALID_ARGUMENT,
+            "submitted group filter request of " + std::to_string(req.n) + " checks is above max_batch");
+    gck_batch* b = submit_device(e, {cs, contexts, context_lens, n_contexts}, req, now_us);
+    if (req.n == 0) {
+      try {
+        device_select_groups_empty(e, *sel, n_owners, own ? nullptr : stream);
+      } catch (...) {
+        delete b;
+        throw;
+      }
+    }
+    *out = b;
+  });
+}
+
 int gck_device_compact_stats(gck_engine* ge, uint64_t out[2]) {
   return guard([&] {
     Engine& e = need(ge);
@@ -2320,6 +2428,79 @@ int gck_test_select_cols(const uint64_t* words, uint32_t S, uint32_t R, uint32_t
         }
       for (uint32_t chunk = 0; chunk < gck::kColChunks; ++chunk)
         for (uint32_t lane = 0; lane < gck::kColGroup; ++lane) carry[lane] += part[chunk][lane];
+    }
+  }
+  return 0;
+}
+
+// gck_test_group_of: the group lookup of k_dc_group_pairs (select_plane.hpp select_group_of) for n_k
+// positions, on the host; whatever `off` holds, every result is within [0, S - 1]. -1 for S == 0 or
+// null arguments.
+int gck_test_group_of(const uint32_t* off, uint32_t S, const uint32_t* k, uint32_t n_k, uint32_t* out) {
+  if (!off || S == 0 || (n_k && (!k || !out))) return -1;
+  for (uint32_t i = 0; i < n_k; ++i) out[i] = gck::select_group_of(off, S, k[i]);
+  return 0;
+}
+
+// gck_test_groups_rule: the group filter entry points' rule function (groups_fault) over the same
+// arguments, reading no buffer: 0 when they are good, -1 when the entry points refuse them.
+int gck_test_groups_rule(const gck_uniform* hdr, uint32_t vary, const uint32_t* d_owners, size_t S,
+                         const uint32_t* d_group_off, const uint32_t* d_candidates, size_t n, size_t n_contexts,
+                         const gck_select_groups* sel, const uint64_t* d_out_packed, const gck_item_error* d_out_errs,
+                         size_t err_cap, const uint32_t* d_out_n_errs) {
+  return groups_fault(hdr, vary, d_owners, S, d_group_off, d_candidates, n, n_contexts, sel, d_out_packed, d_out_errs,
+                      err_cap, d_out_n_errs).empty() ? 0 : -1;
+}
+
+// gck_test_select_groups: the group-segmented selection of a group filter request (select_plane.hpp;
+// k_dc_groups_count, k_dc_rows_scan and k_dc_groups_write in device_compact.inc) over a dense plane of
+// ceil(n / 32) words on the host, with the same functions, group by group and piece by piece of L
+// words as the kernels walk them (lanes == 0: the kernels' own choice, select_group_lanes; else a power
+// of two within 1 .. 64): the clamped ranges, the counts, their prefix, then each word's survivors from
+// the in-group rank the words before it give. Outputs and NULL rules are gck_select_groups' (src_ids:
+// the candidate list, needed with out_ids). -1 for the selection's argument errors. What this pins is
+// the per-word functions, the clamps and the protocol; the kernels' lane scans inside a wave are
+// covered only by the GPU tests.
+int gck_test_select_groups(const uint64_t* words, uint32_t n, const uint32_t* off, uint32_t S, uint32_t mask,
+                           uint32_t group_limit, size_t cap, uint32_t lanes, const uint32_t* src_ids, uint32_t* out_row_off,
+                           uint32_t* out_row_n, uint32_t* out_ids, uint32_t* out_pos, uint8_t* out_perm, uint32_t* out_n) {
+  gck_select_groups sel{mask, group_limit, out_row_off, out_row_n, out_ids, out_pos, out_perm, cap, out_n};
+  const gck_uniform hdr{};
+  static const uint64_t plane0 = 0;  // (the rule wants a plane pointer; the hook's own is checked below)
+  if (!groups_fault(&hdr, GCK_VARY_RESOURCE, off, S, off, off, 0, 0, &sel, &plane0, nullptr, 0, nullptr).empty()) return -1;
+  if (n && (!words || !off || S == 0 || (out_ids && !src_ids))) return -1;
+  if (lanes && (lanes > 64u || (lanes & (lanes - 1u)))) return -1;
+  const uint32_t L = lanes ? lanes : gck::select_group_lanes(n, S);
+  const gck::SelectRowsOut o{out_ids, out_pos, out_perm, (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu), src_ids};
+  const auto range = [&](uint32_t s, uint32_t& lo, uint32_t& hi, uint32_t& w0, uint32_t& nw) {
+    gck::select_group_range(off, s, n, lo, hi);
+    w0 = lo >> 5;
+    nw = hi > lo ? ((hi - 1u) >> 5) - w0 + 1u : 0u;
+  };
+  for (uint32_t s = 0; s < S; ++s) {  // k_dc_groups_count
+    uint32_t lo, hi, w0, nw, sum = 0;
+    range(s, lo, hi, w0, nw);
+    for (uint32_t p0 = 0; p0 < nw; p0 += L)
+      for (uint32_t t = p0; t < nw && t < p0 + L; ++t)
+        sum += gck::select_count(gck::select_group_mask(words[w0 + t], mask, w0 + t, lo, hi));
+    out_row_off[s + 1u] = gck::select_row_kept(sum, group_limit);
+    if (out_row_n) out_row_n[s] = sum;
+  }
+  uint32_t run = 0;  // k_dc_rows_scan
+  for (uint32_t s = 0; s < S; ++s) out_row_off[s + 1u] = run += out_row_off[s + 1u];
+  out_row_off[0] = 0u;
+  *out_n = run;
+  for (uint32_t s = 0; s < S && n && o.cap; ++s) {  // k_dc_groups_write
+    uint32_t lo, hi, w0, nw, carry = 0;
+    range(s, lo, hi, w0, nw);
+    for (uint32_t p0 = 0; p0 < nw && !(group_limit && carry >= group_limit); p0 += L) {
+      uint32_t rank = carry;
+      for (uint32_t t = p0; t < nw && t < p0 + L; ++t) {
+        const uint64_t word = words[w0 + t], m = gck::select_group_mask(word, mask, w0 + t, lo, hi);
+        gck::select_write_row(word, m, (w0 + t) * 32u, rank, out_row_off[s], group_limit, o);
+        rank += gck::select_count(m);
+      }
+      carry = rank;
     }
   }
   return 0;

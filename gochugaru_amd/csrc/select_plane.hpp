@@ -5,7 +5,10 @@
 // exports it for the tests as gck_test_select_plane). Below them, the row-segmented form over a cross
 // request's row-padded plane (gck_filter_cross_device; k_dc_rows_count / k_dc_rows_write, and
 // gck_test_select_rows on the host), and its mirror, the column-segmented form
-// (gck_filter_cross_cols_device; k_dc_cols_count / k_dc_cols_write, gck_test_select_cols).
+// (gck_filter_cross_cols_device; k_dc_cols_count / k_dc_cols_write, gck_test_select_cols). Last, the
+// group-segmented form over a dense plane cut by caller-given offsets, and the group lookup of its
+// pair expansion (gck_filter_groups_device; k_dc_group_pairs, k_dc_groups_count / k_dc_groups_write,
+// gck_test_group_of and gck_test_select_groups).
 //
 // A word holds 32 checks, check b in bits 2b .. 2b + 1 (GCK_PERM_*: 0 unspecified — an errored check
 // and a tail lane alike —, 1 NO, 2 HAS, 3 CONDITIONAL). `mask` has bit v set when value v survives
@@ -205,5 +208,64 @@ GCK_SEL_HD inline uint32_t select_col_walk(const uint64_t* words, size_t step, u
   }
   return met;
 }
+
+// ---- the group-segmented selection over a dense plane (include/gck.h gck_filter_groups_device) ----
+// The plane is the uniform request's: check k in bits 2 (k % 32) of word k / 32, ceil(n / 32) words.
+// Group s owns the checks [off[s], off[s + 1]) — the words lo / 32 .. (hi - 1) / 32, the first and
+// the last masked to the group's bits; two groups may share a word, and each reads it — and keeps its
+// first kept_s survivors at ranks row_off[s] + j of the request. The offsets are the caller's device
+// memory, which nobody has validated when the kernels read them: every function below stays inside
+// [0, S - 1] and [0, n] whatever they hold. The kernels (k_dc_groups_count, k_dc_groups_write) and the
+// host hook (gck_test_select_groups) give a group L lanes of a wave and walk it in pieces of L words.
+
+// The group of check k: the last s in [0, S - 1] with off[s] <= k — for good offsets and k < n,
+// off[s] <= k < off[s + 1], the group an upper-bound search of k in off[0 .. S] ends before. S >= 1.
+// Reads off[1 .. S - 1] only; on offsets in no order the search still ends, somewhere in [0, S - 1].
+GCK_SEL_HD inline uint32_t select_group_of(const uint32_t* off, uint32_t S, uint32_t k) {
+  uint32_t lo = 0, hi = S - 1u;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo + 1u) / 2u;  // (lo < mid <= hi)
+    if (off[mid] <= k) lo = mid;
+    else hi = mid - 1u;
+  }
+  return lo;
+}
+
+// Group s's checks [lo, hi), clamped into the request: lo = min(off[s], n), hi = min(max(off[s + 1],
+// lo), n). n == 0 reads no offset.
+GCK_SEL_HD inline void select_group_range(const uint32_t* off, uint32_t s, uint32_t n, uint32_t& lo, uint32_t& hi) {
+  lo = hi = 0;
+  if (n == 0) return;
+  const uint32_t a = off[s], b = off[s + 1u];
+  lo = a < n ? a : n;
+  hi = b > lo ? b : lo;
+  if (hi > n) hi = n;
+}
+
+// The lanes of a wave one group takes in a request of n checks in S groups: the smallest power of two
+// >= ceil(n / S / 32) + 1 (an average group's words, and one more for a group that begins inside a
+// word), within 1 .. 64. A longer group takes pieces of L words, with a carried rank.
+GCK_SEL_HD inline uint32_t select_group_lanes(uint32_t n, uint32_t S) {
+  const uint32_t per = S ? (uint32_t)(((uint64_t)n + S - 1u) / S) : 0u;
+  const uint32_t want = (per + 31u) / 32u + 1u;
+  uint32_t l = 1;
+  while (l < want && l < 64u) l <<= 1;
+  return l;
+}
+
+// The survivor mask of plane word t for the group [lo, hi): select_mask, with the checks below lo and
+// at or above hi cleared. A word outside the group's words gives 0.
+GCK_SEL_HD inline uint64_t select_group_mask(uint64_t word, uint32_t mask, uint32_t t, uint32_t lo, uint32_t hi) {
+  const uint64_t k0 = (uint64_t)t * 32u;
+  if (hi <= k0 || lo >= k0 + 32u || lo >= hi) return 0;
+  uint64_t m = select_mask(word, mask);
+  if (lo > k0) m &= ~((1ull << (2u * (uint32_t)(lo - k0))) - 1ull);
+  if (hi < k0 + 32u) m &= (1ull << (2u * (uint32_t)(hi - k0))) - 1ull;
+  return m;
+}
+
+// A group's kept survivors are written by select_write_row: SelectRowsOut with the candidate list as
+// src_ids and the positions as `col`, col0 = 32 t — a survivor's column is its position k in the
+// request, its id candidates[k].
 
 }  // namespace gck

@@ -179,6 +179,14 @@ class SelectCols(C.Structure):
                 ("d_out_perm", C.c_void_p), ("cap", C.c_size_t), ("d_out_n", C.c_void_p)]
 
 
+class SelectGroups(C.Structure):
+    """gck_select_groups (include/gck.h): which Permissionships survive a group filter request, how
+    many each group keeps, and the device arrays of the CSR they go to."""
+    _fields_ = [("mask", C.c_uint32), ("group_limit", C.c_uint32), ("d_out_row_off", C.c_void_p),
+                ("d_out_row_n", C.c_void_p), ("d_out_ids", C.c_void_p), ("d_out_pos", C.c_void_p),
+                ("d_out_perm", C.c_void_p), ("cap", C.c_size_t), ("d_out_n", C.c_void_p)]
+
+
 SELECT_NO = 1 << PERM_NO                       # GCK_SELECT_NO
 SELECT_HAS = 1 << PERM_HAS                     # GCK_SELECT_HAS
 SELECT_CONDITIONAL = 1 << PERM_CONDITIONAL     # GCK_SELECT_CONDITIONAL
@@ -415,6 +423,15 @@ _SIGS = {
                                                       _P, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
                                                       C.c_size_t, C.c_int64, C.POINTER(SelectCols), _P, _P, C.c_size_t,
                                                       _P, C.c_uint32, _P, C.POINTER(_P)]),
+    "gck_filter_groups_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), C.c_uint32, _P, C.c_size_t,
+                                           _P, _P, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                           C.c_size_t, C.c_int64, C.POINTER(SelectGroups), _P, _P, C.c_size_t, _P, _P,
+                                           C.POINTER(C.c_uint64)]),
+    "gck_filter_submit_groups_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), C.c_uint32, _P,
+                                                  C.c_size_t, _P, _P, C.c_size_t, C.POINTER(C.c_char_p),
+                                                  C.POINTER(C.c_size_t), C.c_size_t, C.c_int64,
+                                                  C.POINTER(SelectGroups), _P, _P, C.c_size_t, _P, C.c_uint32, _P,
+                                                  C.POINTER(_P)]),
     "gck_lookup_resources_among": (C.c_int, [_P, C.POINTER(_Consistency), C.c_uint16, C.c_uint16, C.c_uint16,
                                              C.c_uint16, C.c_uint32, _P, C.c_size_t, C.c_int64, _P, _P, C.c_size_t,
                                              C.POINTER(C.c_size_t)]),
@@ -1623,6 +1640,112 @@ class Engine:
         out = (col_off, out_ids[:total])
         if want_row:
             out += (out_row[:total],)
+        if want_perm:
+            out += (out_perm[:total],)
+        return out
+
+    # ---- group filter requests (gck_filter_groups_device): a candidate list per owner, each owner's
+    # survivors as a CSR. d_owners: S u32; d_group_off: S + 1 u32; d_candidates: n u32. d_out_row_off:
+    # S + 1 u32 (required); d_out_n: one u32 (required); d_out_row_n: S u32, 0: not wanted; d_out_ids /
+    # d_out_pos (u32) and d_out_perm (u8): `cap` entries each, 0: not wanted; d_out_packed (ceil(n / 32)
+    # u64) is required.
+    def filter_groups_device(self, header, d_owners: int, n_owners: int, d_group_off: int, d_candidates: int,
+                             n_candidates: int, d_out_row_off: int, d_out_n: int, cap: int, d_out_packed: int,
+                             d_out_ids: int = 0, d_out_pos: int = 0, d_out_perm: int = 0, d_out_row_n: int = 0,
+                             vary: int = VARY_RESOURCE, select: int = SELECT_LOOKUP, group_limit: int = 0,
+                             d_out_errs: int = 0, err_cap: int = 0, d_out_n_errs: int = 0,
+                             stream: Optional[int] = None, requirement: int = CONSISTENCY_MIN_LATENCY,
+                             revision: int = 0, now_us: int = 0, contexts: Optional[Sequence] = None) -> int:
+        """gck_filter_groups_device: check k is candidate k against the owner of the group it lies in
+        (VARY_RESOURCE: owners are subject ids, candidates resource ids; VARY_SUBJECT: the mirror); then
+        for each group the candidates whose Permissionship `select` (SELECT_*) names, in the group's
+        order and at most `group_limit` of them (0: all): group offsets, ids, positions and
+        Permissionships into the device arrays, their number into *d_out_n. A per-item error does not
+        fail the call; malformed offsets do (GckError, InvalidArgument). Returns the evaluated revision."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        sel = SelectGroups(select, group_limit, d_out_row_off or None, d_out_row_n or None, d_out_ids or None,
+                           d_out_pos or None, d_out_perm or None, cap, d_out_n or None)
+        rev = C.c_uint64(0)
+        _check(self._lib.gck_filter_groups_device(self._h, C.byref(cs), C.byref(hdr), vary, d_owners or None, n_owners,
+                                                  d_group_off or None, d_candidates or None, n_candidates, *tail[:4],
+                                                  C.byref(sel), *tail[4:], stream, C.byref(rev)))
+        return rev.value
+
+    def submit_filter_groups_device(self, header, d_owners: int, n_owners: int, d_group_off: int, d_candidates: int,
+                                    n_candidates: int, d_out_row_off: int, d_out_n: int, cap: int, d_out_packed: int,
+                                    d_out_ids: int = 0, d_out_pos: int = 0, d_out_perm: int = 0, d_out_row_n: int = 0,
+                                    vary: int = VARY_RESOURCE, select: int = SELECT_LOOKUP, group_limit: int = 0,
+                                    d_out_errs: int = 0, err_cap: int = 0, d_out_n_errs: int = 0,
+                                    stream: Optional[int] = None, engine_stream: bool = False,
+                                    requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                                    contexts: Optional[Sequence] = None) -> "DeviceCompactBatch":
+        """gck_filter_submit_groups_device (n_candidates <= max_batch): as submit_uniform_device, with
+        filter_groups_device's outputs; malformed offsets fail the wait."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        sel = SelectGroups(select, group_limit, d_out_row_off or None, d_out_row_n or None, d_out_ids or None,
+                           d_out_pos or None, d_out_perm or None, cap, d_out_n or None)
+        b = DeviceCompactBatch(self, hdr)
+        _check(self._lib.gck_filter_submit_groups_device(self._h, C.byref(cs), C.byref(hdr), vary, d_owners or None,
+                                                         n_owners, d_group_off or None, d_candidates or None,
+                                                         n_candidates, *tail[:4], C.byref(sel), *tail[4:],
+                                                         SUBMIT_ENGINE_STREAM if engine_stream else 0, stream,
+                                                         C.byref(b._h)))
+        return b
+
+    def filter_groups_ids(self, header, owners, offsets, candidates, vary: int = VARY_RESOURCE,
+                          select: int = SELECT_LOOKUP, group_limit: int = 0, want_pos: bool = False,
+                          want_perm: bool = False, requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0,
+                          now_us: int = 0, contexts: Optional[Sequence] = None):
+        """For each of `owners` those of its own candidates that it may see (VARY_SUBJECT: that may see
+        it) — device int32 / uint32 tensors: S owners, S + 1 offsets into the flat `candidates` — as a CSR
+        of torch tensors: (row_off, ids), row_off an int32 [S + 1] tensor and ids (in the candidates'
+        dtype) the kept survivors of owner s at row_off[s] .. row_off[s + 1], in its candidates' order;
+        then their positions in `candidates` (int32) and Permissionships (uint8) when asked for.
+        `group_limit`: at most so many per owner (0: all). Runs filter_groups_device on the current stream
+        with outputs allocated on the tensors' device (cap = n, or S * group_limit when that is smaller)
+        and reads the two count words — the call's only copy to the host. A per-item error raises
+        GckError with the lookups' message."""
+        import torch
+        for name, t in (("owners", owners), ("offsets", offsets), ("candidates", candidates)):
+            if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.uint32) or not t.is_cuda:
+                raise GckError(GCK_E_INVALID_ARGUMENT, f"filter_groups_ids: {name} must be a device int32 / uint32 tensor")
+        if owners.device != candidates.device or offsets.device != candidates.device:
+            raise GckError(GCK_E_INVALID_ARGUMENT, "filter_groups_ids: the tensors are on different devices")
+        owners, offsets, candidates = (t.contiguous().reshape(-1) for t in (owners, offsets, candidates))
+        S, n, dev = owners.numel(), candidates.numel(), candidates.device
+        if offsets.numel() != S + 1:
+            raise GckError(GCK_E_INVALID_ARGUMENT, f"filter_groups_ids: {offsets.numel()} offsets for {S} owners")
+        cap = min(n, S * group_limit) if group_limit else n
+        with torch.cuda.device(dev):
+            plane = torch.empty(max(1, (n + 31) // 32), dtype=torch.int64, device=dev)  # (required, also when empty)
+            row_off = torch.empty(S + 1, dtype=torch.int32, device=dev)
+            counts = torch.empty(2, dtype=torch.int32, device=dev)  # [kept survivors, errors]
+            out_ids = torch.empty(cap, dtype=candidates.dtype, device=dev)
+            out_pos = torch.empty(cap, dtype=torch.int32, device=dev) if want_pos else None
+            out_perm = torch.empty(cap, dtype=torch.uint8, device=dev) if want_perm else None
+            err = torch.empty(2, dtype=torch.int32, device=dev)  # the first error record
+            self.filter_groups_device(header, owners.data_ptr() if n else 0, S, offsets.data_ptr() if n else 0,
+                                      candidates.data_ptr() if n else 0, n, row_off.data_ptr(), counts.data_ptr(), cap,
+                                      plane.data_ptr(), d_out_ids=out_ids.data_ptr() if cap else 0,
+                                      d_out_pos=out_pos.data_ptr() if want_pos and cap else 0,
+                                      d_out_perm=out_perm.data_ptr() if want_perm and cap else 0, vary=vary,
+                                      select=select, group_limit=group_limit, d_out_errs=err.data_ptr(), err_cap=1,
+                                      d_out_n_errs=counts.data_ptr() + 4,
+                                      stream=torch.cuda.current_stream(dev).cuda_stream, requirement=requirement,
+                                      revision=revision, now_us=now_us, contexts=contexts)
+            total, n_errs = (int(x) & 0xFFFFFFFF for x in counts.tolist())
+            if n_errs:
+                code = int(err[1].item())
+                raise GckError(GCK_E_INVALID_ARGUMENT,
+                               ITEM_ERROR_MESSAGES[ITEM_ERR_MAX_DEPTH] if code == ITEM_ERR_MAX_DEPTH
+                               else f"lookup failed: per-item error {code}")
+        out = (row_off, out_ids[:total])
+        if want_pos:
+            out += (out_pos[:total],)
         if want_perm:
             out += (out_perm[:total],)
         return out

@@ -835,6 +835,72 @@ int gck_filter_submit_cross_cols_device(gck_engine* e, const gck_consistency* cs
                                         uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
                                         uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out);
 
+/* ---- group filter requests (ABI 13, additive) -------------------------------------------------
+ * A candidate list per owner: S owners (d_owners) and a CSR of candidates — d_group_off, S + 1
+ * offsets, and d_candidates, n ids — all in device memory: what a retrieval or ranking step returns,
+ * its own top-K for each query or user. Check k (k < n) belongs to group s where off[s] <= k <
+ * off[s + 1], and is (hdr, d_candidates[k], d_owners[s]) with vary == GCK_VARY_RESOURCE — owners are
+ * subject ids, candidates resource ids — or (hdr, d_owners[s], d_candidates[k]) with GCK_VARY_SUBJECT:
+ * for each of these documents, which of its own candidate users. 4 B per check and 4 B per group in.
+ * d_out_packed (required) is the dense plane of ceil(n / 32) words, written exactly as
+ * gck_check_bulk_uniform_device writes it for the same pairs (every word written, padding bits and
+ * errored checks 0); the error records are (index = k, GCK_ITEM_*) ascending, under the device compact
+ * calls' err_cap / *d_out_n_errs protocol. A per-item error does not fail the call: the check never
+ * survives.
+ * The selection, over the finished plane — gck_filter_cross_device's with "row s" read as "group s":
+ *   surv_s = the checks of group s whose Permissionship `mask` selects, ascending in k;
+ *   kept_s = group_limit ? min(surv_s, group_limit) : surv_s      (the first kept_s of them)
+ *   d_out_row_off[0] = 0, d_out_row_off[s + 1] = d_out_row_off[s] + kept_s: all S + 1 entries written;
+ *     an empty group has equal consecutive offsets.
+ *   record j of group s has rank d_out_row_off[s] + j, j ascending with k; each given record array is
+ *     written at a rank while rank < cap. Entries at and beyond min(total, cap) stay untouched.
+ *   d_out_row_n[s] = surv_s (before group_limit) when the array is given; *d_out_n = row_off[S], always
+ *     written.
+ * The offsets are device memory, so no host code validates them: a kernel checks the rule off[0] == 0,
+ * off[s] <= off[s + 1], off[S] == n, and a violation is GCK_E_INVALID_ARGUMENT from the synchronous
+ * call or from the wait, the message naming the smallest offending s. The outputs are then unspecified,
+ * but nothing outside them was written and nothing outside the inputs read: every kernel of the request
+ * clamps what it takes from the offsets (a group index into [0, S - 1], a group's range into [0, n], a
+ * record's rank below cap). S == 0 requires n == 0 and writes only row_off[0] = 0, *d_out_n = 0 and the
+ * error count word; n == 0 with S > 0 reads no offset and writes S + 1 zero offsets (and S zero counts).
+ * Stream ordering, flags / GCK_SUBMIT_ENGINE_STREAM, consistency and the evaluated revision are the
+ * list device call's; d_owners, d_group_off and d_candidates stay valid and unchanged until the
+ * synchronous call or the wait returns; `sel` is copied by the call. The synchronous form chunks n by
+ * max_batch & ~31 as the uniform device form does; the submit form takes n <= max_batch. Each chunk is
+ * expanded to 8-B pairs in the workspace by a kernel and runs as a uniform device chunk, counted in
+ * gck_device_compact_stats as one (in place or expanded); an empty request is not counted.
+ * GCK_E_INVALID_ARGUMENT, nothing launched and nothing written, for sel == NULL, a bad mask
+ * (gck_select's rule), a header whose `reserved` is not 0, a vary that is neither GCK_VARY_*,
+ * d_out_row_off, d_out_n or d_out_packed NULL, cap > 0 with all three record arrays NULL, n or S at or
+ * above 2^32, n > 0 with S == 0, a null input with n > 0, a d_out_packed that is not 8-byte aligned, any
+ * other device pointer that is not 4-byte aligned, and a context slot beyond n_contexts.
+ * Out of scope: the joins reading the CSR without the pair expansion; shaped (multi-header) groups; a
+ * form without a plane; the kernels of a one-chunk request fused. */
+typedef struct gck_select_groups {
+  uint32_t mask;           /* GCK_SELECT_*: gck_select's rule (bit 0 clear, != 0, <= 0xE) */
+  uint32_t group_limit;    /* 0: keep every survivor; else at most this many per group, the first in the group's order */
+  uint32_t* d_out_row_off; /* device, S + 1 entries, required */
+  uint32_t* d_out_row_n;   /* device, S entries, may be NULL: survivors of group s BEFORE group_limit */
+  uint32_t* d_out_ids;     /* device, cap entries, may be NULL: d_candidates[k] of a kept survivor */
+  uint32_t* d_out_pos;     /* device, cap entries, may be NULL: its position k in d_candidates (global, not in-group) */
+  uint8_t*  d_out_perm;    /* device, cap entries, may be NULL: its GCK_PERM_* */
+  size_t    cap;
+  uint32_t* d_out_n;       /* device, required: kept survivors of the whole request (== row_off[S]) */
+} gck_select_groups;       /* 64 bytes */
+int gck_filter_groups_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr, uint32_t vary,
+                             const uint32_t* d_owners, size_t n_owners, const uint32_t* d_group_off,
+                             const uint32_t* d_candidates, size_t n_candidates, const char* const* contexts,
+                             const size_t* context_lens, size_t n_contexts, int64_t now_us,
+                             const gck_select_groups* sel, uint64_t* d_out_packed, gck_item_error* d_out_errs,
+                             size_t err_cap, uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision);
+int gck_filter_submit_groups_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr, uint32_t vary,
+                                    const uint32_t* d_owners, size_t n_owners, const uint32_t* d_group_off,
+                                    const uint32_t* d_candidates, size_t n_candidates, const char* const* contexts,
+                                    const size_t* context_lens, size_t n_contexts, int64_t now_us,
+                                    const gck_select_groups* sel, uint64_t* d_out_packed, gck_item_error* d_out_errs,
+                                    size_t err_cap, uint32_t* d_out_n_errs, uint32_t flags, void* stream,
+                                    gck_batch** out);
+
 /* ---- lookups (Client.LookupResources / LookupSubjects, client/client.go:508-599) -------- */
 /* Ids of the `resource_type` objects on which the subject has `permission` — HAS or CONDITIONAL,
  * out_perm[k] says which — ascending. Every object of the type is checked on the device (the
