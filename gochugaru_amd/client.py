@@ -25,7 +25,7 @@ from typing import Iterable, Iterator, List, Optional, Tuple
 from . import consistency as _cs
 from . import rel as _rel
 from .consistency import Background, Context, Strategy
-from .engine import (CONSISTENCY_AT_LEAST, CONSISTENCY_FULL, CONSISTENCY_MIN_LATENCY,
+from .engine import (CHANGE_ANY, CHANGE_GAINED, CHANGE_LOST, CONSISTENCY_AT_LEAST, CONSISTENCY_FULL, CONSISTENCY_MIN_LATENCY,
                      CONSISTENCY_SNAPSHOT, ELLIPSIS, GCK_E_DEVICE, GCK_E_NOT_FOUND, GCK_E_REVISION,
                      ID_ABSENT, ID_WILDCARD, ITEM_ERROR_MESSAGES, PERM_HAS, REL_INVALID, TYPE_INVALID,
                      VARY_RESOURCE, VARY_SUBJECT, Engine, GckError, shape_request, unpack_cross, unpack_results)
@@ -535,6 +535,119 @@ class Client:
                     raise GckError(GCK_E_NOT_FOUND, "object definition or relation not found")
                 return eng.filter_cross_ids((rt, perm, st, srel), subjects, resources, row_limit=limit,
                                             requirement=requirement, revision=revision)
+            return retryRetriableErrors(ctx or Background, run), None
+        except Exception as e:  # noqa: BLE001 — Go returns (nil, err)
+            return None, e
+
+    # ---- recheck requests (Engine.recheck_ids / recheck_cross_ids): what changed since the plane kept ----
+    def _recheck_list(self, ctx, cs, what, fixed, names, vary, types, prev, transitions):
+        """RecheckResourcesDevice / RecheckSubjectsDevice after their own parsing. types() resolves
+        (header, fixed type, varying type) per attempt. Returns ((plane, revision, changes), err)."""
+        try:
+            import numpy as np
+            import torch
+            names = list(names)
+            requirement, revision = _requirement(cs)
+            eng = self.engine
+
+            def run():
+                hdr, fixed_type, vary_type = types()
+                fid = int(eng.intern(fixed_type, [fixed])[0])
+                ids = torch.from_numpy(np.ascontiguousarray(eng.intern(vary_type, names), dtype=np.uint32).view(np.int32))
+                ids = ids.to(torch.device("cuda", eng.device))
+                plane, rev, _, pos, trans = eng.recheck_ids(hdr, fid, vary, ids, prev=prev, transitions=transitions,
+                                                            requirement=requirement, revision=revision)
+                return plane, rev, [(names[p], t >> 2, t & 3) for p, t in zip(pos.tolist(), trans.tolist())]
+            return retryRetriableErrors(ctx or Background, run), None
+        except Exception as e:  # noqa: BLE001 — Go returns (nil, err)
+            return None, e
+
+    def RecheckResourcesDevice(self, ctx: Optional[Context], cs: Optional[Strategy], permission: str, subject: str,
+                               resources: Iterable[str], prev=None, transitions: int = CHANGE_ANY):
+        """Which of ``resources`` (ids of ``permission``'s type, "document#view") changed for
+        ``subject`` since ``prev``, the plane an earlier call with the same arguments returned (None:
+        nothing was granted, so ``CHANGE_GAINED`` yields the initial grant set). The request is
+        evaluated at the strategy's revision and compared with ``prev`` on the device
+        (Engine.recheck_ids); only count words and the change records come back. Returns
+        ``((plane, revision, changes), err)``: the new plane (a device tensor: the next call's
+        ``prev``), the evaluated revision and ``[(resource id, old, new), ...]`` in the caller's order,
+        old and new the PERM_* values of the selected ``transitions`` (``CHANGE_*``)."""
+        self.checkOverlap(ctx)
+        try:
+            subj_type, subj_id, subj_rel = _rel.ParseObjectSet(subject)
+            obj_type, obj_rel = _rel.ParseTypedRelation(permission)
+            eng = self.engine
+
+            def types():
+                rt, st = eng.type_id(obj_type), eng.type_id(subj_type)
+                perm = eng.relation_id(rt, obj_rel)
+                srel = ELLIPSIS if subj_rel in ("", "...") else eng.relation_id(st, subj_rel)
+                if TYPE_INVALID in (rt, st) or REL_INVALID in (perm, srel):
+                    raise GckError(GCK_E_NOT_FOUND, "object definition or relation not found")
+                return (rt, perm, st, srel), st, rt
+        except Exception as e:  # noqa: BLE001
+            return None, e
+        return self._recheck_list(ctx, cs, "RecheckResourcesDevice", subj_id, resources, VARY_RESOURCE, types, prev,
+                                  transitions)
+
+    def RecheckSubjectsDevice(self, ctx: Optional[Context], cs: Optional[Strategy], resource: str, permission: str,
+                              subject_type: str, subjects: Iterable[str], prev=None, transitions: int = CHANGE_ANY):
+        """The mirror: which of ``subjects`` (ids of ``subject_type``, "user" or "team#member") changed
+        on ``resource`` ("document:readme") for ``permission`` since ``prev``. Returns
+        ``((plane, revision, [(subject id, old, new), ...]), err)``."""
+        self.checkOverlap(ctx)
+        try:
+            res_type, res_id, _ = _rel.ParseObjectSet(resource)
+            stype, srel_name, _ = _rel._cut(subject_type, "#")
+            eng = self.engine
+
+            def types():
+                rt, st = eng.type_id(res_type), eng.type_id(stype)
+                perm = eng.relation_id(rt, permission)
+                srel = ELLIPSIS if srel_name in ("", "...") else eng.relation_id(st, srel_name)
+                if TYPE_INVALID in (rt, st) or REL_INVALID in (perm, srel):
+                    raise GckError(GCK_E_NOT_FOUND, "object definition or relation not found")
+                return (rt, perm, st, srel), rt, st
+        except Exception as e:  # noqa: BLE001
+            return None, e
+        return self._recheck_list(ctx, cs, "RecheckSubjectsDevice", res_id, subjects, VARY_SUBJECT, types, prev,
+                                  transitions)
+
+    def RecheckCrossDevice(self, ctx: Optional[Context], cs: Optional[Strategy], permission: str,
+                           resources: Iterable[str], subject_type: str, subjects: Iterable[str], prev=None,
+                           transitions: int = CHANGE_ANY):
+        """Every one of ``subjects`` (ids of ``subject_type``) against every one of ``resources`` (ids
+        of ``permission``'s type), compared with ``prev``, the plane an earlier call with the same
+        arguments returned (None: nothing was granted). Returns ``((plane, revision, changes), err)``:
+        the new plane (a device tensor, the next call's ``prev``), the evaluated revision and
+        ``[(subject id, resource id, old, new), ...]`` by subject and then in the resources' order
+        (Engine.recheck_cross_ids)."""
+        self.checkOverlap(ctx)
+        try:
+            import numpy as np
+            import torch
+            obj_type, obj_rel = _rel.ParseTypedRelation(permission)
+            stype, srel_name, _ = _rel._cut(subject_type, "#")
+            resources, subjects = list(resources), list(subjects)
+            requirement, revision = _requirement(cs)
+            eng = self.engine
+
+            def run():
+                rt, st = eng.type_id(obj_type), eng.type_id(stype)
+                perm = eng.relation_id(rt, obj_rel)
+                srel = ELLIPSIS if srel_name in ("", "...") else eng.relation_id(st, srel_name)
+                if TYPE_INVALID in (rt, st) or REL_INVALID in (perm, srel):
+                    raise GckError(GCK_E_NOT_FOUND, "object definition or relation not found")
+                dev = torch.device("cuda", eng.device)
+                up = lambda t, names: torch.from_numpy(
+                    np.ascontiguousarray(eng.intern(t, names), dtype=np.uint32).view(np.int32)).to(dev)
+                plane, rev, row_off, _, col, trans = eng.recheck_cross_ids(
+                    (rt, perm, st, srel), up(st, subjects), up(rt, resources), prev=prev, transitions=transitions,
+                    requirement=requirement, revision=revision)
+                off = row_off.tolist()
+                col, trans = col.tolist(), trans.tolist()
+                return plane, rev, [(subjects[s], resources[col[k]], trans[k] >> 2, trans[k] & 3)
+                                    for s in range(len(subjects)) for k in range(off[s], off[s + 1])]
             return retryRetriableErrors(ctx or Background, run), None
         except Exception as e:  # noqa: BLE001 — Go returns (nil, err)
             return None, e

@@ -701,6 +701,198 @@ void device_select_groups_empty(Engine& e, const gck_select_groups& sel, size_t 
   HIP_OK(hipStreamSynchronize((hipStream_t)stream));
 }
 
+// A recheck request (include/gck.h gck_recheck_list_device, gck_recheck_cross_device): the selection
+// over two planes — the caller's previous plane and the finished new one — a request-level step in the
+// two places the row selection runs: behind the last chunk or tile of the synchronous form, and in
+// device_collect of a submitted batch. The previous plane may be null (all zeros); its padding lanes,
+// the caller's memory, may hold anything, so every word's mask goes through change_tail_mask or
+// change_row_mask. No atomics; order by construction.
+//
+// Dense (k_dc_diff): k_dc_select over two words per thread. A block's first rank is the count before
+// the chunk (*prev; null: 0) plus its own recount of the chunk's earlier tiles plus the scan inside the
+// tile; the last tile's block writes the count so far to *next — never the word `prev` names — and to
+// *out_n. A plane longer than a chunk (chunk_words, at most max_batch / 32 words: what a block may count
+// again) is walked chunk by chunk on one stream, the count chained through the two words of `pair`, so
+// the work stays linear in the plane.
+struct DcDiff {
+  const unsigned long long* old_plane;  // the chunk's words of the previous plane; null: zeros
+  const unsigned long long* new_plane;
+  uint32_t words, n, transitions;  // the chunk's words and checks (n <= 32 * words: the tail lanes are cleared)
+  gck::ChangeOut o;
+  const uint32_t* prev;
+  uint32_t* next;
+  uint32_t* out_n;
+};
+
+__global__ void __launch_bounds__(kBlock) k_dc_diff(DcDiff a) {
+  __shared__ uint32_t before_tot[kWaves];
+  __shared__ uint32_t wave_tot[kWaves];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t tile0 = blockIdx.x * blockDim.x, t = tile0 + threadIdx.x;
+  const uint64_t* oldp = reinterpret_cast<const uint64_t*>(a.old_plane);
+  const uint64_t* newp = reinterpret_cast<const uint64_t*>(a.new_plane);
+  uint32_t mine = gck::change_count_strided(oldp, newp, threadIdx.x, tile0, blockDim.x, a.transitions, a.n);
+  for (int d = 32; d >= 1; d >>= 1) mine += (uint32_t)__shfl_xor((int)mine, d, 64);
+  const uint64_t nw = t < a.words ? newp[t] : 0ull, ow = t < a.words && oldp ? oldp[t] : 0ull;
+  const uint64_t m = t < a.words ? gck::change_tail_mask(ow, nw, a.transitions, t, a.n) : 0ull;
+  const uint32_t pc = gck::select_count(m);
+  uint32_t incl = pc;
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
+    if (lane >= (uint32_t)d) incl += up;
+  }
+  if (lane == 63u) {
+    wave_tot[wave] = incl;
+    before_tot[wave] = mine;
+  }
+  __syncthreads();
+  uint32_t base = a.prev ? *a.prev : 0u, tot = 0;
+  for (uint32_t k = 0; k < (uint32_t)kWaves; ++k) {
+    base += before_tot[k];
+    if (k < wave) base += wave_tot[k];
+    tot += wave_tot[k];
+  }
+  gck::change_write(ow, nw, m, t, base + incl - pc, a.o);
+  if (threadIdx.x == 0 && tile0 + blockDim.x >= a.words) {  // (wave 0: base holds nothing of this tile)
+    const uint32_t total = base + tot;
+    if (a.next) *a.next = total;
+    *a.out_n = total;
+  }
+}
+
+// The dense diff of a plane of n checks on `st`, chunk by chunk of chunk_words words; the caller
+// waits. `pair`: two device words for the chained count (needed only when the plane is more than one
+// chunk). n == 0 writes *d_out_n = 0 alone.
+static void dc_diff_plane(const gck_select_changes& sel, const unsigned long long* old_plane,
+                          const unsigned long long* new_plane, size_t n, const uint32_t* ids, uint32_t first_id,
+                          size_t chunk_words, uint32_t* pair, hipStream_t st) {
+  if (n == 0) {
+    HIP_OK(hipMemsetAsync(sel.d_out_n, 0, 4, st));
+    return;
+  }
+  const size_t words = (n + 31u) / 32u, cw = std::max<size_t>(chunk_words, 1);
+  if (words > cw && !pair) throw Error(GCK_E_DEVICE, "engine invariant violated: a chained diff without its count words");
+  for (size_t w0 = 0, k = 0; w0 < words; w0 += cw, ++k) {
+    const size_t pos = w0 * 32u;
+    DcDiff a{};
+    a.old_plane = old_plane ? old_plane + w0 : nullptr;
+    a.new_plane = new_plane + w0;
+    a.words = (uint32_t)std::min(cw, words - w0);
+    a.n = (uint32_t)std::min<size_t>((size_t)a.words * 32u, n - pos);
+    a.transitions = sel.transitions;
+    a.o = gck::ChangeOut{sel.d_out_ids, sel.d_out_pos, sel.d_out_trans, (uint32_t)std::min<size_t>(sel.cap, 0xFFFFFFFFu),
+                         ids ? ids + pos : nullptr, ids ? 0u : first_id + (uint32_t)pos, (uint32_t)pos};
+    a.prev = k ? pair + ((k - 1) & 1) : nullptr;
+    a.next = words > cw ? pair + (k & 1) : nullptr;
+    a.out_n = sel.d_out_n;
+    hipLaunchKernelGGL(k_dc_diff, dim3((a.words + kBlock - 1) / kBlock), dim3(kBlock), 0, st, a);
+    HIP_OK(hipGetLastError());
+  }
+}
+
+// Rows (k_dc_diff_rows_count, k_dc_rows_scan as it is, k_dc_diff_rows_write): the cross plane, S rows
+// of `stride` words, with the lane mapping of the row selection (dc_row_lane): a row takes L lanes, a
+// wave carries 64 / L rows, a longer row is walked in 64-word pieces with a carried rank. The result is
+// a CSR by row; there is no per-row limit.
+struct DcDiffRows {
+  const unsigned long long* old_plane;  // null: zeros
+  const unsigned long long* new_plane;
+  uint32_t S, R, stride, transitions;
+  uint32_t* row_off;
+  gck::ChangeRowsOut o;
+};
+
+// Word t of `row` as its change mask (ow / nw get the two plane words). Every lane of a wave stays
+// in the kernel: a lane beyond S or beyond the row holds two empty words.
+__device__ inline uint64_t dc_diff_row_word(const DcDiffRows& a, uint32_t row, uint32_t t, uint64_t& ow, uint64_t& nw) {
+  const bool in = row < a.S && t < a.stride;
+  const size_t at = (size_t)row * a.stride + t;
+  nw = in ? reinterpret_cast<const uint64_t*>(a.new_plane)[at] : 0ull;
+  ow = in && a.old_plane ? reinterpret_cast<const uint64_t*>(a.old_plane)[at] : 0ull;
+  return in ? gck::change_row_mask(ow, nw, a.transitions, t, a.R) : 0ull;
+}
+
+__global__ void __launch_bounds__(kBlock) k_dc_diff_rows_count(DcDiffRows a) {
+  uint32_t L, row, j;
+  dc_row_lane(a.stride, L, row, j);
+  uint32_t sum = 0;
+  for (uint32_t p0 = 0; p0 < a.stride; p0 += gck::kRowPiece) {  // (one pass unless stride > 64; the carried count is `sum`)
+    uint64_t ow, nw;
+    sum += gck::select_count(dc_diff_row_word(a, row, p0 + j, ow, nw));
+  }
+  for (uint32_t d = L >> 1; d >= 1u; d >>= 1) sum += (uint32_t)__shfl_xor((int)sum, (int)d, 64);  // (d < L: inside the row's lanes)
+  if (j == 0u && row < a.S) a.row_off[row + 1u] = sum;
+}
+
+__global__ void __launch_bounds__(kBlock) k_dc_diff_rows_write(DcDiffRows a) {
+  uint32_t L, row, j;
+  dc_row_lane(a.stride, L, row, j);
+  const uint32_t row_base = row < a.S ? a.row_off[row] : 0u;
+  uint32_t carry = 0;  // the row's changes in the pieces before this one (the same in every lane of the row)
+  for (uint32_t p0 = 0; p0 < a.stride; p0 += gck::kRowPiece) {
+    const uint32_t t = p0 + j;
+    uint64_t ow, nw;
+    const uint64_t m = dc_diff_row_word(a, row, t, ow, nw);
+    const uint32_t pc = gck::select_count(m);
+    uint32_t incl = pc;
+    for (uint32_t d = 1; d < L; d <<= 1) {
+      const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
+      if (j >= d) incl += up;  // (lane - d is inside the row's lanes)
+    }
+    gck::change_write_row(ow, nw, m, t * 32u, carry + incl - pc, row_base, a.o);
+    if (a.stride <= gck::kRowPiece) break;
+    carry += (uint32_t)__shfl((int)incl, 63, 64);  // (L == 64: the wave is one row)
+  }
+}
+
+// The three kernels on `st`; the caller waits. S == 0 writes row_off[0] and *out_n alone; R == 0
+// (stride 0, no plane read) writes S + 1 zeros.
+static void dc_diff_rows(const gck_select_row_changes& sel, const unsigned long long* old_plane,
+                         const unsigned long long* new_plane, size_t S, size_t R, const uint32_t* resources,
+                         hipStream_t st) {
+  DcDiffRows a{};
+  a.old_plane = old_plane;
+  a.new_plane = new_plane;
+  a.S = (uint32_t)S;
+  a.R = (uint32_t)R;
+  a.stride = (uint32_t)((R + 31u) / 32u);
+  a.transitions = sel.transitions;
+  a.row_off = sel.d_out_row_off;
+  a.o = gck::ChangeRowsOut{sel.d_out_ids, sel.d_out_col, sel.d_out_trans, (uint32_t)std::min<size_t>(sel.cap, 0xFFFFFFFFu),
+                           resources};
+  const uint32_t per_block = (uint32_t)kWaves * (64u / gck::select_row_lanes(a.stride));
+  const dim3 grid((a.S + per_block - 1u) / per_block), block(kBlock);
+  if (a.S) {
+    hipLaunchKernelGGL(k_dc_diff_rows_count, grid, block, 0, st, a);
+    HIP_OK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_dc_rows_scan, dim3(1), block, 0, st, a.row_off, a.S, sel.d_out_n);
+  HIP_OK(hipGetLastError());
+  if (a.S && a.stride && a.o.cap) {
+    hipLaunchKernelGGL(k_dc_diff_rows_write, grid, block, 0, st, a);
+    HIP_OK(hipGetLastError());
+  }
+}
+
+// The plane-only calls (gck_diff_planes_device, gck_diff_cross_planes_device): the selection alone,
+// synchronous on `stream`. The dense form chains its count through w's pair of count words, which no
+// batch uses while the caller holds the workspace, in chunks of what a batch of w would be.
+void device_diff_planes(Engine& e, Workspace& w, const gck_select_changes& sel, const uint64_t* d_old,
+                        const uint64_t* d_new, size_t n, const uint32_t* d_ids, uint32_t first_id, void* stream) {
+  HIP_OK(hipSetDevice(e.device));
+  dc_diff_plane(sel, reinterpret_cast<const unsigned long long*>(d_old), reinterpret_cast<const unsigned long long*>(d_new), n,
+                d_ids, first_id, (w.max_batch & ~(size_t)31) / 32u, w.dc_aux + 2, (hipStream_t)stream);
+  HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+}
+
+void device_diff_rows(Engine& e, const gck_select_row_changes& sel, const uint64_t* d_old, const uint64_t* d_new,
+                      size_t S, size_t R, const uint32_t* d_resources, void* stream) {
+  HIP_OK(hipSetDevice(e.device));
+  dc_diff_rows(sel, reinterpret_cast<const unsigned long long*>(d_old), reinterpret_cast<const unsigned long long*>(d_new), S,
+               R, d_resources, (hipStream_t)stream);
+  HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+}
+
 // The word a device request counts its errors in, cleared on `st` before the request's first chunk:
 // the caller's, or the workspace's own (which stays 0 until an emit adds to it).
 // (the caller's word of a submitted batch is left to the batch: CompactRun::zero_cnt)
@@ -818,6 +1010,16 @@ static void device_collect(Engine& e, Workspace& w) {
   }
   if (c.select_cols) {  // (its twin by resource: the same finished plane, by column)
     dc_select_cols(c.csel, c.out, c.csel_S, c.R, c.csel_ids, st);
+    launched = true;
+  }
+  if (c.diff) {
+    // a submitted recheck request: this batch was its one chunk, so the dense plane is finished once
+    // the kernels above have run on this stream (one chunk: no chained count)
+    dc_diff_plane(c.dsel, c.diff_prev, c.out, n, c.dsel_ids, c.dsel_first, words, nullptr, st);
+    launched = true;
+  }
+  if (c.diff_rows) {  // (its cross form: this batch was the one tile or chunk of the whole plane)
+    dc_diff_rows(c.rdsel, c.diff_prev, c.out, c.rdsel_S, c.R, c.rdsel_ids, st);
     launched = true;
   }
   uint32_t bad_group = 0xFFFFFFFFu;

@@ -265,6 +265,17 @@ struct CompactRun {
   const uint32_t* gsel_off = nullptr;  // the request's S + 1 offsets
   const uint32_t* gsel_ids = nullptr;  // ... and its candidates
   size_t gsel_S = 0;
+  // a submitted recheck request's batch (CompactReq::diff / diff_rows): the whole request as well, so
+  // its collect ends with the diff of `out` against the caller's previous plane (dc_diff_plane,
+  // dc_diff_rows; diff_prev may be null: all zeros)
+  bool diff = false, diff_rows = false;
+  const unsigned long long* diff_prev = nullptr;
+  gck_select_changes dsel{};
+  const uint32_t* dsel_ids = nullptr;  // the list request's varying ids (null: a range from dsel_first)
+  uint32_t dsel_first = 0;
+  gck_select_row_changes rdsel{};
+  const uint32_t* rdsel_ids = nullptr;  // the cross request's resource list
+  size_t rdsel_S = 0;
   bool in_place() const { return mode == kInPlace; }
   bool table_join() const { return mode == kInPlace && indexed; }  // the join reads index bytes and a shape table
 };
@@ -4074,6 +4085,22 @@ void device_submit_compact(Engine& e, Workspace* w, const CompactReq& req, int64
     w->cb.gsel_S = q.S;
     w->cb.out = reinterpret_cast<unsigned long long*>(q.packed);
   }
+  if (q.diff) {  // (likewise: its collect compares the dense plane with the previous one)
+    w->cb.diff = true;
+    w->cb.dsel = *q.diff;
+    w->cb.diff_prev = reinterpret_cast<const unsigned long long*>(q.prev);
+    w->cb.dsel_ids = q.ids;
+    w->cb.dsel_first = q.first_id;
+    w->cb.out = reinterpret_cast<unsigned long long*>(q.packed);
+  }
+  if (q.diff_rows) {  // (... and the cross plane, row by row)
+    w->cb.diff_rows = true;
+    w->cb.rdsel = *q.diff_rows;
+    w->cb.diff_prev = reinterpret_cast<const unsigned long long*>(q.prev);
+    w->cb.rdsel_ids = q.resources;
+    w->cb.rdsel_S = q.S;
+    w->cb.out = reinterpret_cast<unsigned long long*>(q.packed);
+  }
 }
 
 // The chunks of a request that is no cross request: max_batch checks each, rounded down to a multiple
@@ -4137,6 +4164,11 @@ void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const Compact
       dc_select_cols(*q.sel_cols, reinterpret_cast<const unsigned long long*>(q.packed), q.S, q.R, q.subjects, w0->stream);
       HIP_OK(hipStreamSynchronize(w0->stream));
     }
+    if (q.diff_rows) {  // (the same place, for a recheck request: the finished plane against the previous one)
+      dc_diff_rows(*q.diff_rows, reinterpret_cast<const unsigned long long*>(q.prev),
+                   reinterpret_cast<const unsigned long long*>(q.packed), q.S, q.R, q.resources, w0->stream);
+      HIP_OK(hipStreamSynchronize(w0->stream));
+    }
     return;
   }
   if (req.cross()) {
@@ -4153,7 +4185,16 @@ void device_check_compact(Engine& e, Workspace* w0, Workspace* w1, const Compact
     return;
   }
   std::vector<gck_item_error> errs;
-  compact_chunks(e, w0, w1, req, now_us, cav, errs);
+  const size_t mb = compact_chunks(e, w0, w1, req, now_us, cav, errs);
+  if (req.diff) {
+    // a recheck request: every chunk is collected — its stream completed — so the dense plane is
+    // finished and w0 is idle: the diff against the previous plane, walked in the request's own chunks
+    // with the count chained through w0's pair of count words, then the wait
+    dc_diff_plane(*req.diff, reinterpret_cast<const unsigned long long*>(req.prev),
+                  reinterpret_cast<const unsigned long long*>(req.packed), req.n, req.ids, req.first_id, mb / 32u,
+                  w0->dc_aux + 2, w0->stream);
+    HIP_OK(hipStreamSynchronize(w0->stream));
+  }
   if (req.groups()) {
     // every chunk is collected — its stream completed — so the dense plane is finished: the group
     // selection over the whole of it, the offsets' check word behind it, then the wait

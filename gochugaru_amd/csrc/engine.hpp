@@ -470,7 +470,22 @@ struct CompactReq {
   const uint32_t* group_off = nullptr;
   const gck_select_groups* sel_groups = nullptr;
   bool groups() const { return sel_groups != nullptr; }
+  // a recheck request (gck_recheck_list_device / gck_recheck_cross_device; a list or cross request over
+  // device buffers): once the whole plane is finished it is compared with `prev`, the caller's previous
+  // plane in the same layout (device memory; null: all zeros), and the changes go to *diff's arrays in
+  // ascending position, or to *diff_rows' as a CSR by subject (copied by the submit;
+  // device_compact.inc dc_diff_plane, dc_diff_rows). At most one of the two
+  const uint64_t* prev = nullptr;
+  const gck_select_changes* diff = nullptr;
+  const gck_select_row_changes* diff_rows = nullptr;
 };
+// The plane-only diffs (gck_diff_planes_device, gck_diff_cross_planes_device), synchronous on `stream`;
+// the dense form uses w's count words. The row form with S == 0 or R == 0 reads no plane: an empty
+// recheck cross request's outputs.
+void device_diff_planes(Engine& e, Workspace& w, const gck_select_changes& sel, const uint64_t* d_old,
+                        const uint64_t* d_new, size_t n, const uint32_t* d_ids, uint32_t first_id, void* stream);
+void device_diff_rows(Engine& e, const gck_select_row_changes& sel, const uint64_t* d_old, const uint64_t* d_new,
+                      size_t S, size_t R, const uint32_t* d_resources, void* stream);
 // The outputs of an empty cross filter request (S == 0 or R == 0), synchronous on `stream`.
 void device_select_rows_empty(Engine& e, const gck_select_rows& sel, size_t S, void* stream);
 // Likewise by resource: col_off[0] and the count alone for R == 0, else R + 1 zero offsets.

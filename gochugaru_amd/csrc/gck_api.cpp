@@ -1919,6 +1919,226 @@ int gck_filter_submit_groups_device(gck_engine* ge, const gck_consistency* cs, c
   });
 }
 
+// ---- recheck requests (include/gck.h gck_recheck_list_device) ---------------------------------
+
+// The rules of the two forms beyond the underlying call's own, each in one function shared by the
+// form's entry points, its plane-only call and the host hooks (gck_test_changes_rule,
+// gck_test_row_changes_rule): empty when the arguments are good, else what is wrong with them. Reads
+// no buffer but *sel. `words`: the 8-B words of each plane; need_plane: the new plane is required.
+static std::string change_common_fault(const std::string& g, uint32_t transitions, uint32_t reserved, const void* d_out_n,
+                                       bool arrays, size_t cap, const uint64_t* d_prev, const uint64_t* d_out,
+                                       size_t words, bool need_plane) {
+  const auto aligned = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+  if (transitions == 0 || (transitions & ~(uint32_t)GCK_CHANGE_ANY))
+    return g + "transitions must be non-zero and within GCK_CHANGE_ANY";
+  if (reserved != 0) return g + "reserved must be 0";
+  if (!d_out_n) return g + "null d_out_n";
+  if (need_plane && !d_out) return g + "null d_out_packed";
+  if (cap != 0 && !arrays) return g + "cap > 0 without an output array";
+  if (!aligned(d_prev, 8) || !aligned(d_out, 8)) return g + "d_prev_packed or d_out_packed is not 8-byte aligned";
+  if (d_prev && d_out && words) {
+    const uintptr_t a = (uintptr_t)d_prev, b = (uintptr_t)d_out, len = (uintptr_t)words * 8u;
+    if (a < b + len && b < a + len) return g + "d_prev_packed overlaps d_out_packed";
+  }
+  return std::string();
+}
+
+static std::string changes_fault(const gck_select_changes* sel, const uint64_t* d_prev, const uint64_t* d_out, size_t n,
+                                 bool need_plane) {
+  const auto aligned = [](const void* p) { return ((uintptr_t)p & 3u) == 0; };
+  const std::string g = "recheck request: ";
+  if (!sel) return g + "null gck_select_changes";
+  const std::string f =
+      change_common_fault(g, sel->transitions, sel->reserved, sel->d_out_n, sel->d_out_ids || sel->d_out_pos || sel->d_out_trans,
+                          sel->cap, d_prev, d_out, n / 32u + (n % 32u != 0), need_plane);
+  if (!f.empty()) return f;
+  if (!aligned(sel->d_out_ids) || !aligned(sel->d_out_pos) || !aligned(sel->d_out_n))
+    return g + "d_out_ids, d_out_pos or d_out_n is not 4-byte aligned";
+  return std::string();
+}
+
+static std::string row_changes_fault(const gck_select_row_changes* sel, const uint64_t* d_prev, const uint64_t* d_out,
+                                     size_t S, size_t R, bool need_plane) {
+  const auto aligned = [](const void* p) { return ((uintptr_t)p & 3u) == 0; };
+  const std::string g = "recheck cross request: ";
+  if (!sel) return g + "null gck_select_row_changes";
+  if (!sel->d_out_row_off) return g + "null d_out_row_off";
+  const size_t stride = R / 32u + (R % 32u != 0);
+  if (stride && S > SIZE_MAX / 8u / stride) return g + "the plane is too large";
+  const std::string f =
+      change_common_fault(g, sel->transitions, sel->reserved, sel->d_out_n, sel->d_out_ids || sel->d_out_col || sel->d_out_trans,
+                          sel->cap, d_prev, d_out, S * stride, need_plane);
+  if (!f.empty()) return f;
+  if (!aligned(sel->d_out_row_off) || !aligned(sel->d_out_ids) || !aligned(sel->d_out_col) || !aligned(sel->d_out_n))
+    return g + "d_out_row_off, d_out_ids, d_out_col or d_out_n is not 4-byte aligned";
+  return std::string();
+}
+
+// The rules against the call, before anything is launched or written; then the list device request
+// with the diff (`sel` is the caller's: the engine copies it before the call returns).
+static CompactReq recheck_list_request(const uint64_t* d_prev, const gck_select_changes* sel, const gck_uniform* hdr,
+                                       uint32_t fixed_id, uint32_t vary, const uint32_t* d_ids, uint32_t first_id, size_t n,
+                                       size_t n_contexts, uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                       uint32_t* d_out_n_errs, void* stream, bool engine_stream) {
+  const std::string fault = changes_fault(sel, d_prev, d_out_packed, n, true);
+  REQUIRE(fault.empty(), GCK_E_INVALID_ARGUMENT, fault);
+  CompactReq q = device_request(
+      list_request(hdr, fixed_id, vary, d_ids, first_id, n, n_contexts, d_out_packed, d_out_errs, err_cap, nullptr),
+      d_out_errs, d_out_n_errs, stream, engine_stream);
+  q.prev = d_prev;
+  q.diff = sel;
+  return q;
+}
+
+int gck_recheck_list_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                            uint32_t vary, const uint32_t* d_ids, uint32_t first_id, size_t n,
+                            const char* const* contexts, const size_t* context_lens, size_t n_contexts, int64_t now_us,
+                            const uint64_t* d_prev_packed, const gck_select_changes* sel, uint64_t* d_out_packed,
+                            gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, void* stream,
+                            uint64_t* out_revision) {
+  return guard([&] {
+    Engine& e = need(ge);
+    const CompactReq req = recheck_list_request(d_prev_packed, sel, hdr, fixed_id, vary, d_ids, first_id, n, n_contexts,
+                                                d_out_packed, d_out_errs, err_cap, d_out_n_errs, stream, true);
+    check_device_sync(e, {cs, contexts, context_lens, n_contexts}, req, now_us, out_revision);
+    if (req.n == 0) device_zero_count(e, sel->d_out_n, stream);  // (no check ran: no change)
+  });
+}
+
+int gck_recheck_submit_list_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                                   uint32_t vary, const uint32_t* d_ids, uint32_t first_id, size_t n,
+                                   const char* const* contexts, const size_t* context_lens, size_t n_contexts,
+                                   int64_t now_us, const uint64_t* d_prev_packed, const gck_select_changes* sel,
+                                   uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                   uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    check_submit_flags(flags);
+    const bool own = (flags & GCK_SUBMIT_ENGINE_STREAM) != 0;
+    const CompactReq req = recheck_list_request(d_prev_packed, sel, hdr, fixed_id, vary, d_ids, first_id, n, n_contexts,
+                                                d_out_packed, d_out_errs, err_cap, d_out_n_errs, stream, own);
+    gck_batch* b = submit_device(e, {cs, contexts, context_lens, n_contexts}, req, now_us);
+    if (req.n == 0) {
+      try {
+        device_zero_count(e, sel->d_out_n, own ? nullptr : stream);
+      } catch (...) {
+        delete b;
+        throw;
+      }
+    }
+    *out = b;
+  });
+}
+
+static CompactReq recheck_cross_request(const uint64_t* d_prev, const gck_select_row_changes* sel, const gck_uniform* hdr,
+                                        const uint32_t* d_subjects, size_t S, const uint32_t* d_resources, size_t R,
+                                        size_t n_contexts, uint64_t* d_out_packed, gck_item_error* d_out_errs,
+                                        size_t err_cap, uint32_t* d_out_n_errs, void* stream, bool engine_stream) {
+  const std::string fault = row_changes_fault(sel, d_prev, d_out_packed, S, R, true);
+  REQUIRE(fault.empty(), GCK_E_INVALID_ARGUMENT, fault);
+  CompactReq q = cross_device_request(hdr, d_subjects, S, d_resources, R, n_contexts, d_out_packed, d_out_errs, err_cap,
+                                      d_out_n_errs, stream, engine_stream);
+  q.prev = d_prev;
+  q.diff_rows = sel;
+  return q;
+}
+
+int gck_recheck_cross_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr,
+                             const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                             size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                             size_t n_contexts, int64_t now_us, const uint64_t* d_prev_packed,
+                             const gck_select_row_changes* sel, uint64_t* d_out_packed, gck_item_error* d_out_errs,
+                             size_t err_cap, uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision) {
+  return guard([&] {
+    Engine& e = need(ge);
+    const CompactReq req = recheck_cross_request(d_prev_packed, sel, hdr, d_subjects, n_subjects, d_resources, n_resources,
+                                                 n_contexts, d_out_packed, d_out_errs, err_cap, d_out_n_errs, stream, true);
+    const CallCtx c{cs, contexts, context_lens, n_contexts};
+    if (req.n == 0) {  // (no check runs: the count word, then the offsets of S rows without a change)
+      check_device_sync(e, c, req, now_us, out_revision);
+      return device_diff_rows(e, *sel, nullptr, nullptr, n_subjects, n_resources, nullptr, stream);
+    }
+    // (the workspaces of gck_check_bulk_cross_device)
+    uint32_t rows = 0;
+    const size_t mb = max_batch_of(e);
+    const size_t one = gck_cross_tile_device(n_subjects, n_resources, mb, &rows) ? (size_t)rows * n_resources
+                                                                                 : (mb & ~(size_t)31);
+    check_sync(e, c, req.n, one, out_revision,
+               [&](Workspace* w0, Workspace* w1, const CavCall& cav) { device_check_compact(e, w0, w1, req, now_us, cav); });
+  });
+}
+
+int gck_recheck_submit_cross_device(gck_engine* ge, const gck_consistency* cs, const gck_uniform* hdr,
+                                    const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                                    size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                                    size_t n_contexts, int64_t now_us, const uint64_t* d_prev_packed,
+                                    const gck_select_row_changes* sel, uint64_t* d_out_packed,
+                                    gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, uint32_t flags,
+                                    void* stream, gck_batch** out) {
+  return guard([&] {
+    Engine& e = need(ge);
+    REQUIRE(out, GCK_E_INVALID_ARGUMENT, "null out");
+    *out = nullptr;
+    check_submit_flags(flags);
+    const bool own = (flags & GCK_SUBMIT_ENGINE_STREAM) != 0;
+    const CompactReq req = recheck_cross_request(d_prev_packed, sel, hdr, d_subjects, n_subjects, d_resources, n_resources,
+                                                 n_contexts, d_out_packed, d_out_errs, err_cap, d_out_n_errs, stream, own);
+    uint32_t rows = 0;
+    REQUIRE(req.n == 0 || (gck_cross_tile_device(n_subjects, n_resources, max_batch_of(e), &rows) && rows == n_subjects),
+            GCK_E_INVALID_ARGUMENT,
+            "submitted recheck cross request of " + std::to_string(n_subjects) + " x " + std::to_string(n_resources) +
+                " is not one tile (gck_cross_tile_device)");
+    gck_batch* b = submit_device(e, {cs, contexts, context_lens, n_contexts}, req, now_us);
+    if (req.n == 0) {
+      try {
+        device_diff_rows(e, *sel, nullptr, nullptr, n_subjects, n_resources, nullptr, own ? nullptr : stream);
+      } catch (...) {
+        delete b;
+        throw;
+      }
+    }
+    *out = b;
+  });
+}
+
+// The plane-only calls: the selection alone over two planes the caller holds.
+int gck_diff_planes_device(gck_engine* ge, const uint64_t* d_old, const uint64_t* d_new, size_t n, const uint32_t* d_ids,
+                           uint32_t first_id, const gck_select_changes* sel, void* stream) {
+  return guard([&] {
+    Engine& e = need(ge);
+    const std::string fault = changes_fault(sel, d_old, d_new, n, n != 0);
+    REQUIRE(fault.empty(), GCK_E_INVALID_ARGUMENT, fault);
+    REQUIRE(n < 0x100000000ull, GCK_E_INVALID_ARGUMENT, "recheck request: " + std::to_string(n) + " checks reach 2^32");
+    REQUIRE(((uintptr_t)d_ids & 3u) == 0, GCK_E_INVALID_ARGUMENT, "recheck request: d_ids is not 4-byte aligned");
+    REQUIRE(d_ids || (uint64_t)first_id + n <= 0x100000000ull, GCK_E_INVALID_ARGUMENT,
+            "recheck request: the range " + std::to_string(first_id) + " + " + std::to_string(n) + " passes 2^32");
+    precheck(e);
+    WsLease lease(e);  // (its pair of count words chains a plane of more than one chunk)
+    device_diff_planes(e, *lease.w, *sel, d_old, d_new, n, d_ids, first_id, stream);
+  });
+}
+
+int gck_diff_cross_planes_device(gck_engine* ge, const uint64_t* d_old, const uint64_t* d_new, size_t n_subjects,
+                                 size_t n_resources, const uint32_t* d_resources, const gck_select_row_changes* sel,
+                                 void* stream) {
+  return guard([&] {
+    Engine& e = need(ge);
+    const bool checks = n_subjects != 0 && n_resources != 0;
+    const std::string fault = row_changes_fault(sel, d_old, d_new, n_subjects, n_resources, checks);
+    REQUIRE(fault.empty(), GCK_E_INVALID_ARGUMENT, fault);
+    REQUIRE(n_subjects < 0x100000000ull && n_resources < 0x100000000ull &&
+                (!checks || n_subjects <= 0xFFFFFFFFull / n_resources),
+            GCK_E_INVALID_ARGUMENT, "recheck cross request: the checks reach 2^32");
+    REQUIRE(((uintptr_t)d_resources & 3u) == 0, GCK_E_INVALID_ARGUMENT, "recheck cross request: d_resources is not 4-byte aligned");
+    REQUIRE(!checks || !sel->d_out_ids || d_resources, GCK_E_INVALID_ARGUMENT,
+            "recheck cross request: d_out_ids without d_resources");
+    precheck(e);
+    device_diff_rows(e, *sel, d_old, d_new, n_subjects, n_resources, d_resources, stream);
+  });
+}
+
 int gck_device_compact_stats(gck_engine* ge, uint64_t out[2]) {
   return guard([&] {
     Engine& e = need(ge);
@@ -2498,6 +2718,105 @@ int gck_test_select_groups(const uint64_t* words, uint32_t n, const uint32_t* of
       for (uint32_t t = p0; t < nw && t < p0 + L; ++t) {
         const uint64_t word = words[w0 + t], m = gck::select_group_mask(word, mask, w0 + t, lo, hi);
         gck::select_write_row(word, m, (w0 + t) * 32u, rank, out_row_off[s], group_limit, o);
+        rank += gck::select_count(m);
+      }
+      carry = rank;
+    }
+  }
+  return 0;
+}
+
+// gck_test_changes_rule / gck_test_row_changes_rule: the recheck entry points' rule functions
+// (changes_fault, row_changes_fault) over the same arguments, reading no buffer: 0 when they are
+// good, -1 when the entry points refuse them. need_plane: d_out is required (a request call; a
+// plane-only call with checks).
+int gck_test_changes_rule(const gck_select_changes* sel, const uint64_t* d_prev, const uint64_t* d_out, size_t n,
+                          int need_plane) {
+  return changes_fault(sel, d_prev, d_out, n, need_plane != 0).empty() ? 0 : -1;
+}
+
+int gck_test_row_changes_rule(const gck_select_row_changes* sel, const uint64_t* d_prev, const uint64_t* d_out, size_t S,
+                              size_t R, int need_plane) {
+  return row_changes_fault(sel, d_prev, d_out, S, R, need_plane != 0).empty() ? 0 : -1;
+}
+
+// gck_test_change_plane: the dense diff of a recheck request (select_plane.hpp; k_dc_diff and
+// dc_diff_plane in device_compact.inc) over two planes of ceil(n / 32) words on the host, chunk by chunk
+// of chunk_words words and tile by tile as the kernel's blocks take a chunk: a tile's first rank is
+// the count before the chunk plus a recount of the chunk's words before the tile, ranks inside the tile
+// run on, and the count is carried from chunk to chunk. old_words may be null (all zeros). Outputs and
+// NULL rules are gck_select_changes' (src_ids: the varying ids, or null for first_id + i). -1 for the
+// rule's argument errors. What this pins is the per-word functions, the tail mask and the protocol;
+// the kernel's lane scan is covered only by the GPU tests.
+int gck_test_change_plane(const uint64_t* old_words, const uint64_t* new_words, uint32_t n, uint32_t transitions,
+                          uint32_t chunk_words, size_t cap, const uint32_t* src_ids, uint32_t first_id, uint32_t* out_ids,
+                          uint32_t* out_pos, uint8_t* out_trans, uint32_t* out_n) {
+  gck_select_changes sel{transitions, 0u, out_ids, out_pos, out_trans, cap, out_n};
+  if (!changes_fault(&sel, old_words, new_words, n, n != 0).empty() || chunk_words == 0) return -1;
+  const uint32_t words = n / 32u + (n % 32u != 0);
+  uint32_t total = 0;
+  for (uint32_t w0 = 0; w0 < words; w0 += std::min(chunk_words, words - w0)) {  // dc_diff_plane's chunks
+    const uint32_t cw = std::min(chunk_words, words - w0), pos = w0 * 32u, cn = std::min(cw * 32u, n - pos);
+    const uint64_t* o_ = old_words ? old_words + w0 : nullptr;
+    const uint64_t* n_ = new_words + w0;
+    const gck::ChangeOut o{out_ids, out_pos, out_trans, (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu),
+                           src_ids ? src_ids + pos : nullptr, src_ids ? 0u : first_id + pos, pos};
+    const uint32_t base = total;
+    for (uint32_t tile0 = 0; tile0 < cw; tile0 += gck::kSelBlock) {  // k_dc_diff's blocks
+      uint32_t rank = base + gck::change_count_strided(o_, n_, 0, tile0, 1, transitions, cn);
+      for (uint32_t t = tile0; t < cw && t < tile0 + gck::kSelBlock; ++t) {
+        const uint64_t ow = o_ ? o_[t] : 0ull, m = gck::change_tail_mask(ow, n_[t], transitions, t, cn);
+        gck::change_write(ow, n_[t], m, t, rank, o);
+        rank += gck::select_count(m);
+      }
+      total = rank;
+    }
+  }
+  *out_n = total;
+  return 0;
+}
+
+// gck_test_change_rows: the row form (k_dc_diff_rows_count, k_dc_rows_scan and k_dc_diff_rows_write)
+// over two row-padded planes of S rows of ceil(R / 32) words on the host, row by row and piece by
+// piece of kRowPiece words as the kernels walk them: the counts, their prefix, then each word's changes
+// from the in-row rank the words before it give. Outputs and NULL rules are gck_select_row_changes'
+// (src_ids: the resource list, needed with out_ids). -1 for the rule's argument errors.
+int gck_test_change_rows(const uint64_t* old_words, const uint64_t* new_words, uint32_t S, uint32_t R, uint32_t transitions,
+                         size_t cap, const uint32_t* src_ids, uint32_t* out_row_off, uint32_t* out_ids, uint32_t* out_col,
+                         uint8_t* out_trans, uint32_t* out_n) {
+  gck_select_row_changes sel{transitions, 0u, out_row_off, out_ids, out_col, out_trans, cap, out_n};
+  if (!row_changes_fault(&sel, old_words, new_words, S, R, S != 0 && R != 0).empty()) return -1;
+  if (out_ids && !src_ids && R) return -1;
+  if (S && R && S > 0xFFFFFFFFu / R) return -1;
+  const uint32_t stride = R / 32u + (R % 32u != 0);
+  const gck::ChangeRowsOut o{out_ids, out_col, out_trans, (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu), src_ids};
+  const auto row_word = [&](uint32_t s, uint32_t t, uint64_t& ow, uint64_t& nw) {
+    const size_t at = (size_t)s * stride + t;
+    nw = new_words[at];
+    ow = old_words ? old_words[at] : 0ull;
+    return gck::change_row_mask(ow, nw, transitions, t, R);
+  };
+  for (uint32_t s = 0; s < S; ++s) {  // k_dc_diff_rows_count
+    uint32_t sum = 0;
+    for (uint32_t p0 = 0; p0 < stride; p0 += gck::kRowPiece)
+      for (uint32_t t = p0; t < stride && t < p0 + gck::kRowPiece; ++t) {
+        uint64_t ow, nw;
+        sum += gck::select_count(row_word(s, t, ow, nw));
+      }
+    out_row_off[s + 1u] = sum;
+  }
+  uint32_t run = 0;  // k_dc_rows_scan
+  for (uint32_t s = 0; s < S; ++s) out_row_off[s + 1u] = run += out_row_off[s + 1u];
+  out_row_off[0] = 0u;
+  *out_n = run;
+  for (uint32_t s = 0; s < S && stride && o.cap; ++s) {  // k_dc_diff_rows_write
+    uint32_t carry = 0;
+    for (uint32_t p0 = 0; p0 < stride; p0 += gck::kRowPiece) {
+      uint32_t rank = carry;
+      for (uint32_t t = p0; t < stride && t < p0 + gck::kRowPiece; ++t) {
+        uint64_t ow, nw;
+        const uint64_t m = row_word(s, t, ow, nw);
+        gck::change_write_row(ow, nw, m, t * 32u, rank, out_row_off[s], o);
         rank += gck::select_count(m);
       }
       carry = rank;

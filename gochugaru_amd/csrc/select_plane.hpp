@@ -8,7 +8,10 @@
 // (gck_filter_cross_cols_device; k_dc_cols_count / k_dc_cols_write, gck_test_select_cols). Last, the
 // group-segmented form over a dense plane cut by caller-given offsets, and the group lookup of its
 // pair expansion (gck_filter_groups_device; k_dc_group_pairs, k_dc_groups_count / k_dc_groups_write,
-// gck_test_group_of and gck_test_select_groups).
+// gck_test_group_of and gck_test_select_groups). At the end, the selection over two planes of one
+// request: the checks whose value changed from the old plane to the new one (gck_recheck_list_device,
+// gck_recheck_cross_device; k_dc_diff, k_dc_diff_rows_count / k_dc_diff_rows_write, gck_test_change_plane
+// and gck_test_change_rows).
 //
 // A word holds 32 checks, check b in bits 2b .. 2b + 1 (GCK_PERM_*: 0 unspecified — an errored check
 // and a tail lane alike —, 1 NO, 2 HAS, 3 CONDITIONAL). `mask` has bit v set when value v survives
@@ -267,5 +270,117 @@ GCK_SEL_HD inline uint64_t select_group_mask(uint64_t word, uint32_t mask, uint3
 // A group's kept survivors are written by select_write_row: SelectRowsOut with the candidate list as
 // src_ids and the positions as `col`, col0 = 32 t — a survivor's column is its position k in the
 // request, its id candidates[k].
+
+// ---- the selection over two planes (include/gck.h gck_recheck_list_device, gck_recheck_cross_device) ----
+// Two planes of one request, the caller's previous one and the one just written: check b of a word
+// changed when its 2-bit fields differ, from v in the old word to w in the new one. `transitions` has
+// bit 4 v + w set when that pair is selected (GCK_CHANGE_*; the diagonal bits 4 v + v are never set).
+// Value 0 — an errored check — is a legal end of a transition. The change mask keeps select_mask's
+// spacing, so a count is one popcount and the kernels are the selection kernels over two words.
+// The old plane is the caller's memory: the padding lanes of a row's last word, or of a dense plane's
+// last word, may hold anything in either plane, so every reader clears them (change_row_mask,
+// change_tail_mask) and a change's column or position is below R or n whatever they hold.
+
+constexpr uint32_t kChangeAny = 0x7BDEu;  // every off-diagonal pair (GCK_CHANGE_ANY)
+
+// Bit 2b set: check b went from v to w, v != w, and `transitions` selects (v, w).
+GCK_SEL_HD inline uint64_t change_mask(uint64_t old_word, uint64_t new_word, uint32_t transitions) {
+  const uint64_t k = 0x5555555555555555ull;
+  const uint64_t oe = old_word & k, oo = (old_word >> 1) & k, ne = new_word & k, no = (new_word >> 1) & k;
+  const uint64_t ov[4] = {~oe & ~oo & k, oe & ~oo, oo & ~oe, oo & oe};
+  const uint64_t nv[4] = {~ne & ~no & k, ne & ~no, no & ~ne, no & ne};
+  uint64_t m = 0;
+#pragma unroll
+  for (uint32_t v = 0; v < 4u; ++v)
+#pragma unroll
+    for (uint32_t w = 0; w < 4u; ++w)
+      if (v != w && ((transitions >> (4u * v + w)) & 1u)) m |= ov[v] & nv[w];
+  return m;
+}
+
+// The change mask of word t of a row of R checks: change_mask, with the padding lanes of the row's
+// last word cleared.
+GCK_SEL_HD inline uint64_t change_row_mask(uint64_t old_word, uint64_t new_word, uint32_t transitions, uint32_t t,
+                                           uint32_t R) {
+  const uint32_t col0 = t * 32u;
+  if (col0 >= R) return 0;
+  uint64_t m = change_mask(old_word, new_word, transitions);
+  if (R - col0 < 32u) m &= (1ull << (2u * (R - col0))) - 1ull;
+  return m;
+}
+
+// The change mask of word t of a dense plane of n checks: change_mask, with the lanes at or beyond n
+// cleared (t < 2^27: a plane of fewer than 2^32 checks).
+GCK_SEL_HD inline uint64_t change_tail_mask(uint64_t old_word, uint64_t new_word, uint32_t transitions, uint32_t t,
+                                            uint32_t n) {
+  return change_row_mask(old_word, new_word, transitions, t, n);
+}
+
+// The changes of words begin, begin + stride, ... below `end` of a dense plane of n checks (old: null
+// reads as zeros): select_count_strided over two planes.
+GCK_SEL_HD inline uint32_t change_count_strided(const uint64_t* old_words, const uint64_t* new_words, uint32_t begin,
+                                                uint32_t end, uint32_t stride, uint32_t transitions, uint32_t n) {
+  uint32_t c = 0;
+  for (uint32_t t = begin; t < end; t += stride)
+    c += select_count(change_tail_mask(old_words ? old_words[t] : 0ull, new_words[t], transitions, t, n));
+  return c;
+}
+
+// A change's transition byte: 4 * old + new, its bit index in `transitions`.
+GCK_SEL_HD inline uint8_t change_byte(uint64_t old_word, uint64_t new_word, uint32_t bit) {
+  return (uint8_t)(4u * ((uint32_t)(old_word >> bit) & 3u) + ((uint32_t)(new_word >> bit) & 3u));
+}
+
+// Where the dense form's records go: SelectOut with the transition byte in place of the value.
+struct ChangeOut {
+  uint32_t* ids;
+  uint32_t* pos;
+  uint8_t* trans;
+  uint32_t cap;
+  const uint32_t* src_ids;
+  uint32_t first_id, pos0;
+};
+
+// The changes m of word t of the chunk, the first of them at `rank` of the request: each is written
+// while its rank is below cap. Ascending within the word.
+GCK_SEL_HD inline void change_write(uint64_t old_word, uint64_t new_word, uint64_t m, uint32_t t, uint32_t rank,
+                                    const ChangeOut& o) {
+  while (m && rank < o.cap) {
+    const uint32_t bit = (uint32_t)__builtin_ctzll(m);
+    m &= m - 1u;
+    const uint32_t i = t * 32u + (bit >> 1);
+    if (o.ids) o.ids[rank] = o.src_ids ? o.src_ids[i] : o.first_id + i;
+    if (o.pos) o.pos[rank] = o.pos0 + i;
+    if (o.trans) o.trans[rank] = change_byte(old_word, new_word, bit);
+    ++rank;
+  }
+}
+
+// Where the row form's records go: a change's id is src_ids[r], r its column.
+struct ChangeRowsOut {
+  uint32_t* ids;
+  uint32_t* col;
+  uint8_t* trans;
+  uint32_t cap;
+  const uint32_t* src_ids;
+};
+
+// The changes m of one word of a row (col0 = the column of its check 0), the first of them at in-row
+// rank `rank`; the row's first record is at `row_base` of the request. Each is written while its rank
+// in the request is below cap. Ascending within the word.
+GCK_SEL_HD inline void change_write_row(uint64_t old_word, uint64_t new_word, uint64_t m, uint32_t col0, uint32_t rank,
+                                        uint32_t row_base, const ChangeRowsOut& o) {
+  while (m) {
+    const uint32_t at = row_base + rank;
+    if (at >= o.cap) return;
+    const uint32_t bit = (uint32_t)__builtin_ctzll(m);
+    m &= m - 1u;
+    const uint32_t r = col0 + (bit >> 1);
+    if (o.ids) o.ids[at] = o.src_ids[r];
+    if (o.col) o.col[at] = r;
+    if (o.trans) o.trans[at] = change_byte(old_word, new_word, bit);
+    ++rank;
+  }
+}
 
 }  // namespace gck

@@ -187,10 +187,37 @@ class SelectGroups(C.Structure):
                 ("d_out_perm", C.c_void_p), ("cap", C.c_size_t), ("d_out_n", C.c_void_p)]
 
 
+class SelectChanges(C.Structure):
+    """gck_select_changes (include/gck.h): which transitions a recheck request over a dense plane
+    reports, and the device arrays the change records go to."""
+    _fields_ = [("transitions", C.c_uint32), ("reserved", C.c_uint32), ("d_out_ids", C.c_void_p),
+                ("d_out_pos", C.c_void_p), ("d_out_trans", C.c_void_p), ("cap", C.c_size_t), ("d_out_n", C.c_void_p)]
+
+
+class SelectRowChanges(C.Structure):
+    """gck_select_row_changes (include/gck.h): which transitions a recheck cross request reports, and
+    the device arrays of the CSR by subject the change records go to."""
+    _fields_ = [("transitions", C.c_uint32), ("reserved", C.c_uint32), ("d_out_row_off", C.c_void_p),
+                ("d_out_ids", C.c_void_p), ("d_out_col", C.c_void_p), ("d_out_trans", C.c_void_p),
+                ("cap", C.c_size_t), ("d_out_n", C.c_void_p)]
+
+
 SELECT_NO = 1 << PERM_NO                       # GCK_SELECT_NO
 SELECT_HAS = 1 << PERM_HAS                     # GCK_SELECT_HAS
 SELECT_CONDITIONAL = 1 << PERM_CONDITIONAL     # GCK_SELECT_CONDITIONAL
 SELECT_LOOKUP = SELECT_HAS | SELECT_CONDITIONAL  # GCK_SELECT_LOOKUP: LookupResources' rule
+
+# A transition (old value v, new value w) of PERM_* is bit 4 * v + w of a `transitions` word, and a
+# change record's transition byte is that bit index.
+CHANGE_GAINED = 0x00CC  # GCK_CHANGE_GAINED: {UNSPECIFIED, NO} -> {HAS, CONDITIONAL}
+CHANGE_LOST = 0x3300    # GCK_CHANGE_LOST: {HAS, CONDITIONAL} -> {UNSPECIFIED, NO}
+CHANGE_ANY = 0x7BDE     # GCK_CHANGE_ANY: every pair of different values
+
+
+def change_split(trans):
+    """A change record's transition byte (an int, or an array of them) as (old, new) PERM_* values."""
+    return trans >> 2, trans & 3
+
 
 CROSS_IDS = 2048  # GCK_CROSS_IDS
 VARY_RESOURCE = 1  # GCK_VARY_RESOURCE: a list request's ids are resource ids (the fixed id is the subject's)
@@ -432,6 +459,25 @@ _SIGS = {
                                                   C.POINTER(C.c_size_t), C.c_size_t, C.c_int64,
                                                   C.POINTER(SelectGroups), _P, _P, C.c_size_t, _P, C.c_uint32, _P,
                                                   C.POINTER(_P)]),
+    "gck_diff_planes_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_uint32, C.POINTER(SelectChanges), _P]),
+    "gck_diff_cross_planes_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, _P, C.POINTER(SelectRowChanges), _P]),
+    "gck_recheck_list_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), C.c_uint32, C.c_uint32, _P,
+                                          C.c_uint32, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                          C.c_size_t, C.c_int64, _P, C.POINTER(SelectChanges), _P, _P, C.c_size_t, _P,
+                                          _P, C.POINTER(C.c_uint64)]),
+    "gck_recheck_submit_list_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), C.c_uint32,
+                                                 C.c_uint32, _P, C.c_uint32, C.c_size_t, C.POINTER(C.c_char_p),
+                                                 C.POINTER(C.c_size_t), C.c_size_t, C.c_int64, _P,
+                                                 C.POINTER(SelectChanges), _P, _P, C.c_size_t, _P, C.c_uint32, _P,
+                                                 C.POINTER(_P)]),
+    "gck_recheck_cross_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), _P, C.c_size_t, _P,
+                                           C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t,
+                                           C.c_int64, _P, C.POINTER(SelectRowChanges), _P, _P, C.c_size_t, _P, _P,
+                                           C.POINTER(C.c_uint64)]),
+    "gck_recheck_submit_cross_device": (C.c_int, [_P, C.POINTER(_Consistency), C.POINTER(Uniform), _P, C.c_size_t, _P,
+                                                  C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t,
+                                                  C.c_int64, _P, C.POINTER(SelectRowChanges), _P, _P, C.c_size_t, _P,
+                                                  C.c_uint32, _P, C.POINTER(_P)]),
     "gck_lookup_resources_among": (C.c_int, [_P, C.POINTER(_Consistency), C.c_uint16, C.c_uint16, C.c_uint16,
                                              C.c_uint16, C.c_uint32, _P, C.c_size_t, C.c_int64, _P, _P, C.c_size_t,
                                              C.POINTER(C.c_size_t)]),
@@ -1749,6 +1795,208 @@ class Engine:
         if want_perm:
             out += (out_perm[:total],)
         return out
+
+    # ---- recheck requests (gck_recheck_list_device, gck_recheck_cross_device): a list or cross device
+    # request evaluated again and compared on the device with the caller's previous plane. d_prev_packed:
+    # that plane (0: all zeros); d_out_packed: the new one (required; the next call's previous plane);
+    # d_out_n: one u32 (required); the record arrays (u32, u32, u8 transition bytes): `cap` entries each,
+    # 0: not wanted. `transitions`: CHANGE_*.
+    def diff_planes_device(self, d_old: int, d_new: int, n: int, d_out_n: int, cap: int, d_ids: int = 0,
+                           first_id: int = 0, d_out_ids: int = 0, d_out_pos: int = 0, d_out_trans: int = 0,
+                           transitions: int = CHANGE_ANY, stream: Optional[int] = None) -> None:
+        """gck_diff_planes_device: the changes between two dense planes of n checks the caller holds
+        (d_old = 0: all zeros), in ascending position; synchronous on `stream`."""
+        sel = SelectChanges(transitions, 0, d_out_ids or None, d_out_pos or None, d_out_trans or None, cap,
+                            d_out_n or None)
+        _check(self._lib.gck_diff_planes_device(self._h, d_old or None, d_new or None, n, d_ids or None, first_id,
+                                                C.byref(sel), stream))
+
+    def diff_cross_planes_device(self, d_old: int, d_new: int, n_subjects: int, n_resources: int, d_resources: int,
+                                 d_out_row_off: int, d_out_n: int, cap: int, d_out_ids: int = 0, d_out_col: int = 0,
+                                 d_out_trans: int = 0, transitions: int = CHANGE_ANY,
+                                 stream: Optional[int] = None) -> None:
+        """gck_diff_cross_planes_device: the changes between two cross planes of S x R checks, as a CSR
+        by subject; synchronous on `stream`."""
+        sel = SelectRowChanges(transitions, 0, d_out_row_off or None, d_out_ids or None, d_out_col or None,
+                               d_out_trans or None, cap, d_out_n or None)
+        _check(self._lib.gck_diff_cross_planes_device(self._h, d_old or None, d_new or None, n_subjects, n_resources,
+                                                      d_resources or None, C.byref(sel), stream))
+
+    def recheck_list_device(self, header, fixed_id: int, vary: int, n: int, d_prev_packed: int, d_out_packed: int,
+                            d_out_n: int, cap: int, d_out_ids: int = 0, d_out_pos: int = 0, d_out_trans: int = 0,
+                            transitions: int = CHANGE_ANY, d_ids: int = 0, first_id: int = 0, d_out_errs: int = 0,
+                            err_cap: int = 0, d_out_n_errs: int = 0, stream: Optional[int] = None,
+                            requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                            contexts: Optional[Sequence] = None) -> int:
+        """gck_recheck_list_device: check_list_device into d_out_packed, then the checks whose value
+        differs from d_prev_packed's by a selected transition: ids, positions and transition bytes into
+        the device arrays, their number into *d_out_n. Returns the evaluated revision."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        sel = SelectChanges(transitions, 0, d_out_ids or None, d_out_pos or None, d_out_trans or None, cap,
+                            d_out_n or None)
+        rev = C.c_uint64(0)
+        _check(self._lib.gck_recheck_list_device(self._h, C.byref(cs), C.byref(hdr), fixed_id, vary, d_ids or None,
+                                                 first_id, n, *tail[:4], d_prev_packed or None, C.byref(sel), *tail[4:],
+                                                 stream, C.byref(rev)))
+        return rev.value
+
+    def submit_recheck_list_device(self, header, fixed_id: int, vary: int, n: int, d_prev_packed: int,
+                                   d_out_packed: int, d_out_n: int, cap: int, d_out_ids: int = 0, d_out_pos: int = 0,
+                                   d_out_trans: int = 0, transitions: int = CHANGE_ANY, d_ids: int = 0,
+                                   first_id: int = 0, d_out_errs: int = 0, err_cap: int = 0, d_out_n_errs: int = 0,
+                                   stream: Optional[int] = None, engine_stream: bool = False,
+                                   requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                                   contexts: Optional[Sequence] = None) -> "DeviceCompactBatch":
+        """gck_recheck_submit_list_device: as submit_list_device, with recheck_list_device's outputs."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        sel = SelectChanges(transitions, 0, d_out_ids or None, d_out_pos or None, d_out_trans or None, cap,
+                            d_out_n or None)
+        b = DeviceCompactBatch(self, hdr)
+        _check(self._lib.gck_recheck_submit_list_device(self._h, C.byref(cs), C.byref(hdr), fixed_id, vary,
+                                                        d_ids or None, first_id, n, *tail[:4], d_prev_packed or None,
+                                                        C.byref(sel), *tail[4:],
+                                                        SUBMIT_ENGINE_STREAM if engine_stream else 0, stream,
+                                                        C.byref(b._h)))
+        return b
+
+    def recheck_cross_device(self, header, d_subjects: int, n_subjects: int, d_resources: int, n_resources: int,
+                             d_prev_packed: int, d_out_packed: int, d_out_row_off: int, d_out_n: int, cap: int,
+                             d_out_ids: int = 0, d_out_col: int = 0, d_out_trans: int = 0,
+                             transitions: int = CHANGE_ANY, d_out_errs: int = 0, err_cap: int = 0, d_out_n_errs: int = 0,
+                             stream: Optional[int] = None, requirement: int = CONSISTENCY_MIN_LATENCY,
+                             revision: int = 0, now_us: int = 0, contexts: Optional[Sequence] = None) -> int:
+        """gck_recheck_cross_device: check_cross_device into d_out_packed, then each subject's checks
+        whose value differs from d_prev_packed's by a selected transition, as a CSR: row offsets, resource
+        ids, columns and transition bytes, their number into *d_out_n. Returns the evaluated revision."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        sel = SelectRowChanges(transitions, 0, d_out_row_off or None, d_out_ids or None, d_out_col or None,
+                               d_out_trans or None, cap, d_out_n or None)
+        rev = C.c_uint64(0)
+        _check(self._lib.gck_recheck_cross_device(self._h, C.byref(cs), C.byref(hdr), d_subjects or None, n_subjects,
+                                                  d_resources or None, n_resources, *tail[:4], d_prev_packed or None,
+                                                  C.byref(sel), *tail[4:], stream, C.byref(rev)))
+        return rev.value
+
+    def submit_recheck_cross_device(self, header, d_subjects: int, n_subjects: int, d_resources: int,
+                                    n_resources: int, d_prev_packed: int, d_out_packed: int, d_out_row_off: int,
+                                    d_out_n: int, cap: int, d_out_ids: int = 0, d_out_col: int = 0,
+                                    d_out_trans: int = 0, transitions: int = CHANGE_ANY, d_out_errs: int = 0,
+                                    err_cap: int = 0, d_out_n_errs: int = 0, stream: Optional[int] = None,
+                                    engine_stream: bool = False, requirement: int = CONSISTENCY_MIN_LATENCY,
+                                    revision: int = 0, now_us: int = 0,
+                                    contexts: Optional[Sequence] = None) -> "DeviceCompactBatch":
+        """gck_recheck_submit_cross_device (one device tile): as submit_cross_device, with
+        recheck_cross_device's outputs."""
+        hdr = header if isinstance(header, Uniform) else _header(header)
+        cs, tail = self._device_tail(requirement, revision, now_us, contexts, d_out_packed, d_out_errs, err_cap,
+                                     d_out_n_errs)
+        sel = SelectRowChanges(transitions, 0, d_out_row_off or None, d_out_ids or None, d_out_col or None,
+                               d_out_trans or None, cap, d_out_n or None)
+        b = DeviceCompactBatch(self, hdr)
+        _check(self._lib.gck_recheck_submit_cross_device(self._h, C.byref(cs), C.byref(hdr), d_subjects or None,
+                                                         n_subjects, d_resources or None, n_resources, *tail[:4],
+                                                         d_prev_packed or None, C.byref(sel), *tail[4:],
+                                                         SUBMIT_ENGINE_STREAM if engine_stream else 0, stream,
+                                                         C.byref(b._h)))
+        return b
+
+    @staticmethod
+    def _prev_plane(name, prev, words, dev):
+        import torch
+        if prev is None:
+            return 0
+        if prev.dtype != torch.int64 or prev.device != dev or prev.numel() != words or not prev.is_contiguous():
+            raise GckError(GCK_E_INVALID_ARGUMENT, f"{name}: prev must be the contiguous int64 plane of {words} words "
+                                                   "an earlier call of the same request returned")
+        return prev.data_ptr() if words else 0
+
+    def recheck_ids(self, header, fixed_id: int, vary: int, ids=None, first_id: int = 0, n: Optional[int] = None,
+                    prev=None, transitions: int = CHANGE_ANY, requirement: int = CONSISTENCY_MIN_LATENCY,
+                    revision: int = 0, now_us: int = 0, contexts: Optional[Sequence] = None):
+        """A list request evaluated now and compared with `prev`, the plane an earlier call of the same
+        request returned (None: all zeros, so CHANGE_GAINED yields the initial grant set). `ids` is a
+        device int32 / uint32 tensor of varying ids (None: the range first_id .. first_id + n - 1).
+        Returns (plane, revision, ids, pos, trans): the new plane (int64 [ceil(n / 32)], the next call's
+        `prev`), the evaluated revision, and the changed checks in ascending position — their ids (in
+        the tensor's dtype), positions (int32) and transition bytes (uint8; change_split). Runs
+        recheck_list_device on the current stream and reads back the two count words, the call's only
+        copy to the host. A per-item error is no failure here: the check reads 0 in the plane, and 0
+        is a legal end of a transition."""
+        import torch
+        if ids is not None:
+            if ids.dtype not in (torch.int32, torch.uint32) or not ids.is_cuda:
+                raise GckError(GCK_E_INVALID_ARGUMENT, "recheck_ids: ids must be a device int32 / uint32 tensor")
+            ids = ids.contiguous().reshape(-1)
+            n, dev, dtype = ids.numel(), ids.device, ids.dtype
+        else:
+            if n is None:
+                raise GckError(GCK_E_INVALID_ARGUMENT, "recheck_ids: a range needs n")
+            dev, dtype = torch.device("cuda", self.device), torch.int32
+        words = (n + 31) // 32
+        d_prev = self._prev_plane("recheck_ids", prev, words, dev)
+        with torch.cuda.device(dev):
+            plane = torch.empty(max(1, words), dtype=torch.int64, device=dev)  # (required, also when empty)
+            counts = torch.empty(2, dtype=torch.int32, device=dev)  # [changes, errors]
+            out_ids = torch.empty(n, dtype=dtype, device=dev)
+            out_pos = torch.empty(n, dtype=torch.int32, device=dev)
+            out_trans = torch.empty(n, dtype=torch.uint8, device=dev)
+            rev = self.recheck_list_device(header, fixed_id, vary, n, d_prev, plane.data_ptr(), counts.data_ptr(), n,
+                                           d_out_ids=out_ids.data_ptr() if n else 0,
+                                           d_out_pos=out_pos.data_ptr() if n else 0,
+                                           d_out_trans=out_trans.data_ptr() if n else 0, transitions=transitions,
+                                           d_ids=ids.data_ptr() if ids is not None and n else 0, first_id=first_id,
+                                           d_out_n_errs=counts.data_ptr() + 4,
+                                           stream=torch.cuda.current_stream(dev).cuda_stream, requirement=requirement,
+                                           revision=revision, now_us=now_us, contexts=contexts)
+            total = int(counts[0].item()) & 0xFFFFFFFF
+        return plane[:words], rev, out_ids[:total], out_pos[:total], out_trans[:total]
+
+    def recheck_cross_ids(self, header, subjects, resources, prev=None, transitions: int = CHANGE_ANY,
+                          requirement: int = CONSISTENCY_MIN_LATENCY, revision: int = 0, now_us: int = 0,
+                          contexts: Optional[Sequence] = None):
+        """A cross request evaluated now and compared with `prev`, the plane an earlier call of the same
+        request returned (None: all zeros). Returns (plane, revision, row_off, ids, col, trans): the new
+        plane (int64 [S, ceil(R / 32)], check_cross_ids' layout and the next call's `prev`), the
+        evaluated revision, and the changes as a CSR by subject — row_off an int32 [S + 1] tensor, and
+        at row_off[s] .. row_off[s + 1] subject s's changed resources in list order: their ids (in the
+        resources' dtype), columns (int32) and transition bytes (uint8; change_split). Runs
+        recheck_cross_device on the current stream and reads back the two count words. A per-item error
+        is no failure here: the check reads 0 in the plane."""
+        import torch
+        for name, t in (("subjects", subjects), ("resources", resources)):
+            if t.dtype not in (torch.int32, torch.uint32) or not t.is_cuda:
+                raise GckError(GCK_E_INVALID_ARGUMENT, f"recheck_cross_ids: {name} must be a device int32 / uint32 tensor")
+        if subjects.device != resources.device:
+            raise GckError(GCK_E_INVALID_ARGUMENT, "recheck_cross_ids: the two lists are on different devices")
+        subjects, resources = subjects.contiguous().reshape(-1), resources.contiguous().reshape(-1)
+        S, R, dev = subjects.numel(), resources.numel(), subjects.device
+        stride = (R + 31) // 32
+        d_prev = self._prev_plane("recheck_cross_ids", prev, S * stride, dev)
+        cap = S * R
+        with torch.cuda.device(dev):
+            plane = torch.empty(max(1, S * stride), dtype=torch.int64, device=dev)  # (required, also when empty)
+            row_off = torch.empty(S + 1, dtype=torch.int32, device=dev)
+            counts = torch.empty(2, dtype=torch.int32, device=dev)  # [changes, errors]
+            out_ids = torch.empty(cap, dtype=resources.dtype, device=dev)
+            out_col = torch.empty(cap, dtype=torch.int32, device=dev)
+            out_trans = torch.empty(cap, dtype=torch.uint8, device=dev)
+            rev = self.recheck_cross_device(header, subjects.data_ptr() if cap else 0, S,
+                                            resources.data_ptr() if cap else 0, R, d_prev, plane.data_ptr(),
+                                            row_off.data_ptr(), counts.data_ptr(), cap,
+                                            d_out_ids=out_ids.data_ptr() if cap else 0,
+                                            d_out_col=out_col.data_ptr() if cap else 0,
+                                            d_out_trans=out_trans.data_ptr() if cap else 0, transitions=transitions,
+                                            d_out_n_errs=counts.data_ptr() + 4,
+                                            stream=torch.cuda.current_stream(dev).cuda_stream, requirement=requirement,
+                                            revision=revision, now_us=now_us, contexts=contexts)
+            total = int(counts[0].item()) & 0xFFFFFFFF
+        return plane[:S * stride].reshape(S, stride), rev, row_off, out_ids[:total], out_col[:total], out_trans[:total]
 
     def device_compact_stats(self) -> Tuple[int, int]:
         """gck_device_compact_stats: chunks of device requests whose join read and wrote the caller's

@@ -63,6 +63,10 @@
  *   gck_filter_cross_cols_device / gck_filter_submit_cross_cols_device
  *       its mirror: each resource's surviving subjects, optionally the first K of them, as a CSR by
  *       resource (column offsets, ids, rows, Permissionships).
+ *   gck_recheck_list_device / gck_recheck_cross_device, their gck_recheck_submit_* forms and
+ *   gck_diff_planes_device / gck_diff_cross_planes_device
+ *       the list and cross device requests evaluated again after a Watch batch and compared on the
+ *       device with the caller's previous plane: the ordered records of the checks that changed.
  *
  * Ownership: all inputs and outputs are caller-allocated; the engine never retains a caller
  * pointer after a call returns, except that gck_check_submit keeps the output pointers (and, for
@@ -900,6 +904,102 @@ int gck_filter_submit_groups_device(gck_engine* e, const gck_consistency* cs, co
                                     const gck_select_groups* sel, uint64_t* d_out_packed, gck_item_error* d_out_errs,
                                     size_t err_cap, uint32_t* d_out_n_errs, uint32_t flags, void* stream,
                                     gck_batch** out);
+
+/* ---- recheck requests (ABI 13, additive) ----------------------------------------------
+ * "What changed since the plane I kept?" A list or cross device request is evaluated at the current
+ * revision and compared on the device with the caller's previous plane of the same request (device
+ * memory, the layout the call itself writes). The answer is the new plane plus the ordered records of
+ * the checks whose value changed; nothing but the count words (*d_out_n, *d_out_n_errs) needs to cross
+ * PCIe. The use: an ACL column of a search or vector index, a per-user cache of visible documents, a
+ * denormalised permission-set table — anything that keeps an answer across Watch batches
+ * (gck_apply_updates) and must patch it.
+ * A transition is a pair (old value v, new value w) of GCK_PERM_*, v != w. `transitions` has bit
+ * 4 * v + w set when that pair is selected; it is valid iff it is non-zero and lies within
+ * GCK_CHANGE_ANY. Value 0 (GCK_PERM_UNSPECIFIED: an errored check, or a previous plane that is NULL) is
+ * a legal end of a transition: a check that had a GCK_ITEM_* error and now is HAS is a real change. A
+ * change's transition byte is 4 * old + new, its bit index in `transitions`.
+ * d_prev_packed: the previous plane, ceil(n / 32) words (list) or S rows of ceil(R / 32) words (cross),
+ * 8-byte aligned; NULL reads as all zeros, so a first call with GCK_CHANGE_GAINED yields the initial
+ * grant set. Its padding lanes may hold anything: a change's position is below n, its column below R.
+ * Its range must not overlap d_out_packed's. d_out_packed is required, is written exactly as
+ * gck_check_bulk_list_device / gck_check_bulk_cross_device write it, and is the previous plane of the
+ * caller's next call.
+ * The check itself is the list or cross device call's, unchanged in every respect (tiling, in-place
+ * and expanded paths, fallbacks, stream ordering and `flags`, consistency, error records, the
+ * evaluated revision). The comparison is a request-level step behind the last chunk or tile of the
+ * synchronous form, and in the wait of a submitted batch.
+ *   gck_select_changes (list form): records (varying id, position, transition byte) in ascending
+ *     position; record k goes to every array that is not NULL iff k < cap; *d_out_n = the number of
+ *     changes of the whole request, always written (for n == 0 too).
+ *   gck_select_row_changes (cross form): a CSR by subject. d_out_row_off[0] = 0, row_off[s + 1] =
+ *     row_off[s] + the changes of row s; all S + 1 entries always written (S == 0: row_off[0] alone;
+ *     R == 0: S + 1 zeros). Change j of row s, ascending in r, has rank row_off[s] + j; its resource id
+ *     (d_resources[r]), its column r and its transition byte go to every array that is not NULL iff
+ *     rank < cap. *d_out_n = row_off[S], always written. There is no per-row limit.
+ * Entries at and beyond min(total, cap) stay untouched. The structs are copied by the call (the submit
+ * call included). GCK_E_INVALID_ARGUMENT, nothing launched and nothing written, for a NULL struct, bad
+ * `transitions`, reserved != 0, a missing required pointer (d_out_n; d_out_row_off; d_out_packed of a
+ * request call; the new plane of a plane-only call with checks), cap > 0 with all three record arrays
+ * NULL, a plane that is not 8-byte aligned or any other pointer that is not 4-byte aligned, a
+ * d_prev_packed range that overlaps d_out_packed's, and everything the underlying call refuses.
+ * gck_device_compact_stats counts a recheck as the list or cross device request it is.
+ * Out of scope: a group-segmented form (a group request's plane is dense: use the dense form and map
+ * positions with the offsets), and a diff combined with a survivor filter in one call. */
+#define GCK_CHANGE_GAINED 0x00CCu /* {UNSPECIFIED, NO} -> {HAS, CONDITIONAL} */
+#define GCK_CHANGE_LOST   0x3300u /* {HAS, CONDITIONAL} -> {UNSPECIFIED, NO} */
+#define GCK_CHANGE_ANY    0x7BDEu /* every pair of different values */
+typedef struct gck_select_changes {
+  uint32_t transitions;  /* GCK_CHANGE_*: != 0, within GCK_CHANGE_ANY */
+  uint32_t reserved;     /* 0 */
+  uint32_t* d_out_ids;   /* device, cap entries, may be NULL: the changed check's varying id (ids[i] or first_id + i) */
+  uint32_t* d_out_pos;   /* device, cap entries, may be NULL: its position i in the request */
+  uint8_t*  d_out_trans; /* device, cap entries, may be NULL: 4 * old + new */
+  size_t    cap;
+  uint32_t* d_out_n;     /* device, required: the changes of the whole request */
+} gck_select_changes;    /* 48 bytes */
+typedef struct gck_select_row_changes {
+  uint32_t transitions;    /* GCK_CHANGE_*: != 0, within GCK_CHANGE_ANY */
+  uint32_t reserved;       /* 0 */
+  uint32_t* d_out_row_off; /* device, S + 1 entries, required */
+  uint32_t* d_out_ids;     /* device, cap entries, may be NULL: resources[r] of a change */
+  uint32_t* d_out_col;     /* device, cap entries, may be NULL: its position r in the resource list */
+  uint8_t*  d_out_trans;   /* device, cap entries, may be NULL: 4 * old + new */
+  size_t    cap;
+  uint32_t* d_out_n;       /* device, required: the changes of the whole request (== row_off[S]) */
+} gck_select_row_changes;  /* 56 bytes */
+/* The comparison alone, for a caller that already holds both planes (any dense plane: a uniform,
+ * shaped, list or group request's; or a cross plane). d_ids: the n varying ids, or NULL for
+ * first_id + i. Synchronous on `stream`; needs a committed snapshot, as every device call does. */
+int gck_diff_planes_device(gck_engine* e, const uint64_t* d_old, const uint64_t* d_new, size_t n, const uint32_t* d_ids,
+                           uint32_t first_id, const gck_select_changes* sel, void* stream);
+int gck_diff_cross_planes_device(gck_engine* e, const uint64_t* d_old, const uint64_t* d_new, size_t n_subjects,
+                                 size_t n_resources, const uint32_t* d_resources, const gck_select_row_changes* sel,
+                                 void* stream);
+int gck_recheck_list_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                            uint32_t vary, const uint32_t* d_ids, uint32_t first_id, size_t n,
+                            const char* const* contexts, const size_t* context_lens, size_t n_contexts, int64_t now_us,
+                            const uint64_t* d_prev_packed, const gck_select_changes* sel, uint64_t* d_out_packed,
+                            gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, void* stream,
+                            uint64_t* out_revision);
+int gck_recheck_submit_list_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr, uint32_t fixed_id,
+                                   uint32_t vary, const uint32_t* d_ids, uint32_t first_id, size_t n,
+                                   const char* const* contexts, const size_t* context_lens, size_t n_contexts,
+                                   int64_t now_us, const uint64_t* d_prev_packed, const gck_select_changes* sel,
+                                   uint64_t* d_out_packed, gck_item_error* d_out_errs, size_t err_cap,
+                                   uint32_t* d_out_n_errs, uint32_t flags, void* stream, gck_batch** out);
+int gck_recheck_cross_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr,
+                             const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                             size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                             size_t n_contexts, int64_t now_us, const uint64_t* d_prev_packed,
+                             const gck_select_row_changes* sel, uint64_t* d_out_packed, gck_item_error* d_out_errs,
+                             size_t err_cap, uint32_t* d_out_n_errs, void* stream, uint64_t* out_revision);
+int gck_recheck_submit_cross_device(gck_engine* e, const gck_consistency* cs, const gck_uniform* hdr,
+                                    const uint32_t* d_subjects, size_t n_subjects, const uint32_t* d_resources,
+                                    size_t n_resources, const char* const* contexts, const size_t* context_lens,
+                                    size_t n_contexts, int64_t now_us, const uint64_t* d_prev_packed,
+                                    const gck_select_row_changes* sel, uint64_t* d_out_packed,
+                                    gck_item_error* d_out_errs, size_t err_cap, uint32_t* d_out_n_errs, uint32_t flags,
+                                    void* stream, gck_batch** out);
 
 /* ---- lookups (Client.LookupResources / LookupSubjects, client/client.go:508-599) -------- */
 /* Ids of the `resource_type` objects on which the subject has `permission` — HAS or CONDITIONAL,
